@@ -9,6 +9,10 @@ data-path collective, so N GPUs = N independent batch-32 shards (
 communication is the timing barrier.  Inputs (resized 300x300 slices, targets, weights) are resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0.
 
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: set up, W warm-up steps, N timed steps, the
+outputs of the last timed step if --dump-outputs DIR is given, the line.  Everything below except `value` is measured under --full
+(the --no-* options then pick among the legs); without it those fields of the line are null and `full` is false.
+
   value        : EXACTLY --steps timed steps between barrier + synchronize pairs, max over ranks.  `steady` repeats the
                  measurement over 100 more steps (>= 1 s of GPU time) so the short default region can be judged.
   roofline     : the dominant hand-written kernel instance (most time in two untimed survey passes that bracket every tagged
@@ -103,7 +107,7 @@ def compact_line(full, detail_path=None):
     """The ONE stdout line: the contract's fields + `roofline` + `cpu_baseline` + short summaries of the other legs, <= LINE_LIMIT
     bytes.  Everything else (per-kernel tables, per-layer trunk table, notes) lives in the detail file."""
     line = _pick(full, ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
-                        'vs_baseline', 'dtype', 'data'))
+                        'vs_baseline', 'dtype', 'data', 'full'))
     cfg = full.get('config') or {}
     line['config'] = dict(_pick(cfg, ('batch_per_gpu', 'global_batch', 'alg_gflop_per_img', 'alg_mb_per_img')),
                           workload=str(cfg.get('workload_short') or cfg.get('workload', ''))[:200])
@@ -169,6 +173,23 @@ def write_detail(full, path):
     except OSError as e:
         print(f'bench.py: could not write {path}: {e}', file=sys.stderr)
         return None
+
+
+DUMP_LIMIT = 64 << 20      # bytes of --dump-outputs in all
+
+
+def dump_outputs(arrays, d):
+    """--dump-outputs: every array as d/<name>.npy (float32).  Past DUMP_LIMIT in all (a --batch far above the default), each large array
+    is cut to a fixed, seeded sample of its flattened elements: the same elements in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(4 * v.size for v in arrays.values())
+    for k, v in arrays.items():
+        v = np.ascontiguousarray(v, np.float32)
+        if total > DUMP_LIMIT and v.size > 1024:
+            idx = np.random.default_rng(0).choice(v.size, max(1024, v.size * (DUMP_LIMIT - 65536) // total), replace=False)
+            v = v.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(d, k + '.npy'), v)
 
 
 def cpu_baseline(cfg_name, sample_b, seed, twin=None):
@@ -312,8 +333,9 @@ def trunk_roofline(survey, n_pass, B, dtype):
                 note='eager survey passes, every trunk launch bracketed by HIP events on the launch stream')
 
 
-def measure(cfg, a, dev, gd, rank, world, dtype='f32'):
-    """Build the net of one config on this rank, time --steps forward + loss steps; returns the result dict."""
+def measure(cfg, a, dev, gd, rank, world, dtype='f32', dump=False):
+    """Build the net of one config on this rank, time --steps forward + loss steps; returns the result dict.  `dump`: keep what the
+    last timed step returned (loc, conf, priors, the two losses) as float32 arrays under `outputs`."""
     from gssd import synth
     from layers.modules import MultiBoxLoss
     from models.ssd_multiphase_custom_group import build_ssd
@@ -329,9 +351,12 @@ def measure(cfg, a, dev, gd, rank, world, dtype='f32'):
     x = synth.synth_images(B, seed=gd.shard_seed(100, rank)).to(dev)      # rank r owns its own 32 images
     tg = [t.to(dev) for t in synth.synth_targets(B, seed=gd.shard_seed(100, rank))]
 
+    last = {}                       # the forward's outputs of the most recent step (--dump-outputs)
+
     def step():
         with torch.no_grad():
-            return crit(net(x), tg)
+            last['out'] = net(x)
+            return crit(last['out'], tg)
 
     def sync():
         gd.barrier(dev)
@@ -398,6 +423,12 @@ def measure(cfg, a, dev, gd, rank, world, dtype='f32'):
     sync()
     dt = time.perf_counter() - t0
     net.__dict__['_events'] = None
+    # what the last timed step handed its caller, copied before anything else runs on this net
+    outputs = None
+    if dump:
+        loc, conf, pri = last['out']
+        outputs = dict(loc=loc, conf=conf, priors=pri, loss_l=ll, loss_c=lc)
+        outputs = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
     if events is not None and not inside:
         # event-record nodes INSIDE the step's hipGraph (round 6): the launches keep their place in the graph and their neighbours on the other
         # branches -- the same conditions as the timed region and as a rocprofv3 trace of it (bracketing them eagerly cut the graph around every
@@ -432,14 +463,16 @@ def measure(cfg, a, dev, gd, rank, world, dtype='f32'):
 
     # host side of a step: wall time this rank's Python needs to ENQUEUE a step (graph replays + loss launches), nothing waited for.
     # With 8 ranks on one host this -- not the GPU -- is what weak scaling can lose; max / per-rank values are reported.
-    sync()
-    nh = max(1, min(a.steps, 20))
-    t0 = time.perf_counter()
-    for _ in range(nh):
-        step()
-    host_ms = 1e3 * (time.perf_counter() - t0) / nh
-    sync()
-    host_per_rank = [round(t, 3) for t in gd.gather_over_ranks(host_ms, dev)]
+    host_per_rank = None
+    if a.full:
+        sync()
+        nh = max(1, min(a.steps, 20))
+        t0 = time.perf_counter()
+        for _ in range(nh):
+            step()
+        host_ms = 1e3 * (time.perf_counter() - t0) / nh
+        sync()
+        host_per_rank = [round(t, 3) for t in gd.gather_over_ranks(host_ms, dev)]
 
     roof, kernels = None, {}
     peak_t = PEAK_BF16_TFLOPS if dtype == 'bf16' else PEAK_F32_TFLOPS
@@ -545,7 +578,7 @@ def measure(cfg, a, dev, gd, rank, world, dtype='f32'):
                                frac_hbm_peak=round(value * mb_img / 1e3 / (PEAK_HBM_GBS * world), 4)),
                host_enqueue_ms_per_step=host_per_rank,
                first_step_loss=[round(first_loss[0], 5), round(first_loss[1], 5)], roofline=roof, roofline_hbm_trunk=roof_hbm,
-               trunk=trunk, kernels=kernels)
+               trunk=trunk, kernels=kernels, outputs=outputs)
     return res, net, crit, x, tg, first_loss
 
 
@@ -763,7 +796,22 @@ def main():
                          '(tests/test_host_cpu.py drives the self-launcher with it on the CPU)')
     ap.add_argument('--replay-detail', metavar='JSON', help='no GPU: read a full record (a detail file) and print the stdout line a run '
                                                             'would print from it (tests/test_host_cpu.py checks its size)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline: roofline events, steady, host enqueue, bf16 leg, input stage, secondary, '
+                         'PixelLink++, CPU baseline, full training steps and the detail file (the other options above pick among them); '
+                         'without it a run sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps write what the last timed step returned (loc, conf, priors, loss_l, loss_c) as '
+                         'DIR/<name>.npy, float32, at most 64 MB in all (rank 0)')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not a.full:
+        if a.full_step:
+            ap.error('--full-step K runs the training-step leg: it needs --full')
+        # a plain run: the headline's warm-up and timed steps, nothing else
+        a.no_events = a.no_bf16 = a.no_input_stage = a.no_secondary = True
+        a.steady, a.cpu_sample, a.full_step = 0, 0, 0
     if a.replay_detail:
         print(json.dumps(compact_line(json.load(open(a.replay_detail)), os.path.relpath(a.replay_detail, ROOT))), flush=True)
         return
@@ -800,7 +848,11 @@ def main():
     import copy
     import threading
     B = a.batch
-    res, net, crit, x, tg, loss = measure(a.config, a, dev, gd, rank, world, a.dtype)
+    res, net, crit, x, tg, loss = measure(a.config, a, dev, gd, rank, world, a.dtype, dump=bool(a.dump_outputs))
+    outputs = res.pop('outputs')
+    if outputs is not None and rank == 0:
+        dump_outputs(outputs, a.dump_outputs)
+    del outputs
 
     # BASELINE.json configs[4] (bf16 storage, bf16 MFMA, fp32 accumulate / BN statistics / loss / NMS) on the same workload: its
     # `roofline` is the HBM roofline of the WHOLE grouped-conv backbone (north_star's ">= 70 % HBM roofline on the backbone")
@@ -876,6 +928,7 @@ def main():
     secondary = None
     if world == 1 and not a.no_secondary and a.config == 'gssdpp':
         sres = measure('gssd', a, dev, gd, rank, world, a.dtype)[0]
+        sres.pop('outputs')
         secondary = dict(metric='512x512 4-phase CT img/s (fwd+loss)', unit='img/s', **sres)
         torch.cuda.empty_cache()
 
@@ -894,7 +947,7 @@ def main():
     line = {
         'metric': '512x512 4-phase CT img/s (fwd+loss)', 'value': res['value'], 'unit': 'img/s',
         'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': res['ms_per_step'],
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic',
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic', 'full': a.full,
         'config': {'workload': res['workload'], 'workload_short': WORKLOAD_SHORT[a.config] + (', bf16 storage' if a.dtype == 'bf16' else ''),
                    'batch_per_gpu': B, 'global_batch': B * world, 'priors': 8732,
                    'alg_gflop_per_img': res['alg_gflop_per_img'], 'alg_mb_per_img': res['alg_mb_per_img']},
@@ -918,7 +971,7 @@ def main():
                 line['full_step'] = full_step
             if rank == 0:
                 # the full record (per-kernel tables, per-layer trunk table, notes) goes to the detail file; stdout carries ONE short line
-                dp = write_detail(line, a.detail)
+                dp = write_detail(line, a.detail) if a.full else None
                 print(json.dumps(compact_line(line, dp and os.path.relpath(dp, ROOT))), flush=True)
             if code is not None:
                 os._exit(code)

@@ -29,7 +29,7 @@ def test_bench_two_ranks_code_path_on_one_gpu():
     gather, broadcast of the weights, the overlapped gradient reducer inside the full-step leg (its all-reduces really run, on
     ranges of the flat gradient buffer, while the backward is still enqueueing), the watchdog.  Not a measurement."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2', '--steady', '0',
-                        '--no-bf16', '--full-step', '2', '--batch', '8'], capture_output=True, text=True, timeout=1500,
+                        '--no-bf16', '--full', '--full-step', '2', '--batch', '8'], capture_output=True, text=True, timeout=1500,
                        env=dict(os.environ, GSSD_DIST_SAME_DEVICE='1', GSSD_DIST_BACKEND='gloo'))
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]
@@ -53,7 +53,7 @@ def test_bench_eight_ranks_code_path_on_one_gpu():
     # private directory instead of a loopback port picked ahead of rank 0's bind -- gssd/dist.py::init, bench.py::self_launch -- and there is
     # ONE attempt again, so a rendezvous failure is a test failure)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '2', '--steady', '0',
-                        '--no-bf16', '--no-events', '--full-step', '2', '--batch', '4'], capture_output=True, text=True, timeout=2400,
+                        '--no-bf16', '--no-events', '--full', '--full-step', '2', '--batch', '4'], capture_output=True, text=True, timeout=2400,
                        env=dict(os.environ, GSSD_DIST_SAME_DEVICE='1', GSSD_DIST_BACKEND='gloo'))
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert r.returncode == 0 and len(lines) == 1, f'rc {r.returncode}\n' + r.stderr[-4000:]
@@ -98,7 +98,7 @@ def test_bench_two_gpus_self_launched_rccl():
     """`python bench.py --gpus 2` (no launcher): two ranks, RCCL barrier + the full-step leg's overlapped gradient all-reduce."""
     if torch.cuda.device_count() < 2:
         pytest.skip('needs 2 GPUs in one box')
-    rc, lines, err = _bench('--gpus', '2', '--steps', '3', '--warmup', '2', '--steady', '0', '--no-bf16', '--full-step', '2')
+    rc, lines, err = _bench('--gpus', '2', '--steps', '3', '--warmup', '2', '--steady', '0', '--no-bf16', '--full', '--full-step', '2')
     assert rc == 0 and len(lines) == 1, err
     ln = lines[0]
     assert ln['n_gpus'] == 2 and ln['rccl_ranks'] == 2 and len(ln['per_rank_ms_per_step']) == 2 and ln['launcher'].startswith('self')

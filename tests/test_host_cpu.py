@@ -230,6 +230,33 @@ def test_bench_self_launch_two_ranks_rendezvous():
     assert rc == 7 and lines == []
 
 
+def test_bench_extra_legs_need_full():
+    """A plain run times the headline only: asking for the training-step leg without --full is an error before anything starts."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full-step', '2'], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and '--full' in r.stderr and not r.stdout.strip()
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: arrays as float32 .npy; past 64 MB in all, the same seeded sample of elements in every run."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    small = dict(loc=np.arange(12, dtype=np.float64).reshape(3, 4), loss_l=np.float32(1.5))
+    bench.dump_outputs(small, str(tmp_path / 'a'))
+    back = np.load(tmp_path / 'a' / 'loc.npy')
+    assert back.dtype == np.float32 and np.array_equal(back, small['loc']) and np.load(tmp_path / 'a' / 'loss_l.npy') == 1.5
+    big = dict(x=np.random.default_rng(1).standard_normal(20 << 20, dtype=np.float32), y=np.ones(3, np.float32))
+    for d in ('b', 'c'):
+        bench.dump_outputs(big, str(tmp_path / d))
+    size = sum(os.path.getsize(tmp_path / 'b' / f) for f in os.listdir(tmp_path / 'b'))
+    assert size <= bench.DUMP_LIMIT == 64 << 20 and size > 48 << 20
+    xb, xc = np.load(tmp_path / 'b' / 'x.npy'), np.load(tmp_path / 'c' / 'x.npy')
+    assert xb.dtype == np.float32 and xb.size < big['x'].size and np.array_equal(xb, xc)
+    assert np.array_equal(np.load(tmp_path / 'b' / 'y.npy'), big['y'])
+
+
 def test_bench_stdout_line_is_short_and_parses(tmp_path):
     """the driver keeps a bounded tail of stdout -- the ONE JSON line must stay under 8 KB (r04's 21.6 KB line left
     BENCH_r04.parsed = null).  Replays a full record of a real run (the committed round-4 detail, per-rank lists widened to 8 ranks)

@@ -39,6 +39,12 @@ class ConvDesc(C.Structure):
     ]
 
 
+class DcnGeom(C.Structure):
+    """struct gssd_dcn_geom (include/gssd_hip.h): geometry of the any-geometry DCNv2 sampling kernels."""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'H', 'W', 'C', 'x_stride', 'Ho', 'Wo', 'kh', 'kw', 'sh', 'sw', 'ph', 'pw', 'dh', 'dw', 'dg',
+                                         'off_stride', 'mask_stride', 'mask_logit')]
+
+
 class PlanOp(C.Structure):
     """struct gssd_plan_op (csrc/plan_run.hip): one LAUNCH / WAIT of a launch-plan segment."""
     _fields_ = [('kind', c_i), ('fn', c_i), ('stream', c_i), ('nargs', c_i), ('args', C.c_uint64 * 24)]
@@ -180,6 +186,8 @@ SIGNATURES = {
     'gssd_scale_cast_f64_f32': (c_i, [c_fp, c_fp, c_fp, c_i, c_fp]),
     'gssd_sa_sigma_grad_f32': (c_i, [c_fp, c_fp, c_fp, c_i, c_fp, c_fp]),
     'gssd_dcn_col2im_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp]),
+    'gssd_dcn_geo_im2col_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, C.POINTER(DcnGeom), c_i, c_i, c_fp]),
+    'gssd_dcn_geo_col2im_f32': (c_i, [c_fp] * 7 + [C.POINTER(DcnGeom), c_i, c_i, c_fp]),
     'gssd_match_batch': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_f, c_f, c_f, c_fp, c_fp, c_fp]),
     'gssd_reduce_max_f32': (c_i, [c_fp, c_i64, c_fp, c_i, c_fp]),
     'gssd_hnm_loss': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),

@@ -111,6 +111,8 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_spectral_norm_f32),
     GSSD_PLAN_FN(gssd_dcn_im2col_f32),
     GSSD_PLAN_FN(gssd_dcn_im2col_bf16),
+    GSSD_PLAN_FN(gssd_dcn_geo_im2col_f32),
+    GSSD_PLAN_FN(gssd_dcn_geo_col2im_f32),
     GSSD_PLAN_FN(gssd_dcn_pack_weight_f32),
     GSSD_PLAN_FN(gssd_dcn_forward_f32),
     GSSD_PLAN_FN(gssd_dcn_streamk_reset),

@@ -1,5 +1,5 @@
 """Parameter containers that mirror the reference's module tree (names, shapes, state-dict keys)
-so checkpoints load strictly in both directions.  They hold weights only; the arithmetic runs in
+so checkpoints load strictly in both directions.  Inside build_ssd / PixelLink they hold weights only; the arithmetic runs in
 the HIP engine (``gssd/engine.py``).
 
 Key compatibility (probed against the reference):
@@ -64,21 +64,64 @@ class Self_Attn(nn.Module):
         self.max_pool_factor = max_pool_factor
 
 
-class DCN(nn.Module):
-    """layers/dcn_v2_custom.py:18-89 (state only)."""
+def _pair(v):
+    return tuple(int(a) for a in v) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+class DCNv2(nn.Module):
+    """layers/dcn_v2_custom.py:18-55: modulated deformable conv with caller-supplied offsets and mask; any geometry.  ``forward`` runs
+    gssd.dcn_op.dcn_v2_conv (HIP sampling kernels + the HIP 1x1 contraction; fp32 CUDA tensors only)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, deformable_groups=1):
         super().__init__()
-        if (kernel_size, stride, padding, dilation) != (3, 1, 1, 1):
-            raise NotImplementedError('the path only uses 3x3 / stride 1 / pad 1 DCN (models/...group.py:170-179)')
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size, self.stride, self.padding, self.dilation = (3, 3), (1, 1), (1, 1), (1, 1)
+        self.kernel_size, self.stride, self.padding, self.dilation = _pair(kernel_size), _pair(stride), _pair(padding), _pair(dilation)
         self.deformable_groups = deformable_groups
-        n = in_channels * 9
-        stdv = 1.0 / math.sqrt(n)
-        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 3, 3).uniform_(-stdv, stdv))
+        kh, kw = self.kernel_size
+        stdv = 1.0 / math.sqrt(in_channels * kh * kw)
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kh, kw).uniform_(-stdv, stdv))
         self.bias = nn.Parameter(torch.zeros(out_channels))
-        self.conv_offset_mask = nn.Conv2d(in_channels, deformable_groups * 27, kernel_size=3, stride=1, padding=1,
-                                          bias=True)
+
+    def forward(self, input, offset, mask):
+        from .dcn_op import dcn_v2_conv
+        return dcn_v2_conv(input, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                           self.deformable_groups)
+
+
+class DCN(DCNv2):
+    """layers/dcn_v2_custom.py:58-89: DCNv2 whose offsets and mask come from ``conv_offset_mask`` (zero-initialised).  The engine
+    (build_ssd, PixelLink) reads its weights and runs only 3x3 / stride 1 / pad 1 / dilation 1; ``forward`` (the standalone module)
+    takes any square kernel with isotropic stride and padding -- the offset conv runs on the engine's conv descriptor, which has one
+    kernel size, one stride and one padding."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, deformable_groups=1):
+        kh, kw = _pair(kernel_size)
+        (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+        if kh != kw or sh != sw or ph != pw:
+            raise NotImplementedError(f'DCN: kernel {(kh, kw)}, stride {(sh, sw)}, padding {(ph, pw)}: the offset / mask conv runs on '
+                                      f'a conv with one square kernel, one stride and one padding (DCNv2 / dcn_v2_conv take any)')
+        if ph > kh - 1:
+            raise NotImplementedError(f'DCN: padding {ph} > kernel_size - 1: the offset conv\'s data gradient has no such form here')
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, deformable_groups)
+        self.conv_offset_mask = nn.Conv2d(in_channels, deformable_groups * 3 * kh * kw, kernel_size=self.kernel_size, stride=self.stride,
+                                          padding=self.padding, bias=True)
         self.conv_offset_mask.weight.data.zero_()
         self.conv_offset_mask.bias.data.zero_()
+
+    def is_engine_geometry(self):
+        """The geometry of the detector's DCN layers, the only one the engine's fused kernels run."""
+        return (self.kernel_size, self.stride, self.padding, self.dilation) == ((3, 3), (1, 1), (1, 1), (1, 1))
+
+    def forward(self, input):
+        """(out, offset) as the reference: offset = the first 2*dg*kh*kw channels of conv_offset_mask(input), mask = sigmoid of
+        the rest (applied inside the sampling kernel)."""
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        (dh, dw) = self.dilation
+        H, W = input.shape[2], input.shape[3]
+        om_size = ((H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1)
+        size = ((H + 2 * p - dh * (k - 1) - 1) // s + 1, (W + 2 * p - dw * (k - 1) - 1) // s + 1)
+        if om_size != size:
+            raise ValueError(f'DCN: dilation {self.dilation} makes the deformable conv\'s output {size} differ from the offset conv\'s '
+                             f'{om_size} (the reference\'s offset conv has no dilation)')
+        from .dcn_op import dcn_forward
+        return dcn_forward(self, input)

@@ -357,6 +357,9 @@ class PlanOpsMixin:
         9*Cin-deep contraction (csrc/dcn_fused.hip) -- no column buffer."""
         eng, B = self.eng, self.B
         m = eng.net.dcn_list[li]
+        if not m.is_engine_geometry():
+            raise _lib.GssdError(f'dcn_list.{li}: the engine runs 3x3 / stride 1 / pad 1 / dilation 1 DCN layers only (kernel '
+                                 f'{m.kernel_size}, stride {m.stride}, padding {m.padding}, dilation {m.dilation})')
         dg, Cout = m.deformable_groups, m.out_channels
         w_om = self._packed_conv(f'dcn_list.{li}.om', m.conv_offset_mask)
 

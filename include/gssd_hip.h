@@ -486,6 +486,34 @@ int gssd_dcn_forward_bf16(const void* x, const float* om, const void* w_packed, 
 int gssd_dcn_col2im_f32(const float* x, const float* om, const float* dcols, float* dx, float* dom, int B, int H, int W,
                         int C, int dg, int om_stride, gssd_stream_t stream);
 
+/* DCNv2 sampling for ANY geometry (csrc/dcn_geo.hip): the standalone operator of gssd/dcn_op.py (layers/dcn_v2_custom.py's DCNv2 / DCN /
+ * dcn_v2_conv with any kernel kh x kw, stride, padding, dilation and deformable group count dg, C % dg == 0; any C).  The engine's
+ * 3x3 / 1 / 1 / 1 path does not use it.  Sampling rules as oracle/gssd_oracle.py::dcn_v2_conv: tap k = i*kw + j of output pixel (ho, wo)
+ * samples at (ho*sh - ph + i*dh + dy, wo*sw - pw + j*dw + dx), dy / dx = offset channels d*2K + 2k / + 1 (K = kh*kw), modulation =
+ * mask channel d*K + k (sigmoid of it when mask_logit = 1: the raw conv_offset_mask output of DCN); zero unless -1 < y < H and
+ * -1 < x < W; bilinear, corners outside the map contribute 0.  x is NHWC [B][H][W] with x_stride floats per pixel (channels [0, C));
+ * offset / mask rows are NHWC [B][Ho][Wo] with their own pixel strides (one call can read the two slices of one [pixels][3*dg*K] map).
+ * Only batches [b0, b1) are processed (the host works in chunks to bound the column workspace); all element offsets are 64-bit. */
+typedef struct gssd_dcn_geom {
+    int32_t B, H, W, C, x_stride;
+    int32_t Ho, Wo;                 /* must equal the conv arithmetic of (H, W) */
+    int32_t kh, kw, sh, sw, ph, pw, dh, dw;
+    int32_t dg;
+    int32_t off_stride, mask_stride; /* floats between consecutive pixels of the offset / mask rows */
+    int32_t mask_logit;             /* 1: the mask channel is a logit (modulation = sigmoid); 0: it is the modulation itself */
+} gssd_dcn_geom;
+/* Forward: cols[(b - b0)*Ho*Wo + p][k*Cp + c] = m * bilinear sample of channel c, Cp = C rounded up to 4 (columns [C, Cp) are written
+ * zero): tap-major, the layout gssd_pack_conv_weight(w, wp, Cout, C, kh, kw, Cp, kh*kw*Cp) gives the weight, so the contraction is a
+ * 1x1 gssd_conv2d_nhwc_f32 over cols. */
+int gssd_dcn_geo_im2col_f32(const float* x, const float* offset, const float* mask, float* cols, const gssd_dcn_geom* geom, int b0,
+                            int b1, gssd_stream_t stream);
+/* Backward: given d(cols) (laid out as cols), ADDS d(x) into `dx` (same layout as x; fp32 atomics, caller-zeroed; last bits vary from
+ * run to run) and WRITES d(offset) / d(mask) -- d(mask logit) under mask_logit -- at the offset / mask positions of the processed
+ * pixels (strides off_stride / mask_stride; other channels are not touched).  d(offset) / d(mask) are per-unit wave sums over the
+ * group's channels in a fixed order: no atomics, reproducible.  dx may be NULL (no d(x)); doffset and dmask are both NULL or both set. */
+int gssd_dcn_geo_col2im_f32(const float* x, const float* offset, const float* mask, const float* dcols, float* dx, float* doffset,
+                            float* dmask, const gssd_dcn_geom* geom, int b0, int b1, gssd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Input stage: data/__init__.py:33-54 (base_transform_fast / BaseTransform),
  * utils/augmentations.py:506-524 (ResizeFast, Normalize), train_lesion_multiphase_v2.py:198 ([B,4,3,H,W] -> [B,12,H,W]).

@@ -1,7 +1,8 @@
 """``data`` of the drop-in: the constants the hot path imports (``from data import v2``) and the deterministic input
 transform (``BaseTransform`` / ``base_transform_fast``, ssd_liverdet/data/__init__.py:33-70) as a device stage.
-The datasets, collate functions and random augmentations of the reference (ssd_liverdet/data/*.py,
-utils/augmentations.py) are out of scope."""
+The training augmentation (``SSDAugmentation``, utils/augmentations.py) runs on the device too, on a collated batch:
+``utils.augmentations.SSDAugmentationCUDA`` (gssd/augment.py).  The datasets and collate functions of the
+reference (ssd_liverdet/data/*.py) are out of scope."""
 import numpy as np
 import torch
 

@@ -170,6 +170,10 @@ SIGNATURES = {
     'gssd_resize_u8_horizontal': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp]),
     'gssd_resize_u8_vertical': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     'gssd_input_finish_f32': (c_i, [c_fp, c_fp, c_f, c_f, c_f, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp]),
+    'gssd_aug_desc_size': (c_i, []),
+    'gssd_augment_minmax': (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp]),
+    'gssd_augment_horizontal': (c_i, [c_fp, c_fp, c_fp, c_f, c_f, c_f, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp]),
+    'gssd_augment_vertical': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     'gssd_eval_match': (c_i, [c_fp, C.c_longlong, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_d, c_fp, c_i, c_i, c_fp, c_fp, c_fp]),
     'gssd_eval_workspace_bytes': (C.c_longlong, [c_i]),
     'gssd_eval_ap': (c_i, [c_fp, c_fp, c_i, c_i, c_d, c_i, c_fp, C.c_longlong, c_fp, c_fp]),

@@ -10,10 +10,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "resample8.h"
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;
+using gssd_resample8::PRECISION_BITS;
+using gssd_resample8::clip8;
 
 double filter_bilinear(double x) {
     if (x < 0.0) x = -x;
@@ -38,11 +40,6 @@ Geometry geometry(int in_size, int out_size, int filter) {
     g.support = (filter == GSSD_FILTER_BILINEAR ? 1.0 : 2.0) * g.filterscale;
     g.ksize = (int)ceil(g.support) * 2 + 1;
     return g;
-}
-
-__device__ __forceinline__ uint8_t clip8(int acc) {
-    const int v = acc >> PRECISION_BITS;                    // arithmetic shift, like the C reference
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
 // in [n][H][Win][C] -> out [n][H][Wout][C]; one thread per output pixel (its C bytes are contiguous in both images)
@@ -176,9 +173,7 @@ __global__ __launch_bounds__(256) void resize_h_lds_kernel(const uint8_t* __rest
             const int x0 = bl[2 * xo], n = bl[2 * xo + 1];
             const int* k = kl + xo * ksize;
             const uint8_t* sp = rowb + (size_t)r * Win * C + x0 * C + c;
-            int acc = 1 << (PRECISION_BITS - 1);
-            for (int t = 0; t < n; ++t) acc += __mul24((int)sp[t * C], k[t]);      // 8-bit x 23-bit: exact in the 24-bit multiplier
-            res |= (uint32_t)clip8(acc) << (8 * e);
+            res |= (uint32_t)gssd_resample8::taps8(sp, C, k, n) << (8 * e);
         }
         reinterpret_cast<uint32_t*>(out + (row0 + r) * Wout * C)[w] = res;
     }

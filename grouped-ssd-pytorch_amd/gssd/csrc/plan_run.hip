@@ -125,6 +125,9 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_resize_u8_horizontal),
     GSSD_PLAN_FN(gssd_resize_u8_vertical),
     GSSD_PLAN_FN(gssd_input_finish_f32),
+    GSSD_PLAN_FN(gssd_augment_minmax),
+    GSSD_PLAN_FN(gssd_augment_horizontal),
+    GSSD_PLAN_FN(gssd_augment_vertical),
     GSSD_PLAN_FN(gssd_bgemm_f32),
     GSSD_PLAN_FN(gssd_bgemm_ex_f32),
     GSSD_PLAN_FN(gssd_rowdot_f32),

@@ -541,6 +541,42 @@ int gssd_resize_u8_vertical(const uint8_t* in, uint8_t* out, const int32_t* boun
 int gssd_input_finish_f32(const uint8_t* img, const int32_t* minmax, float mean0, float mean1, float mean2, float* out_nchw,
                           int B, int phases, int S, int C, int normalize, gssd_stream_t stream);
 
+/* Training augmentation (utils/augmentations.py SSDAugmentation with use_normalize, optional p_only) on 4-phase, 3-slice uint8
+ * studies.  The host (gssd/augment.py) draws every random number and fixes the geometry; one descriptor per study tells the
+ * three passes below where the study lies, where Expand placed it on its canvas, which window RandomSampleCrop kept, whether
+ * RandomMirror flipped it and which brightness / contrast PhotometricDistort applied.  A pixel of the window is
+ *   v = fl32(fl32(fl32(u8 + delta) * alpha) - mean[c])   inside the placed image,   0 (= mean - mean) on the canvas fill;
+ * the study's extrema of v normalise it, q = (uint8) fl32(fl32(fl32(v - min) / fl32(max - min)) * 255) is resized to
+ * size x size by Pillow's 8-bit bicubic resampler, and the output is fl32(resized / 255) in [B][4*3][size][size]. */
+typedef struct gssd_aug_desc {
+    int64_t src;                     /* device address of the study's byte (phase 0, slice 0, row 0, column 0) */
+    int64_t work;                    /* byte offset of the study's horizontal-pass rows in `work`: [phases][nrows][size][3] */
+    int32_t H, W;                    /* source rows / columns */
+    int32_t s_phase, s_chan, s_y, s_x;   /* source strides in bytes (any layout, e.g. [4][H][W][3] or [4][3][H][W]) */
+    int32_t top, left;               /* where Expand placed the source on its canvas */
+    int32_t cy, cx, ch, cw;          /* the crop window on the canvas (the whole canvas when RandomSampleCrop chose None) */
+    int32_t mirror;                  /* 1: RandomMirror flipped the crop horizontally */
+    int32_t fill;                    /* 1: the window leaves the placed image, so the fill value 0 joins the extrema */
+    float delta, alpha;              /* brightness (0 when not drawn), contrast (1 when not drawn), as float32 */
+    int32_t hb, hk, hks;             /* horizontal pass cw -> size: bounds / coefficient offsets (int32 elements) in `table`, taps;
+                                        hks == 0: cw == size, a pass-through (Pillow skips the pass) */
+    int32_t vb, vk, vks;             /* vertical pass ch -> size, likewise */
+    int32_t row0, nrows;             /* crop rows the vertical pass reads; the horizontal pass writes only these */
+} gssd_aug_desc;
+int gssd_aug_desc_size(void);
+
+/* Per-study, per-slice extrema of the window's bytes inside the placed image (of phase 2 only under p_only):
+ * minmax[b][3][2] = (255 - min, max), zeroed on the stream here.  `desc` is a device array of B descriptors; max_rows is the
+ * largest crop height of the batch (the grid's extent). */
+int gssd_augment_minmax(const gssd_aug_desc* desc, int B, int max_rows, int p_only, int32_t* minmax, gssd_stream_t stream);
+/* Quantise (from the raw bytes, mirrored read) + the horizontal pass into `work`.  `table`: the coefficient tables the
+ * descriptors point into.  max_rows / max_cw: the largest `nrows` / `cw` of the batch (grid extent, LDS row length). */
+int gssd_augment_horizontal(const gssd_aug_desc* desc, const int32_t* minmax, const int32_t* table, float mean0, float mean1,
+                            float mean2, uint8_t* work, int B, int max_rows, int max_cw, int size, int p_only, gssd_stream_t stream);
+/* Vertical pass + fl32(u8 / 255) into out_nchw [B][12][size][size] (channel = phase * 3 + slice). */
+int gssd_augment_vertical(const gssd_aug_desc* desc, const int32_t* table, const uint8_t* work, float* out_nchw, int B, int size,
+                          int p_only, gssd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Self_Attn backward building blocks (what the reference gets from autograd over
  * layers/self_attn.py:62-89 -- conv2d / bmm / softmax backward kernels)

@@ -8,7 +8,10 @@ Here the split is:
   arithmetic with the reference's numpy dtypes; the pixels it never touches.  Per study it emits one ``gssd_aug_desc``
   (include/gssd_hip.h): source geometry and strides, Expand's canvas placement, the crop window, the mirror flag, brightness /
   contrast as float32, and offsets into the resampling coefficient tables;
-* three HIP launches (csrc/augment.hip) per batch: extrema, quantise + horizontal Pillow pass, vertical pass + ``/ 255``.
+* three HIP launches (csrc/augment.hip) per batch: extrema, quantise + horizontal Pillow pass, vertical pass + ``/ 255``;
+* with ``use_pixel_link`` and a named ``pixel_link_version``, a fourth (csrc/pixellink_targets.hip) builds the PixelLink targets of
+  ``PreparePixelLinkTargets`` (utils/augmentations.py:527-545) from the planned boxes; their corners ride in the descriptors'
+  pinned upload.  That transform draws no random numbers, so the generators are consumed exactly as without it.
 
 Random generators (the reference's trap): in augmentations.py the name ``random`` is Python's stdlib module (re-exported by
 ``from pixel_link.pixellink_data import *`` over ``from numpy import random``), so ``randint(0, 2)`` is inclusive -- a branch
@@ -23,6 +26,7 @@ import torch
 from . import _lib
 from ._lib import lib, check
 from .input_stage import resample_tables
+from . import pixellink_targets as _plt
 
 PHASES, SLICES = 4, 3
 
@@ -202,15 +206,25 @@ class DeviceSSDAugmentation:
     ``aug(raw, targets)`` -> (fp32 CUDA ``[B, 12, size, size]``, list of ``torch.float32 [n_i, 5]``): ``raw`` as the reference's
     dataset returns it with an identity transform and collates it (uint8 ``[B, 4, 3, H, W]``, or ``[B, 4, H, W, 3]``, or a list of
     studies), ``targets`` pull_item's ``[n_i, 5]`` percent-coordinate arrays.  Bitwise equal to B consecutive reference calls
-    from the same generator states.  No host synchronisation: descriptors reach the device through a pinned staging buffer."""
+    from the same generator states.  No host synchronisation: descriptors reach the device through a pinned staging buffer.
+
+    ``use_pixel_link=True, pixel_link_version="4s" | "2s"`` (train_lesion_multiphase_v2_pixellink.py:513-518): ``aug(raw, targets)``
+    -> (images, the dict of ``detection_collate_v2_pixel_link`` (data/data_custom_v2.py:399-434)) -- the same images, and the
+    PixelLink targets of the planned boxes (gssd/pixellink_targets.py): the four maps on the device, ``'lables'`` / ``'boxes'`` as
+    CPU float32 tensors.  The reference's constructor defaults the version to "2s"; here it must be named."""
 
     def __init__(self, pixeljitter=0.01, ratio=1.5, size=300, mean=(104, 117, 123), use_normalize=False, p_only=False,
-                 use_pixel_link=False):
+                 use_pixel_link=False, pixel_link_version=None):
         assert use_normalize, 'new ResizeFast implementation assumes --use_normalize to True!'      # the reference's assert
-        if use_pixel_link:
-            raise NotImplementedError('use_pixel_link (PreparePixelLinkTargets) is not part of the device augmentation')
+        if use_pixel_link and pixel_link_version is None:
+            raise NotImplementedError('use_pixel_link (PreparePixelLinkTargets) needs a named version: pass pixel_link_version="4s" '
+                                      'or "2s", as the reference driver does (config.version)')
         self.pixeljitter, self.ratio, self.size = pixeljitter, ratio, int(size)
-        self.use_normalize, self.p_only, self.use_pixel_link = True, bool(p_only), False
+        self.use_normalize, self.p_only, self.use_pixel_link = True, bool(p_only), bool(use_pixel_link)
+        self.pixel_link_version = None
+        if self.use_pixel_link:
+            _plt._check_geometry(self.size, pixel_link_version)
+            self.pixel_link_version = pixel_link_version
         m = np.asarray(mean, np.float32).reshape(-1)
         if m.size != SLICES:
             raise ValueError(f'mean must have {SLICES} values, got {m.size}')
@@ -271,11 +285,14 @@ class DeviceSSDAugmentation:
     def __call__(self, raw, targets, out=None, py_rng=None, np_rng=None):
         studies = _as_studies(raw)
         plan = self.plan([(H, W) for _, H, W, _ in studies], targets, py_rng, np_rng)
+        if self.use_pixel_link:
+            return self.run(studies, plan, out, pixel_link=True)
         images = self.run(studies, plan, out)
         return images, [torch.from_numpy(t) for t in plan.targets]
 
-    def run(self, raw, plan, out=None):
-        """Device half: the three passes for ``plan`` over ``raw`` (as in ``__call__``, or ``_as_studies``'s list)."""
+    def run(self, raw, plan, out=None, pixel_link=False):
+        """Device half: the three passes for ``plan`` over ``raw`` (as in ``__call__``, or ``_as_studies``'s list).  With
+        ``pixel_link`` (needs ``pixel_link_version``): (images, PixelLink target dict) from the plan's boxes."""
         studies = raw if isinstance(raw, list) and raw and isinstance(raw[0], tuple) else _as_studies(raw)
         if len(studies) != len(plan.samples):
             raise _lib.GssdError(f'augment: {len(studies)} studies but a plan for {len(plan.samples)}')
@@ -290,7 +307,15 @@ class DeviceSSDAugmentation:
         elif (out.dtype != torch.float32 or not out.is_cuda or tuple(out.shape) != (B, PHASES * SLICES, S, S)
               or not out.is_contiguous() or out.device != dev):
             raise _lib.GssdError(f'augment: out must be a contiguous fp32 CUDA tensor [{B}, 12, {S}, {S}]')
-        desc = torch.from_numpy(d.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+        staged = d.view(np.uint8)
+        if pixel_link:
+            if self.pixel_link_version is None:
+                raise _lib.GssdError('augment: pixel_link targets need pixel_link_version')
+            packed, offs = _plt.pack_boxes([t[:, :4] for t in plan.targets])
+            tail, boxes_at = _plt.staging(packed, offs)
+            desc_bytes = (staged.size + 15) & ~15
+            staged = np.concatenate([staged, np.zeros(desc_bytes - staged.size, np.uint8), tail])
+        desc = torch.from_numpy(staged).pin_memory().to(dev, non_blocking=True)
         work = torch.empty(max(work_bytes, 1), dtype=torch.uint8, device=dev)
         mm = torch.empty(B, SLICES, 2, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -302,7 +327,13 @@ class DeviceSSDAugmentation:
             check(lib.gssd_augment_vertical(desc.data_ptr(), table.dev.data_ptr(), work.data_ptr(), out.data_ptr(), B, S,
                                             int(self.p_only), stream))
         self.last_minmax, self.last_desc = mm, d
-        return out
+        if not pixel_link:
+            return out
+        base = desc.data_ptr() + desc_bytes
+        targets = _plt.launch(base + boxes_at, base, B, S, self.pixel_link_version, dev)
+        targets['lables'] = [torch.from_numpy(t[:, 4].copy()) for t in plan.targets]
+        targets['boxes'] = [torch.from_numpy(t) for t in plan.targets]
+        return out, targets
 
     def check_not_flat(self):
         """The reference's Normalize asserts ``img_min != img_max``; on the device that costs a sync, so it is opt-in."""

@@ -128,6 +128,7 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_augment_minmax),
     GSSD_PLAN_FN(gssd_augment_horizontal),
     GSSD_PLAN_FN(gssd_augment_vertical),
+    GSSD_PLAN_FN(gssd_pixellink_targets),
     GSSD_PLAN_FN(gssd_bgemm_f32),
     GSSD_PLAN_FN(gssd_bgemm_ex_f32),
     GSSD_PLAN_FN(gssd_rowdot_f32),

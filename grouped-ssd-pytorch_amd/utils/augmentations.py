@@ -9,4 +9,6 @@ __all__ = ['SSDAugmentationCUDA']
 
 class SSDAugmentationCUDA(DeviceSSDAugmentation):
     """``SSDAugmentationCUDA(gt_pixel_jitter, expand_ratio, ssd_dim, means, use_normalize=..., p_only=...)``;
-    ``aug(images_u8_cuda, targets) -> (images [B, 12, size, size], targets)``."""
+    ``aug(images_u8_cuda, targets) -> (images [B, 12, size, size], targets)``.  With ``use_pixel_link=True,
+    pixel_link_version=config.version`` (train_lesion_multiphase_v2_pixellink.py:513-518) the targets are the PixelLink dict of
+    detection_collate_v2_pixel_link, built on the device."""

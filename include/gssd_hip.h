@@ -577,6 +577,26 @@ int gssd_augment_horizontal(const gssd_aug_desc* desc, const int32_t* minmax, co
 int gssd_augment_vertical(const gssd_aug_desc* desc, const int32_t* table, const uint8_t* work, float* out_nchw, int B, int size,
                           int p_only, gssd_stream_t stream);
 
+/* PixelLink training targets: utils/augmentations.py:527-545 PreparePixelLinkTargets (the last transform of SSDAugmentation with
+ * use_pixel_link) through pixel_link/pixellink_data.py:15-99 label_to_mask_and_pixel_pos_weight, in the dtypes of
+ * data/data_custom_v2.py:399-434 detection_collate_v2_pixel_link, for B images in one launch.  `boxes`: float32 [total][4] percent
+ * corners (x0, y0, x1, y1: SamplePlan.target[:, :4]), image b owning rows offsets[b] .. offsets[b + 1] - 1 (at most 255 boxes an
+ * image: the reference counts coverage in uint8 and the host refuses more).  factor = 2 for version "2s", 4 otherwise; the map is
+ * M x M with M = size / factor (1 .. 256).  Per image:
+ *   corners  c = (int64) fl32(b * size), then c / factor with C truncation (the reference's astype(int) of a float64 quotient);
+ *   box i    rows min(y0, y1) .. max(y0, y1), columns min(x0, x1) .. max(x0, x1), both ends inclusive, clipped to [0, M - 1] --
+ *            a restatement of cv2.drawContours(thickness=-1) of the reference's axis-aligned 4-vertex polygon, not checked
+ *            against OpenCV;
+ *   masks    cnt(q) = boxes covering q; pixel_mask = (cnt == 1), neg_pixel_mask = (cnt == 0); P_i = pixels with cnt == 1 in box i;
+ *   weight   fl32(fl64(fl64(A / R) / |P_i|)) on P_i, 0 elsewhere (A = sum |P_i|, R = number of boxes with |P_i| > 0);
+ *   links    link_mask[j][q] = 1 iff q in P_i and some p in P_i has clip(p + d_j) == q, per-axis clipping to [0, M - 1] (the
+ *            reference's scatter form, pixellink_data.py:74-98, with its border behaviour), d_j = (dh, dw) =
+ *            (+1,+1) (+1,0) (+1,-1) (0,-1) (-1,-1) (-1,0) (-1,+1) (0,+1) for j = 0..7.
+ * Outputs (every element written, no memset needed): pixel_mask, neg_pixel_mask int64 [B][M][M], pixel_pos_weight float32 [B][M][M],
+ * link_mask int64 [B][8][M][M].  `offsets` is a device int32 array [B + 1]. */
+int gssd_pixellink_targets(const float* boxes, const int32_t* offsets, int B, int size, int factor, int64_t* pixel_mask,
+                           int64_t* neg_pixel_mask, float* pixel_pos_weight, int64_t* link_mask, gssd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Self_Attn backward building blocks (what the reference gets from autograd over
  * layers/self_attn.py:62-89 -- conv2d / bmm / softmax backward kernels)

@@ -175,6 +175,11 @@ SIGNATURES = {
     'gssd_augment_horizontal': (c_i, [c_fp, c_fp, c_fp, c_f, c_f, c_f, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp]),
     'gssd_augment_vertical': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     'gssd_pixellink_targets': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    'gssd_pixellink_final5_f32': (c_i, [c_fp] * 5 + [c_i] + [c_fp] * 6 + [c_i, c_i, c_fp]),
+    'gssd_pixellink_final5_bwd_f32': (c_i, [c_fp] * 7 + [c_i] + [c_fp] * 7 + [c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
+    'gssd_self_attn_flash_bwd_f32_supported': (c_i, [c_i, c_i]),
+    'gssd_self_attn_flash_bwd_f32': (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i,
+                                           c_i, c_fp]),
     'gssd_eval_match': (c_i, [c_fp, C.c_longlong, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_d, c_fp, c_i, c_i, c_fp, c_fp, c_fp]),
     'gssd_eval_workspace_bytes': (C.c_longlong, [c_i]),
     'gssd_eval_ap': (c_i, [c_fp, c_fp, c_i, c_i, c_d, c_i, c_fp, C.c_longlong, c_fp, c_fp]),

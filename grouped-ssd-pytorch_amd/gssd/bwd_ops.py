@@ -418,10 +418,11 @@ class BackwardOpsMixin:
         dw1 = self._buf(2 * 2 * nf + 2, dtype=torch.float64, zero_each_run=True)
         dw2 = self._buf(16 * 16 * nf + 16, dtype=torch.float64, zero_each_run=True)
         w1, w2 = f1.weight.detach().view(2, -1), f2.weight.detach().view(16, -1)
-        fp = [f.data_ptr() for f in feats] + [0] * (4 - nf)
-        gp = [g.data_ptr() for g in gs] + [0] * (4 - nf)
-        self._add(lib.gssd_pixellink_final_bwd_f32, (self.d_out1.data_ptr(), self.d_out2.data_ptr(), *fp, nf, w1.data_ptr(), w2.data_ptr(),
-                                                     *gp, 0, dw1.data_ptr(), dw2.data_ptr(), B, H * H, self.PL_LD), keep=(w1, w2))
+        fn, nptr = (lib.gssd_pixellink_final5_bwd_f32, 5) if nf > 4 else (lib.gssd_pixellink_final_bwd_f32, 4)    # five features: "2s"
+        fp = [f.data_ptr() for f in feats] + [0] * (nptr - nf)
+        gp = [g.data_ptr() for g in gs] + [0] * (nptr - nf)
+        self._add(fn, (self.d_out1.data_ptr(), self.d_out2.data_ptr(), *fp, nf, w1.data_ptr(), w2.data_ptr(), *gp, 0, dw1.data_ptr(),
+                       dw2.data_ptr(), B, H * H, self.PL_LD), keep=(w1, w2))
         for dw, mod, nw in ((dw1, f1, 4 * nf), (dw2, f2, 256 * nf)):
             self._add(lib.gssd_cast_f64_f32, (dw.data_ptr(), self._pgrad(mod.weight).data_ptr(), nw, 0))
             self._add(lib.gssd_cast_f64_f32, (dw[nw:].data_ptr(), self._pgrad(mod.bias).data_ptr(), mod.bias.numel(), 0))
@@ -553,6 +554,22 @@ class BackwardOpsMixin:
             self._add(lib.gssd_self_attn_flash_bwd_bf16, (tp.data_ptr(), tph.data_ptr(), tpl.data_ptr() if x3 else 0, r['g16'].data_ptr(),
                                                           self._cast16(dag).data_ptr(), lse.data_ptr(), Dv.data_ptr(), dtpg.data_ptr(),
                                                           B, N, C8, C2), keep=(r['g16'], lse, tph, tpl))
+        elif lse is not None and lib.gssd_self_attn_flash_bwd_f32_supported(C8, C2):
+            # fp32, (D, C2) = (16, 64): the 128-channel blocks of PixelLink "2s" on 150 x 150 maps, where the explicit path's two
+            # [N][Nk] maps would take 4 GB per image; d theta | d keys | d values in two launches, no map
+            Dv = self._buf(B, N)
+            self._add(lib.gssd_rowdot_f32, (dag.data_ptr(), ag.data_ptr(), Dv.data_ptr(), M, C2))
+            if pooled:
+                CW = C8 + C2
+                dkg = self._buf(B, Nk, CW)                                    # d(pooled phi) | d(pooled g) per cell
+                dk, dv, ld_kv = dkg, dkg[0, 0, C8:], CW
+            else:
+                dk, dv, ld_kv = dtpg[0, 0, C8:], dtpg[0, 0, C4:], CT
+            self._add(lib.gssd_self_attn_flash_bwd_f32, (tp.data_ptr(), C4, keys.data_ptr(), krow, vals.data_ptr(), Nkp, dag.data_ptr(),
+                                                         lse.data_ptr(), Dv.data_ptr(), dtpg.data_ptr(), CT, dk.data_ptr(), dv.data_ptr(),
+                                                         ld_kv, B, N, Nk, C8, C2))
+            if pooled:
+                self._add(lib.gssd_sa_unpool_f32, (dkg.data_ptr(), dtpg[0, 0, C8:].data_ptr(), B, H, r['P'], CW, CT))
         else:
             self._sa_explicit(r, dtpg, dag, ag, tp, keys, krow, vals, lse, pooled)
         self._sa_tail(r, dtpg, g_out, gx, existed, x, a_tpg, w_tpg, cv, sig, sndot)

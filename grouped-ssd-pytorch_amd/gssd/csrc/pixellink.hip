@@ -9,7 +9,8 @@
 //   - the link decoding of pixel_link/postprocess.py:178-234 (`func`): connected components under directed 8-neighbour links by
 //     min-label propagation in LDS, numbered in raster order of their first pixel exactly like the union-find + root_map of the
 //     reference, plus per-component pixel count, bounding box and score sum.
-// HBM-bound byte work on <= 75 x 75 maps: one workgroup per image (or per row block), no MFMA.
+// HBM-bound byte work on 75 x 75 ("4s") and 150 x 150 ("2s") maps: one workgroup per image (or per row block), no MFMA.  Version "2s"
+// adds the five-feature final kernels, a radix-select loss and a dynamic-LDS decoding for maps above 8192 pixels.
 #include <math.h>
 #include "common.h"
 
@@ -396,12 +397,11 @@ __global__ __launch_bounds__(1024) void pl_loss_bwd_kernel(const float* __restri
 constexpr int PL_MAXPIX = 8192;
 constexpr int PL_STAT_COMPS = 1024;      // components with statistics (LDS table); the label map itself is unlimited
 
-__global__ __launch_bounds__(1024) void pl_decode_kernel(const float* __restrict__ out1, const float* __restrict__ out2,
-                                                         int* __restrict__ labels, float* __restrict__ comps, int* __restrict__ ncomp,
-                                                         int H, int W, float pixel_thr, float link_thr, int max_comp) {
-    __shared__ int lab[PL_MAXPIX];
-    __shared__ unsigned char lk[PL_MAXPIX];
-    __shared__ int nroot;
+// The body of both decode kernels; lab [H*W], lk [H*W], cnt [1024], cstat [PL_STAT_COMPS * 6] and nroot are LDS.
+__device__ __forceinline__ void pl_decode_body(const float* __restrict__ out1, const float* __restrict__ out2, int* __restrict__ labels,
+                                               float* __restrict__ comps, int* __restrict__ ncomp, int H, int W, float pixel_thr,
+                                               float link_thr, int max_comp, int* lab, unsigned char* lk, int* cnt, float* cstat,
+                                               int& nroot) {
     const int b = blockIdx.x, tid = threadIdx.x, HW = H * W;
     constexpr int dy[8] = {-1, -1, -1, 0, 1, 1, 1, 0}, dx[8] = {-1, 0, 1, 1, 1, 0, -1, -1};
     for (int i = tid; i < HW; i += 1024) {
@@ -462,7 +462,6 @@ __global__ __launch_bounds__(1024) void pl_decode_kernel(const float* __restrict
     }
     __syncthreads();
     // rank the roots (lab[i] == i) in raster order: serial over <= HW by one thread per 1024-chunk would do; a block scan is simpler
-    __shared__ int cnt[1024];
     const int per = (HW + 1023) / 1024;
     int mine = 0;
     for (int k = 0; k < per; ++k) {
@@ -510,7 +509,6 @@ __global__ __launch_bounds__(1024) void pl_decode_kernel(const float* __restrict
     // per-component statistics: count, min x, min y, max x, max y, score sum (score = softmax probability of class 1).  Accumulated in
     // LDS (the label array's neighbour `lk` and the scan buffer are dead): thousands of pixels of one component adding to the same six
     // GLOBAL addresses serialise at the L2 atomic unit (0.25 ms per launch).
-    __shared__ float cstat[PL_STAT_COMPS * 6];
     const int ncs = max_comp < PL_STAT_COMPS ? max_comp : PL_STAT_COMPS;
     for (int i = tid; i < ncs * 6; i += 1024) {
         const int f = i % 6;
@@ -576,6 +574,289 @@ __global__ __launch_bounds__(1024) void pl_decode_kernel(const float* __restrict
     if (tid == 0) ncomp[b] = nroot;
 }
 
+__global__ __launch_bounds__(1024) void pl_decode_kernel(const float* __restrict__ out1, const float* __restrict__ out2,
+                                                         int* __restrict__ labels, float* __restrict__ comps, int* __restrict__ ncomp,
+                                                         int H, int W, float pixel_thr, float link_thr, int max_comp) {
+    __shared__ int lab[PL_MAXPIX];
+    __shared__ unsigned char lk[PL_MAXPIX];
+    __shared__ int cnt[1024];
+    __shared__ float cstat[PL_STAT_COMPS * 6];
+    __shared__ int nroot;
+    pl_decode_body(out1, out2, labels, comps, ncomp, H, W, pixel_thr, link_thr, max_comp, lab, lk, cnt, cstat, nroot);
+}
+
+// Maps above PL_MAXPIX (the 150 x 150 maps of version "2s"): the same body with every array in dynamic LDS, up to PL_MAXPIX_LDS pixels
+// (5 bytes per pixel + 28 KB of tables: 141 KB at 150 x 150, within the CU's 160 KB; one workgroup per CU).
+constexpr int PL_MAXPIX_LDS = 26624;
+constexpr int PL_DEC_FIXED = PL_STAT_COMPS * 6 * 4 + 1024 * 4 + 16;      // cstat | cnt | nroot (padded to 16 bytes)
+
+inline size_t pl_decode_lds_bytes(int HW) { return (size_t)PL_DEC_FIXED + (size_t)(HW + 3) / 4 * 16 + (size_t)HW; }
+
+__global__ __launch_bounds__(1024) void pl_decode_lds_kernel(const float* __restrict__ out1, const float* __restrict__ out2,
+                                                             int* __restrict__ labels, float* __restrict__ comps, int* __restrict__ ncomp,
+                                                             int H, int W, float pixel_thr, float link_thr, int max_comp) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* cstat = reinterpret_cast<float*>(smem);
+    int* cnt = reinterpret_cast<int*>(smem + PL_STAT_COMPS * 6 * 4);
+    int* nroot = cnt + 1024;
+    int* lab = reinterpret_cast<int*>(smem + PL_DEC_FIXED);
+    unsigned char* lk = reinterpret_cast<unsigned char*>(smem + PL_DEC_FIXED + (size_t)(H * W + 3) / 4 * 16);
+    pl_decode_body(out1, out2, labels, comps, ncomp, H, W, pixel_thr, link_thr, max_comp, lab, lk, cnt, cstat, *nroot);
+}
+
+// ---- version "2s": five cascade features, maps above PL_SORT pixels ------------------------------------------------------------------
+
+// final_1 / final_2 over nf <= 5 features (model.py:153-155: Conv2d(10, 2), Conv2d(80, 16) in version "2s"); pl_final_kernel's arithmetic in
+// the same order, so for nf <= 4 the outputs equal gssd_pixellink_final_f32's bit for bit.
+__global__ __launch_bounds__(256) void pl_final5_kernel(const float* __restrict__ f0, const float* __restrict__ f1,
+                                                        const float* __restrict__ f2, const float* __restrict__ f3,
+                                                        const float* __restrict__ f4, int nf, const float* __restrict__ w1,
+                                                        const float* __restrict__ b1, const float* __restrict__ w2,
+                                                        const float* __restrict__ b2, float* __restrict__ out1, float* __restrict__ out2,
+                                                        int B, int HW) {
+    __shared__ float sw1[2 * 10], sw2[16 * 80], sb[18];
+    for (int i = threadIdx.x; i < 2 * 2 * nf; i += 256) sw1[i] = w1[i];
+    for (int i = threadIdx.x; i < 16 * 16 * nf; i += 256) sw2[i] = w2[i];
+    if (threadIdx.x < 2) sb[threadIdx.x] = b1[threadIdx.x];
+    if (threadIdx.x >= 2 && threadIdx.x < 18) sb[threadIdx.x] = b2[threadIdx.x - 2];
+    __syncthreads();
+    const float* fs[5] = {f0, f1, f2, f3, f4};
+    const long long total = (long long)B * HW;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < total; p += (long long)gridDim.x * blockDim.x) {
+        float v[5][18];
+        for (int k = 0; k < nf; ++k)
+#pragma unroll
+            for (int c = 0; c < 18; ++c) v[k][c] = fs[k][p * 18 + c];
+        const int b = (int)(p / HW), pix = (int)(p - (long long)b * HW);
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            float a = sb[o];
+            for (int k = 0; k < nf; ++k)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) a = __builtin_fmaf(sw1[o * 2 * nf + k * 2 + c], v[k][c], a);
+            out1[((size_t)b * 2 + o) * HW + pix] = a;
+        }
+        for (int o = 0; o < 16; ++o) {
+            float a = sb[2 + o];
+            for (int k = 0; k < nf; ++k)
+#pragma unroll
+                for (int c = 0; c < 16; ++c) a = __builtin_fmaf(sw2[o * 16 * nf + k * 16 + c], v[k][2 + c], a);
+            out2[((size_t)b * 16 + o) * HW + pix] = a;
+        }
+    }
+}
+
+// d(final_1 / final_2) w.r.t. nf <= 5 features: pl_final_bwd_kernel with a fifth map.
+__global__ __launch_bounds__(256) void pl_final5_bwd_kernel(const float* __restrict__ d1, const float* __restrict__ d2, int nf,
+                                                            const float* __restrict__ w1, const float* __restrict__ w2, float* __restrict__ g0,
+                                                            float* __restrict__ g1, float* __restrict__ g2, float* __restrict__ g3,
+                                                            float* __restrict__ g4, int acc_mask, int B, int HW, int ld) {
+    __shared__ float sw1[2 * 10], sw2[16 * 80];
+    for (int i = threadIdx.x; i < 2 * 2 * nf; i += 256) sw1[i] = w1[i];
+    for (int i = threadIdx.x; i < 16 * 16 * nf; i += 256) sw2[i] = w2[i];
+    __syncthreads();
+    float* gs[5] = {g0, g1, g2, g3, g4};
+    const long long total = (long long)B * HW;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < total; p += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(p / HW), pix = (int)(p - (long long)b * HW);
+        float a1[2], a2[16];
+#pragma unroll
+        for (int o = 0; o < 2; ++o) a1[o] = d1[((size_t)b * 2 + o) * HW + pix];
+#pragma unroll
+        for (int o = 0; o < 16; ++o) a2[o] = d2[((size_t)b * 16 + o) * HW + pix];
+        for (int k = 0; k < nf; ++k) {
+            float* gp = gs[k] + (size_t)p * ld;
+            const bool acc = (acc_mask >> k) & 1;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                float v = 0.f;
+#pragma unroll
+                for (int o = 0; o < 2; ++o) v = __builtin_fmaf(sw1[o * 2 * nf + k * 2 + c], a1[o], v);
+                gp[c] = acc ? gp[c] + v : v;
+            }
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                float v = 0.f;
+#pragma unroll
+                for (int o = 0; o < 16; ++o) v = __builtin_fmaf(sw2[o * 16 * nf + k * 16 + c], a2[o], v);
+                gp[2 + c] = acc ? gp[2 + c] + v : v;
+            }
+        }
+    }
+}
+
+// weight / bias gradients over nf <= 5 features: pl_final_wgrad_kernel's scheme with five final_2 columns per thread (16 rows x 80
+// columns = 256 x 5) and 90 feature channels per pixel in LDS (56 KB).
+__global__ __launch_bounds__(256) void pl_final5_wgrad_kernel(const float* __restrict__ d1, const float* __restrict__ d2,
+                                                              const float* __restrict__ f0, const float* __restrict__ f1,
+                                                              const float* __restrict__ f2, const float* __restrict__ f3,
+                                                              const float* __restrict__ f4, int nf, double* __restrict__ dw1,
+                                                              double* __restrict__ dw2, int B, int HW) {
+    constexpr int TP = 128;
+    __shared__ float sd[TP][18 + 1];
+    __shared__ float sf[TP][90 + 1];        // features: k * 18 + c
+    const float* fs[5] = {f0, f1, f2, f3, f4};
+    const long long total = (long long)B * HW;
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int o2 = threadIdx.x >> 4, cb = (threadIdx.x & 15) * 5;        // final_2: row o2, columns cb .. cb + 4 of [16][16 nf]
+    const int lp = threadIdx.x & (TP - 1), half = threadIdx.x >> 7;      // loader: half 0 = d + f0, f1; half 1 = f2, f3, f4
+    for (long long base = (long long)blockIdx.x * TP; base < total; base += (long long)gridDim.x * TP) {
+        const long long p = base + lp;
+        __syncthreads();
+        const bool ok = p < total;
+        const int b = ok ? (int)(p / HW) : 0, pix = ok ? (int)(p - (long long)b * HW) : 0;
+        if (half == 0) {
+#pragma unroll
+            for (int o = 0; o < 2; ++o) sd[lp][o] = ok ? d1[((size_t)b * 2 + o) * HW + pix] : 0.f;
+#pragma unroll
+            for (int o = 0; o < 16; ++o) sd[lp][2 + o] = ok ? d2[((size_t)b * 16 + o) * HW + pix] : 0.f;
+        }
+        for (int k = half ? 2 : 0; k < (half ? 5 : 2) && k < nf; ++k)
+#pragma unroll
+            for (int c = 0; c < 18; ++c) sf[lp][k * 18 + c] = ok ? fs[k][p * 18 + c] : 0.f;
+        __syncthreads();
+        for (int q = 0; q < TP; ++q) {
+            const float g = sd[q][2 + o2];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+                const int col = cb + j;                        // = k * 16 + c  (c < 16) of final_2's input
+                if (col < 16 * nf) acc[j] = __builtin_fmaf(g, sf[q][(col >> 4) * 18 + 2 + (col & 15)], acc[j]);
+            }
+            const int t = threadIdx.x;                         // leftovers: final_1's 2 x 2 nf weights, then the 2 + 16 biases
+            if (t < 4 * nf) {
+                const int o = t / (2 * nf), col = t - o * 2 * nf;
+                acc[5] = __builtin_fmaf(sd[q][o], sf[q][(col >> 1) * 18 + (col & 1)], acc[5]);
+            } else if (t < 4 * nf + 18) {
+                acc[5] += sd[q][t - 4 * nf];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+        if (cb + j < 16 * nf) unsafeAtomicAdd(dw2 + o2 * 16 * nf + cb + j, (double)acc[j]);
+    const int t = threadIdx.x;
+    if (t < 4 * nf) unsafeAtomicAdd(dw1 + t, (double)acc[5]);
+    else if (t < 4 * nf + 2) unsafeAtomicAdd(dw1 + 4 * nf + (t - 4 * nf), (double)acc[5]);               // db1
+    else if (t < 4 * nf + 18) unsafeAtomicAdd(dw2 + 16 * 16 * nf + (t - 4 * nf - 2), (double)acc[5]);     // db2
+}
+
+// PixelLinkLoss for maps above PL_SORT pixels (150 x 150 in version "2s", up to 256 x 256 from gssd.pixellink_targets): pl_loss_kernel with
+// the sort replaced by a radix select.  The keys are probabilities in [0, 1]: non-negative floats order like their bit patterns, so four
+// passes of an 8-bit histogram over the candidates find the neg_area-th smallest key exactly -- the same threshold as key[neg_area - 1] of
+// the sorted array, hence the same mined set.  The probabilities are recomputed per pass (same expressions, same values).
+constexpr int PL_SELECT_MAX = 1 << 20;
+
+__device__ __forceinline__ float pl_bg_prob(const float* l0, const float* l1, int i) {
+    const float a = l0[i], c = l1[i];
+    const float m = fmaxf(a, c);
+    const float e0 = expf(a - m), e1 = expf(c - m);
+    return e0 / (e0 + e1);
+}
+
+__global__ __launch_bounds__(1024) void pl_loss_select_kernel(const float* __restrict__ out1, const float* __restrict__ out2,
+                                                              const long long* __restrict__ pixel_t, const unsigned char* __restrict__ neg_mask,
+                                                              const float* __restrict__ pos_w, const long long* __restrict__ link_t,
+                                                              double* __restrict__ res, float* __restrict__ neg_w_out, int HW, int ratio) {
+    __shared__ int hist[256];
+    __shared__ double red[16];
+    __shared__ int s_cnt[2];
+    __shared__ unsigned s_sel[2];          // prefix found so far, rank still to find within it
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* l0 = out1 + (size_t)b * 2 * HW;
+    const float* l1 = l0 + HW;
+    const unsigned char* nm = neg_mask + (size_t)b * HW;
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    int area = 0, ncand = 0;
+    for (int i = tid; i < HW; i += 1024) {
+        area += (int)pixel_t[(size_t)b * HW + i];
+        ncand += nm[i] == 1;
+    }
+    area = wave_sum(area);
+    ncand = wave_sum(ncand);
+    if ((tid & 63) == 0) {
+        atomicAdd(&s_cnt[0], area);
+        atomicAdd(&s_cnt[1], ncand);
+    }
+    __syncthreads();
+    area = s_cnt[0];
+    ncand = s_cnt[1];
+    int r_pos = area * ratio;
+    if (r_pos == 0) r_pos = 10000;                                   // criterion.py:41-43
+    const int neg_area = min(r_pos, ncand);
+    float thr = -INFINITY;
+    if (neg_area > 0) {                                               // (uniform over the workgroup)
+        if (tid == 0) {
+            s_sel[0] = 0u;
+            s_sel[1] = (unsigned)neg_area;
+        }
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            const unsigned prefix = s_sel[0], hmask = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
+            for (int i = tid; i < HW; i += 1024) {
+                if (nm[i] != 1) continue;
+                const unsigned u = __float_as_uint(pl_bg_prob(l0, l1, i));
+                if ((u & hmask) == prefix) atomicAdd(&hist[(u >> shift) & 255], 1);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned k = s_sel[1];
+                int d = 0;
+                for (; d < 255 && (unsigned)hist[d] < k; ++d) k -= (unsigned)hist[d];
+                s_sel[0] = prefix | ((unsigned)d << shift);
+                s_sel[1] = k;
+            }
+            __syncthreads();
+        }
+        thr = __uint_as_float(s_sel[0]);
+    }
+    double s_pos = 0.0, s_neg = 0.0;
+    for (int i = tid; i < HW; i += 1024) {
+        const float a = l0[i], c = l1[i];
+        const float m = fmaxf(a, c);
+        const float e0 = expf(a - m), e1 = expf(c - m);
+        const float p0 = e0 / (e0 + e1);
+        const long long t = pixel_t[(size_t)b * HW + i];
+        const float ce = (m + logf(e0 + e1)) - (t ? c : a);           // CrossEntropyLoss(reduce=False)
+        const bool sel = neg_area > 0 && p0 <= thr && nm[i] == 1;
+        if (neg_w_out) neg_w_out[(size_t)b * HW + i] = sel ? 1.f : 0.f;
+        s_pos += (double)(pos_w[(size_t)b * HW + i] * ce);
+        if (sel) s_neg += (double)ce;
+    }
+    s_pos = block_sum(s_pos, red);
+    s_neg = block_sum(s_neg, red);
+    double wp = 0.0, wn = 0.0, lp = 0.0, ln = 0.0;                    // link loss: as pl_loss_kernel
+    for (int i = tid; i < 8 * HW; i += 1024) {
+        const int n = i / HW, pix = i - n * HW;
+        const float a = out2[((size_t)b * 16 + 2 * n) * HW + pix], c = out2[((size_t)b * 16 + 2 * n + 1) * HW + pix];
+        const float m = fmaxf(a, c);
+        const long long t = link_t[((size_t)b * 8 + n) * HW + pix];
+        const float ce = (m + logf(expf(a - m) + expf(c - m))) - (t ? c : a);
+        const float w = pos_w[(size_t)b * HW + pix];
+        if (t == 1) {
+            wp += (double)w;
+            lp += (double)(w * ce);
+        } else if (t == 0) {
+            wn += (double)w;
+            ln += (double)(w * ce);
+        }
+    }
+    wp = block_sum(wp, red);
+    wn = block_sum(wn, red);
+    lp = block_sum(lp, red);
+    ln = block_sum(ln, red);
+    if (tid == 0) {
+        const double den = (double)area + (double)neg_area;
+        res[b * 6 + 0] = s_pos / den;
+        res[b * 6 + 1] = s_neg / den;
+        res[b * 6 + 2] = wp == 0.0 ? 0.0 : lp / wp;
+        res[b * 6 + 3] = wn == 0.0 ? 0.0 : ln / wn;
+        res[b * 6 + 4] = (double)area;
+        res[b * 6 + 5] = (double)neg_area;
+    }
+}
+
 }  // namespace
 
 extern "C" int gssd_interp_add_f32(const float* src, const float* addend, float* out, float* out2, int B, int Hs, int Ws, int Hd,
@@ -605,9 +886,13 @@ extern "C" int gssd_pixellink_loss_f32(const float* out1, const float* out2, con
                                        double* per_image, float* neg_weight_out, int B, int H, int W, int neg_pos_ratio,
                                        gssd_stream_t stream) {
     GSSD_CHECK_ARG(out1 && out2 && pixel_target && neg_pixel_mask && pixel_pos_weight && link_target && per_image);
-    GSSD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H * W <= PL_SORT && neg_pos_ratio > 0);
-    hipLaunchKernelGGL(pl_loss_kernel, dim3(B), dim3(1024), 0, as_stream(stream), out1, out2, pixel_target, neg_pixel_mask,
-                       pixel_pos_weight, link_target, per_image, neg_weight_out, H * W, neg_pos_ratio);
+    GSSD_CHECK_ARG(B > 0 && H > 0 && W > 0 && (long long)H * W <= PL_SELECT_MAX && neg_pos_ratio > 0);
+    if (H * W <= PL_SORT)
+        hipLaunchKernelGGL(pl_loss_kernel, dim3(B), dim3(1024), 0, as_stream(stream), out1, out2, pixel_target, neg_pixel_mask,
+                           pixel_pos_weight, link_target, per_image, neg_weight_out, H * W, neg_pos_ratio);
+    else
+        hipLaunchKernelGGL(pl_loss_select_kernel, dim3(B), dim3(1024), 0, as_stream(stream), out1, out2, pixel_target, neg_pixel_mask,
+                           pixel_pos_weight, link_target, per_image, neg_weight_out, H * W, neg_pos_ratio);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -654,9 +939,53 @@ extern "C" int gssd_pixellink_loss_bwd_f32(const float* out1, const float* out2,
 
 extern "C" int gssd_pixellink_decode_f32(const float* out1, const float* out2, int* labels, float* comps, int* ncomp, int B, int H,
                                          int W, float pixel_thr, float link_thr, int max_comp, gssd_stream_t stream) {
-    GSSD_CHECK_ARG(out1 && out2 && labels && comps && ncomp && B > 0 && H > 0 && W > 0 && H * W <= PL_MAXPIX && max_comp > 0);
-    hipLaunchKernelGGL(pl_decode_kernel, dim3(B), dim3(1024), 0, as_stream(stream), out1, out2, labels, comps, ncomp, H, W, pixel_thr,
-                       link_thr, max_comp);
+    GSSD_CHECK_ARG(out1 && out2 && labels && comps && ncomp && B > 0 && H > 0 && W > 0 && (long long)H * W <= PL_MAXPIX_LDS && max_comp > 0);
+    if (H * W <= PL_MAXPIX) {
+        hipLaunchKernelGGL(pl_decode_kernel, dim3(B), dim3(1024), 0, as_stream(stream), out1, out2, labels, comps, ncomp, H, W, pixel_thr,
+                           link_thr, max_comp);
+    } else {
+        const size_t smem = pl_decode_lds_bytes(H * W);
+        static unsigned attr_mask = 0;
+        if (gssd_attr_needed(&attr_mask)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(pl_decode_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)pl_decode_lds_bytes(PL_MAXPIX_LDS)) != hipSuccess) {
+                gssd_set_error("hipFuncSetAttribute failed (pixellink decode)");
+                return GSSD_ELAUNCH;
+            }
+        }
+        gssd_attr_done(&attr_mask);
+        hipLaunchKernelGGL(pl_decode_lds_kernel, dim3(B), dim3(1024), smem, as_stream(stream), out1, out2, labels, comps, ncomp, H, W,
+                           pixel_thr, link_thr, max_comp);
+    }
+    GSSD_CHECK_LAUNCH();
+    return GSSD_OK;
+}
+
+extern "C" int gssd_pixellink_final5_f32(const float* f0, const float* f1, const float* f2, const float* f3, const float* f4, int nf,
+                                         const float* w1, const float* b1, const float* w2, const float* b2, float* out1, float* out2, int B,
+                                         int HW, gssd_stream_t stream) {
+    GSSD_CHECK_ARG(f0 && w1 && b1 && w2 && b2 && out1 && out2 && B > 0 && HW > 0 && nf >= 1 && nf <= 5);
+    GSSD_CHECK_ARG((nf < 2 || f1) && (nf < 3 || f2) && (nf < 4 || f3) && (nf < 5 || f4));
+    const long long total = (long long)B * HW;
+    hipLaunchKernelGGL(pl_final5_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, as_stream(stream), f0, f1, f2, f3, f4, nf, w1, b1,
+                       w2, b2, out1, out2, B, HW);
+    GSSD_CHECK_LAUNCH();
+    return GSSD_OK;
+}
+
+extern "C" int gssd_pixellink_final5_bwd_f32(const float* d_out1, const float* d_out2, const float* f0, const float* f1, const float* f2,
+                                             const float* f3, const float* f4, int nf, const float* w1, const float* w2, float* g0, float* g1,
+                                             float* g2, float* g3, float* g4, int accumulate_mask, double* dw1, double* dw2, int B, int HW,
+                                             int ld, gssd_stream_t stream) {
+    GSSD_CHECK_ARG(d_out1 && d_out2 && f0 && w1 && w2 && g0 && dw1 && dw2 && B > 0 && HW > 0 && nf >= 1 && nf <= 5 && ld >= 18);
+    GSSD_CHECK_ARG((nf < 2 || (f1 && g1)) && (nf < 3 || (f2 && g2)) && (nf < 4 || (f3 && g3)) && (nf < 5 || (f4 && g4)));
+    const long long total = (long long)B * HW;
+    hipLaunchKernelGGL(pl_final5_bwd_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, as_stream(stream), d_out1, d_out2, nf, w1, w2,
+                       g0, g1, g2, g3, g4, accumulate_mask, B, HW, ld);
+    GSSD_CHECK_LAUNCH();
+    const int blocks = (int)((total + 127) / 128 > 1024 ? 1024 : (total + 127) / 128);
+    hipLaunchKernelGGL(pl_final5_wgrad_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), d_out1, d_out2, f0, f1, f2, f3, f4, nf, dw1,
+                       dw2, B, HW);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }

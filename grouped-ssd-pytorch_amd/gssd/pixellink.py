@@ -1,11 +1,12 @@
-"""Launch plan of PixelLink++ (ssd_liverdet/pixel_link/model.py:189-413, config version "4s") on the GSSD++ kernels.
+"""Launch plan of PixelLink++ (ssd_liverdet/pixel_link/model.py:189-413, config version "4s" or "2s") on the GSSD++ kernels.
 
 Nothing here is a new convolution: the grouped VGG trunk (conv + bias, ReLU applied by the consumer's fused input transform or by
 the pool pass), the Self_Attn blocks (merged projection + flash core + gated output conv), the slice_and_cat + fused deformable
 conv at the 75 x 75 stage, the 1x1 fuse conv + BatchNorm and the 1x1 score heads (pixel 2 + link 16 channels as ONE 18-channel
 conv per stage) are launches of the kernels the detector uses.  New are the upsample-add cascade and the final 1x1 convs
-(csrc/pixellink.hip).  fp32.  Every launch leaves a record (``rec``); a grad-enabled forward is followed by the HIP backward plan
-of gssd/backward.py::PixelLinkBackwardPlan (SURVEY.md 8f row 4 as a TRAINING row).
+(csrc/pixellink.hip).  Version "2s" adds a fifth output stage on the 150 x 150 relu2_2 map and one more cascade step.  fp32.
+Every launch leaves a record (``rec``); a grad-enabled forward is followed by the HIP backward plan of
+gssd/backward.py::PixelLinkBackwardPlan (SURVEY.md 8f row 4 as a TRAINING row).
 """
 import ctypes as C
 
@@ -76,7 +77,7 @@ class _PlanPixelLink(_Plan):
             for name in names:
                 cur, H, Cc = self._conv_raw(name, getattr(net, name), cur, H, Cc, g, xf)
                 xf = self._identity_relu(Cc)                  # the next conv of the stage applies this layer's ReLU on read
-            if si < 2:                                         # pool1 / pool2 directly behind the stage: ReLU + pool, one pass
+            if si == 0 or (si == 1 and net.version != "2s"):    # pool1 / pool2 directly behind the stage: ReLU + pool, one pass
                 cur, H = self._relu_pool(cur, H, Cc, (2, 2, 0, True))
                 continue
             cur, _ = self._relu_pool(cur, H, Cc, None)         # stage output: explicit ReLU (Self_Attn / heads read it)
@@ -91,21 +92,39 @@ class _PlanPixelLink(_Plan):
         assert H4 == H5
         t1 = self._interp(l5, H5, H4, addend=l4)[1]            # l5 + l4 (same size: the interpolation is the identity)
         t2 = self._interp(t1, H4, H3, addend=l3)[1]            # up(l5 + l4) + l3
-        f2, logit = self._interp(t2, H3, H2, addend=l2)        # up(...) ; + l2
-        if net.cascade_fuse:
-            f0 = self._interp(l5, H5, H2)[0]
-            f1 = self._interp(t1, H4, H2)[0]
-            feats = [f0, f1, f2, logit]
+        if net.version == "2s":                                # model.py:306-356 / 357-383: one more step to the 150 x 150 stage 1
+            (l1, H1) = self.l[1]
+            t3 = self._interp(t2, H3, H2, addend=l2)[1]        # up(up(l5 + l4) + l3) + l2
+            f3, logit = self._interp(t3, H2, H1, addend=l1)    # up(...) ; + l1
+            if net.cascade_fuse:
+                f0 = self._interp(l5, H5, H1)[0]
+                f1 = self._interp(t1, H4, H1)[0]
+                f2 = self._interp(t2, H3, H1)[0]
+                feats = [f0, f1, f2, f3, logit]
+            else:
+                feats = [logit]
+            Ho = H1
         else:
-            feats = [logit]
-        self.H_out = H2
+            f2, logit = self._interp(t2, H3, H2, addend=l2)    # up(...) ; + l2
+            if net.cascade_fuse:
+                f0 = self._interp(l5, H5, H2)[0]
+                f1 = self._interp(t1, H4, H2)[0]
+                feats = [f0, f1, f2, logit]
+            else:
+                feats = [logit]
+            Ho = H2
+        self.H_out = Ho
         self._final_step = len(self.steps)
         w1, b1 = net.final_1.weight.detach().view(2, -1), net.final_1.bias.detach()
         w2, b2 = net.final_2.weight.detach().view(16, -1), net.final_2.bias.detach()
-        ptrs = [f.data_ptr() for f in feats] + [0] * (4 - len(feats))
-        self._add(lib.gssd_pixellink_final_f32, ptrs + [len(feats), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), 0, 0, B,
-                                                        H2 * H2], keep=(w1, b1, w2, b2, feats))
-        self.rec.append(('plfinal', dict(feats=feats, H=H2, final_1=net.final_1, final_2=net.final_2)))
+        wargs = [len(feats), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), 0, 0, B, Ho * Ho]
+        if len(feats) > 4:                                     # five cascade features ("2s"): the nf <= 5 entry point
+            fn, nptr = lib.gssd_pixellink_final5_f32, 5
+        else:
+            fn, nptr = lib.gssd_pixellink_final_f32, 4
+        self._final_out = nptr + 5                              # argument index of out1 (out2 follows)
+        self._add(fn, [f.data_ptr() for f in feats] + [0] * (nptr - len(feats)) + wargs, keep=(w1, b1, w2, b2, feats))
+        self.rec.append(('plfinal', dict(feats=feats, H=Ho, final_1=net.final_1, final_2=net.final_2)))
 
     # ------------------------------------------------------------------------------------------------
     def _identity_relu(self, Cc):
@@ -164,7 +183,7 @@ class _PlanPixelLink(_Plan):
         """One output stage (model.py:238-262 and its three repeats): [SA-base] -> (75 x 75 stage only) [slice_and_cat] + DCN* ->
         x continues down the trunk;  side: [SA] -> fuse conv (+ BatchNorm, no ReLU) -> the 2 + 16 channel 1x1 heads."""
         net, B = self.eng.net, self.B
-        k = si                             # stage index k = 2 (conv3_3), 3, 4, 5 (fc7)
+        k = si                             # stage index k = 1 (conv2_2, "2s" only), 2 (conv3_3), 3, 4, 5 (fc7)
         attn_g = None
         if net.use_self_attention_base:
             x, attn_g = self._self_attn('self_attn_base_list', self.sab_i, x, H, Cc, need_out2=bool(net.dcn_cat_sab and k == 2))
@@ -232,7 +251,7 @@ class _PlanPixelLink(_Plan):
         out_2 = torch.empty(B, 16, Ho, Ho, device=dev)
         self.steps[self._pack_step].args[0] = x.data_ptr()
         fin = self.steps[self._final_step].args
-        fin[9], fin[10] = out_1.data_ptr(), out_2.data_ptr()
+        fin[self._final_out], fin[self._final_out + 1] = out_1.data_ptr(), out_2.data_ptr()
         if self.training:
             self.stats.zero_()
         stream = torch.cuda.current_stream().cuda_stream

@@ -1,6 +1,8 @@
 """``PixelLink`` (drop-in for ssd_liverdet/pixel_link/model.py:20-188: same constructor, attribute names and state-dict keys --
 including the ``modules_except_dcn`` aliases -- so reference checkpoints load); ``forward`` runs the HIP launch plan of
-gssd/pixellink.py (a grad-enabled call is differentiable: the HIP backward plan follows) and returns ``[out_1 [B,2,75,75], out_2 [B,16,75,75]]`` like model.py:413."""
+gssd/pixellink.py (a grad-enabled call is differentiable: the HIP backward plan follows) and returns
+``[out_1 [B,2,H,H], out_2 [B,16,H,H]]`` like model.py:413, H = 75 for pixel_link_config version "4s" and 150 for "2s" (a fifth output
+stage on conv2_2).  The version is read once, when the network is built."""
 import os
 
 import torch
@@ -14,6 +16,7 @@ _TRUNK = (('1_1', 12, 64), ('1_2', 64, 64), 'pool1', ('2_1', 64, 128), ('2_2', 1
           ('3_2', 256, 256), ('3_3', 256, 256), 'pool3', ('4_1', 256, 512), ('4_2', 512, 512), ('4_3', 512, 512), 'pool4',
           ('5_1', 512, 512), ('5_2', 512, 512), ('5_3', 512, 512), 'pool5')
 _STAGE_CH = {2: 256, 3: 512, 4: 512, 5: 1024}       # channels of the four output stages (conv3_3, conv4_3, conv5_3, fc7)
+_STAGE_CH_2S = {1: 128, **_STAGE_CH}                # version "2s": stage 1 (conv2_2, 150 x 150) first, as model.py:81-171 registers it
 
 
 def weights_init(m):                                  # model.py:14-17
@@ -26,9 +29,14 @@ class PixelLink(nn.Module):
     def __init__(self, cascade_fuse, use_fuseconv, batch_norm, use_self_attention, use_self_attention_base, num_dcn_layers,
                  groups_dcn, dcn_cat_sab, detach_sab, max_pool_factor=1):
         super().__init__()
-        if config.version != "4s" or config.feature_scale != 1 or not config.dilation:
-            raise NotImplementedError('the HIP PixelLink++ path is built for pixel_link_config version "4s", feature_scale 1, '
+        if config.version not in ("4s", "2s") or config.feature_scale != 1 or not config.dilation:
+            raise NotImplementedError('the HIP PixelLink++ path is built for pixel_link_config version "4s" or "2s", feature_scale 1, '
                                       'dilation True (the reference defaults)')
+        if config.version == "2s" and num_dcn_layers > 0:
+            raise NotImplementedError('version "2s" with num_dcn_layers > 0 is not defined: the reference itself fails there (its DCN after '
+                                      'conv2_2 expects 256 or 512 input channels and gets 128)')
+        self.version = config.version
+        stage_ch = _STAGE_CH_2S if self.version == "2s" else _STAGE_CH
         g = self.vgg_groups = config.vgg_groups
         self.scale = config.feature_scale
         self.cascade_fuse, self.use_fuseconv, self.batch_norm = cascade_fuse, use_fuseconv, batch_norm
@@ -51,23 +59,23 @@ class PixelLink(nn.Module):
         self.conv7 = nn.Conv2d(1024, 1024, 1, stride=1, padding=0, groups=g)
         self.relu7 = nn.ReLU()
         self.modules_except_dcn = nn.ModuleList(trunk + [self.conv6, self.relu6, self.conv7, self.relu7])
-        for k, c in _STAGE_CH.items():
+        for k, c in stage_ch.items():
             setattr(self, f'out{k}_1', nn.Conv2d(c, 2, 1))
             setattr(self, f'out{k}_2', nn.Conv2d(c, 16, 1))
             self.modules_except_dcn.extend([getattr(self, f'out{k}_1'), getattr(self, f'out{k}_2')])
         if use_fuseconv:
-            for k, c in _STAGE_CH.items():
+            for k, c in stage_ch.items():
                 setattr(self, f'fuse{k}', nn.Conv2d(c, c, kernel_size=1))
-            self.modules_except_dcn.extend([getattr(self, f'fuse{k}') for k in _STAGE_CH])
+            self.modules_except_dcn.extend([getattr(self, f'fuse{k}') for k in stage_ch])
             if batch_norm:
-                for k, c in _STAGE_CH.items():
+                for k, c in stage_ch.items():
                     setattr(self, f'bn_fuse{k}', nn.BatchNorm2d(c))
-                self.modules_except_dcn.extend([getattr(self, f'bn_fuse{k}') for k in _STAGE_CH])
-        nf = 4 if cascade_fuse else 1
+                self.modules_except_dcn.extend([getattr(self, f'bn_fuse{k}') for k in stage_ch])
+        nf = len(stage_ch) if cascade_fuse else 1
         self.final_1 = nn.Conv2d(2 * nf, 2, 1)
         self.final_2 = nn.Conv2d(16 * nf, 16, 1)
         self.modules_except_dcn.extend([self.final_1, self.final_2])
-        chans = list(_STAGE_CH.values())
+        chans = list(stage_ch.values())
         if use_self_attention_base:
             self.self_attn_base_in_channel_list = chans
             self.self_attn_base_list = nn.ModuleList([Self_Attn(c, max_pool_factor=max_pool_factor) for c in chans])

@@ -1,5 +1,5 @@
 """Module-level constants of ssd_liverdet/pixel_link/pixel_link_config.py the path reads (same names, same values)."""
-version = "4s"              # :1   ("2s" -- a fifth 150x150 output stage -- is not built in the HIP path)
+version = "4s"              # :1   ("2s": a fifth 150x150 output stage; pixel_link/model.py reads it when a network is built)
 dilation = True             # :4
 pixel_weight = 2            # :21
 link_weight = 1             # :20

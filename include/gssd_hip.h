@@ -730,7 +730,9 @@ int gssd_pixellink_final_f32(const float* f0, const float* f1, const float* f2, 
  * pixel_target [B][H][W] int64 (0/1), neg_pixel_mask [B][H][W] uint8, pixel_pos_weight [B][H][W] fp32, link_target [B][8][H][W] int64.
  * per_image [B][6] fp64 = {pixel_pos, pixel_neg, link_pos, link_neg, area, neg_area}: the reference's four losses are the batch
  * means of the first four columns.  neg_weight_out (optional) [B][H][W] = the mined-negative mask (criterion.py:47-48).
- * H*W <= 8192.  An image without a negative candidate is an IndexError in the reference; here its pixel_neg term is 0. */
+ * H*W <= 2^20: up to 8192 pixels the threshold comes from a bitonic sort in LDS, above that (the 150 x 150 maps of version "2s") from a
+ * radix select over the same keys -- the same threshold, the same mined set.  An image without a negative candidate is an IndexError in the
+ * reference; here its pixel_neg term is 0. */
 int gssd_pixellink_loss_f32(const float* out1, const float* out2, const long long* pixel_target, const unsigned char* neg_pixel_mask,
                             const float* pixel_pos_weight, const long long* link_target, double* per_image, float* neg_weight_out,
                             int B, int H, int W, int neg_pos_ratio, gssd_stream_t stream);
@@ -756,9 +758,30 @@ int gssd_pixellink_loss_bwd_f32(const float* out1, const float* out2, const long
  * 1 + rank of the pixel's connected component by its first pixel in raster order (the reference's root_map numbering; the reference
  * stores it as uint8 and wraps beyond 255 components, this does not).  comps [B][max_comp][6] = {pixel count, min x, min y, max x,
  * max y, sum of the positive-class probability} for the first min(max_comp, 1024) components (the rest: count 0); ncomp [B].
- * H*W <= 8192. */
+ * H*W <= 26624 (150 x 150 = 22500 in version "2s"): the label map lives in LDS, in dynamic LDS above 8192 pixels. */
 int gssd_pixellink_decode_f32(const float* out1, const float* out2, int* labels, float* comps, int* ncomp, int B, int H, int W,
                               float pixel_thr, float link_thr, int max_comp, gssd_stream_t stream);
+
+/* Version "2s" (pixel_link/model.py:153-155,306-356): final_1 / final_2 over nf <= 5 cascade features, the contract of
+ * gssd_pixellink_final_f32 / gssd_pixellink_final_bwd_f32 with a fifth map (w1 [2][2*nf], w2 [16][16*nf]; dw1 fp64 [2*2*nf + 2],
+ * dw2 fp64 [16*16*nf + 16]).  For nf <= 4 the forward and d(features) equal the four-map entry points' bit for bit. */
+int gssd_pixellink_final5_f32(const float* f0, const float* f1, const float* f2, const float* f3, const float* f4, int nf, const float* w1,
+                              const float* b1, const float* w2, const float* b2, float* out1, float* out2, int B, int HW, gssd_stream_t stream);
+int gssd_pixellink_final5_bwd_f32(const float* d_out1, const float* d_out2, const float* f0, const float* f1, const float* f2, const float* f3,
+                                  const float* f4, int nf, const float* w1, const float* w2, float* g0, float* g1, float* g2, float* g3,
+                                  float* g4, int accumulate_mask, double* dw1, double* dw2, int B, int HW, int ld, gssd_stream_t stream);
+
+/* fp32 flash-style backward of the Self_Attn core in key / value form (no [N][Nk] map; two deterministic launches, no atomics): with
+ * S = theta keys^T, P = exp(S - lse), dP = d(attn_g) values^T, dS = P o (dP - dvec):  dq = dS keys, dk = dS^T theta, dv = P^T d(attn_g).
+ * theta = tp [B][N] rows of qstride floats (first D); keys [B][Nk] rows of krow floats (phi inside tp, or the pooled keys); gT [B][C2][Nkp]
+ * the values transposed; dag [B][N][C2]; lse [B][N] from the training forward (gssd_self_attn_core_kv_f32); dvec[b][i] = <dag_i, attn_g_i>
+ * (gssd_rowdot_f32).  dq: rows of ld_q floats (D written); dk, dv: rows of ld_kv floats (D resp. C2 written) -- the [d theta | d phi | d g]
+ * rows of the merged projection's gradient, or the per-cell rows gssd_sa_unpool_f32 reads.  (D, C2) = (16, 64) only (Self_Attn(128), the
+ * 150 x 150 blocks of PixelLink "2s"): gssd_self_attn_flash_bwd_f32_supported; anything else is GSSD_EINVAL. */
+int gssd_self_attn_flash_bwd_f32_supported(int D, int C2);
+int gssd_self_attn_flash_bwd_f32(const float* tp, int qstride, const float* keys, int krow, const float* gT, int Nkp, const float* dag,
+                                 const float* lse, const float* dvec, float* dq, int ld_q, float* dk, float* dv, int ld_kv, int B, int N, int Nk,
+                                 int D, int C2, gssd_stream_t stream);
 
 /* The fp32 Self_Attn core on the BF16 matrix cores with fp32-equivalent products (csrc/flash_attn_x6.hip; layers/self_attn.py:68-80): the
  * contract of gssd_self_attn_core_f32 (tp [B][N][2D] fp32 theta | phi, gT [B][C2][Np] fp32, out [B][N][C2] fp32, optional lse [B][N]) with both

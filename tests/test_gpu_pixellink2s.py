@@ -1,0 +1,371 @@
+"""GPU tests of PixelLink version "2s" (the fifth, 150 x 150 output stage): forward against the reference fixture and the float64
+restatement, parameter gradients, the five-feature final kernels, the loss and decoding above 8192 pixels, the fp32 flash Self_Attn
+backward, the memory bound of an SA training step and an end-to-end training run from the device augmentation."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import pixellink_oracle as PO      # noqa: E402
+from gssd import synth                         # noqa: E402
+import pixellink2s_ref as R2                   # noqa: E402
+from test_pixellink2s_cpu import build2s       # noqa: E402
+from test_pixellink_cpu import rel             # noqa: E402
+
+TOL = 1e-4                                     # the 4s forward gate (tests/test_gpu_pixellink.py)
+_NETS = {}
+
+
+@pytest.fixture(scope='module')
+def dev():
+    assert torch.cuda.is_available(), 'these tests need the MI355X'
+    return torch.device('cuda:0')
+
+
+def net_of(tag):
+    """One network per variant and module, on the device, with its initial state dict kept on the CPU."""
+    if tag not in _NETS:
+        kw, mpf = R2.VARIANTS[tag]
+        net = build2s(kw, mpf)
+        sd = {k: v.clone() for k, v in net.state_dict().items()}
+        _NETS[tag] = (net.cuda(), sd)
+    net, sd = _NETS[tag]
+    net.load_state_dict(sd)                    # (running statistics, u / v and weights as built: tests may have trained it)
+    for p in net.parameters():
+        p.grad = None
+    return net, sd
+
+
+def sd64(sd, dev):
+    return {k: (v.to(dev, torch.float64) if v.is_floating_point() else v.to(dev)) for k, v in sd.items()}
+
+
+def l2rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).norm() / max(float(b.norm()), 1e-30))
+
+
+@pytest.mark.parametrize('tag', list(R2.VARIANTS))
+def test_forward_vs_reference_fixture(dev, golden, tag):
+    g = golden('pixellink2s')
+    net, _ = net_of(tag)
+    kw, _ = R2.VARIANTS[tag]
+    net.train()
+    with torch.no_grad():
+        o1, o2 = net(synth.synth_images(1, seed=300).to(dev))
+    assert tuple(o1.shape) == (1, 2, 150, 150) and tuple(o2.shape) == (1, 16, 150, 150)
+    r1 = g[f'model_{tag}_out1']
+    o1c = o1.cpu() if r1.shape[2] == 150 else o1.cpu()[:, :, ::3, ::3]
+    assert rel(o1c, r1) < TOL and rel(o2.cpu()[:, :, ::5, ::5], g[f'model_{tag}_out2s']) < TOL
+    sd = net.state_dict()
+    if kw['use_fuseconv'] and kw['batch_norm']:
+        assert rel(sd['bn_fuse1.running_mean'].cpu(), g[f'model_{tag}_bn_fuse1_rm']) < TOL
+        assert int(sd['bn_fuse1.num_batches_tracked']) == 1 and int(sd['bn_fuse5.num_batches_tracked']) == 1
+    if kw['use_self_attention']:
+        assert rel(sd['self_attn_list.0.snconv1x1_theta.weight_u'].cpu(), g[f'model_{tag}_sa0_u']) < TOL
+
+
+@pytest.mark.parametrize('tag,training', [('sa', True), ('plain', True), ('plain', False), ('nocascade', False)])
+def test_forward_b4_vs_restatement(dev, tag, training):
+    net, sd = net_of(tag)
+    kw, mpf = R2.VARIANTS[tag]
+    x = synth.synth_images(4, seed=401)
+    with torch.no_grad():
+        r1, r2, upd = R2.pixellink2s_forward(sd64(sd, dev), x.to(dev, torch.float64), max_pool_factor=mpf, training=training, **kw)
+        net.train(training)
+        o1, o2 = net(x.to(dev))
+    assert rel(o1.cpu(), r1.cpu()) < TOL and rel(o2.cpu(), r2.cpu()) < TOL
+    if training and kw['batch_norm']:
+        assert rel(net.bn_fuse1.running_var.cpu(), upd['bn_fuse1.running_var'].cpu()) < TOL
+
+
+def _loss_inputs(B, H, seed):
+    g = torch.Generator().manual_seed(seed)
+    pix = (torch.rand(B, H, H, generator=g) < 0.08).long()
+    neg = ((torch.rand(B, H, H, generator=g) < 0.9) & (pix == 0)).to(torch.uint8)
+    posw = torch.rand(B, H, H, generator=g) * pix.float()
+    link = (torch.rand(B, 8, H, H, generator=g) < 0.5).long() * pix[:, None]
+    return pix, neg, posw, link
+
+
+@pytest.mark.parametrize('tag', ['plain', 'sa'])
+def test_parameter_gradients_vs_float64(dev, tag):
+    """HIP forward -> PixelLinkLoss -> backward at B = 2 against float64 autograd through the restatement (and the loss oracle), relative
+    L2 error per parameter tensor with the bounds of the 4s test (tests/test_gpu_pixellink.py::test_backward_gradients_vs_oracle)."""
+    from pixel_link.criterion import PixelLinkLoss
+    net, sd = net_of(tag)
+    kw, mpf = R2.VARIANTS[tag]
+    B = 2
+    x = synth.synth_images(B, seed=311)
+    pix, neg, posw, link = _loss_inputs(B, 150, 5)
+    wts = (1.0, 1.0, 0.5, 0.5)
+    skip = ('running_mean', 'running_var', 'weight_u', 'weight_v', 'num_batches_tracked')
+    sdg = {k: (v.requires_grad_() if (v.is_floating_point() and not k.endswith(skip)) else v) for k, v in sd64(sd, dev).items()}
+    r1, r2, _ = R2.pixellink2s_forward(sdg, x.to(dev, torch.float64), max_pool_factor=mpf, training=True, **kw)
+    terms = PO.pixel_link_loss(r1.cpu(), r2.cpu(), pix, neg, posw, link, as_tensors=True)[:4]
+    sum(w * t for w, t in zip(wts, terms)).backward()
+    net.train()
+    o1, o2 = net(x.to(dev))
+    crit = PixelLinkLoss()
+    pp, pn = crit.pixel_loss(o1, pix.to(dev), neg.to(dev), posw.to(dev), link=(o2, link.to(dev)))
+    lp, ln = crit.link_loss(o2, link.to(dev))
+    (wts[0] * pp + wts[1] * pn + wts[2] * lp + wts[3] * ln).backward()
+    assert rel([float(pp), float(pn), float(lp), float(ln)], [float(t) for t in terms]) < 1e-4
+    named = dict(net.named_parameters(remove_duplicate=False))
+    keys = ['conv1_1.weight', 'conv2_1.bias', 'conv2_2.weight', 'conv3_3.bias', 'conv5_3.weight', 'conv6.weight', 'fuse1.weight',
+            'bn_fuse1.weight', 'bn_fuse1.bias', 'bn_fuse3.weight', 'out1_1.weight', 'out1_2.bias', 'out2_1.weight', 'out5_2.bias',
+            'final_1.weight', 'final_2.weight', 'final_2.bias']
+    if tag == 'sa':
+        keys += ['self_attn_list.0.snconv1x1_theta.weight_orig', 'self_attn_list.0.snconv1x1_phi.weight_orig',
+                 'self_attn_list.0.snconv1x1_g.weight_orig', 'self_attn_base_list.0.snconv1x1_theta.weight_orig',
+                 'self_attn_base_list.0.snconv1x1_g.weight_orig', 'self_attn_base_list.0.sigma', 'self_attn_list.0.sigma',
+                 'self_attn_base_list.4.snconv1x1_g.bias']
+    missing = [k for k in keys if named[k].grad is None]
+    assert not missing, missing
+    errs = {k: l2rel(named[k].grad, sdg[k].grad) for k in keys}
+    print(tag, '2s gradient L2-relative errors vs float64 autograd', {k: f'{v:.1e}' for k, v in errs.items()})
+    assert errs['final_1.weight'] < 1e-4 and errs['final_2.weight'] < 1e-4 and errs['final_2.bias'] < 1e-4
+    assert max(v for k, v in errs.items() if not k.endswith('sigma')) < 2e-2, errs
+    assert all(v < 6e-2 for k, v in errs.items() if k.endswith('sigma')), errs
+    assert all(torch.isfinite(p.grad).all() for p in net.parameters() if p.grad is not None)
+
+
+def test_final5_kernels(dev):
+    """gssd_pixellink_final5_f32 / _bwd_f32 against float64 at nf = 5; at nf = 4 and 1 the forward and d(features) equal the four-map
+    entry points' bit for bit (the weight gradient is summed with fp64 atomics in either: compared to 1e-6)."""
+    from gssd import _lib
+    lib, st = _lib.lib, torch.cuda.current_stream().cuda_stream
+    B, H, LD = 2, 150, 20
+    HW = H * H
+    gen = torch.Generator().manual_seed(9)
+    feats = [torch.randn(B, H, H, 18, generator=gen).to(dev) for _ in range(5)]
+    d1, d2 = torch.randn(B, 2, H, H, generator=gen).to(dev), torch.randn(B, 16, H, H, generator=gen).to(dev)
+    for nf in (5, 4, 1):
+        w1, b1 = torch.randn(2, 2 * nf, generator=gen).to(dev), torch.randn(2, generator=gen).to(dev)
+        w2, b2 = torch.randn(16, 16 * nf, generator=gen).to(dev), torch.randn(16, generator=gen).to(dev)
+        fp = [f.data_ptr() for f in feats[:nf]] + [0] * (5 - nf)
+        o1, o2 = torch.empty(B, 2, H, H, device=dev), torch.empty(B, 16, H, H, device=dev)
+        _lib.check(lib.gssd_pixellink_final5_f32(*fp, nf, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), o1.data_ptr(),
+                                                 o2.data_ptr(), B, HW, st))
+        gs = [torch.zeros(B, H, H, LD, device=dev) for _ in range(nf)]
+        dw1 = torch.zeros(4 * nf + 2, device=dev, dtype=torch.float64)
+        dw2 = torch.zeros(256 * nf + 16, device=dev, dtype=torch.float64)
+        gp = [g.data_ptr() for g in gs] + [0] * (5 - nf)
+        _lib.check(lib.gssd_pixellink_final5_bwd_f32(d1.data_ptr(), d2.data_ptr(), *fp, nf, w1.data_ptr(), w2.data_ptr(), *gp, 0,
+                                                     dw1.data_ptr(), dw2.data_ptr(), B, HW, LD, st))
+        # float64 reference
+        f64 = [f.double().permute(0, 3, 1, 2) for f in feats[:nf]]
+        x1 = torch.cat([f[:, :2] for f in f64], 1)
+        x2 = torch.cat([f[:, 2:] for f in f64], 1)
+        r1 = torch.einsum('oc,bchw->bohw', w1.double(), x1) + b1.double().view(1, 2, 1, 1)
+        r2 = torch.einsum('oc,bchw->bohw', w2.double(), x2) + b2.double().view(1, 16, 1, 1)
+        assert rel(o1.cpu(), r1.cpu()) < 1e-6 and rel(o2.cpu(), r2.cpu()) < 1e-6
+        gx1 = torch.einsum('oc,bohw->bchw', w1.double(), d1.double())
+        gx2 = torch.einsum('oc,bohw->bchw', w2.double(), d2.double())
+        for k in range(nf):
+            got = gs[k].permute(0, 3, 1, 2)
+            assert rel(got[:, :2].cpu(), gx1[:, 2 * k:2 * k + 2].cpu()) < 1e-6
+            assert rel(got[:, 2:18].cpu(), gx2[:, 16 * k:16 * k + 16].cpu()) < 1e-6
+            assert float(got[:, 18:].abs().max()) == 0.0
+        rw1 = torch.einsum('bohw,bchw->oc', d1.double(), x1)
+        rw2 = torch.einsum('bohw,bchw->oc', d2.double(), x2)
+        assert rel(dw1[:4 * nf].view(2, 2 * nf).cpu(), rw1.cpu()) < 1e-5 and rel(dw2[:256 * nf].view(16, 16 * nf).cpu(), rw2.cpu()) < 1e-5
+        assert rel(dw1[4 * nf:].cpu(), d1.double().sum((0, 2, 3)).cpu()) < 1e-5
+        assert rel(dw2[256 * nf:].cpu(), d2.double().sum((0, 2, 3)).cpu()) < 1e-5
+        if nf <= 4:
+            fp4 = fp[:4]
+            q1, q2 = torch.empty_like(o1), torch.empty_like(o2)
+            _lib.check(lib.gssd_pixellink_final_f32(*fp4, nf, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), q1.data_ptr(),
+                                                    q2.data_ptr(), B, HW, st))
+            hs = [torch.zeros(B, H, H, LD, device=dev) for _ in range(nf)]
+            ew1, ew2 = torch.zeros_like(dw1), torch.zeros_like(dw2)
+            hp = [h.data_ptr() for h in hs] + [0] * (4 - nf)
+            _lib.check(lib.gssd_pixellink_final_bwd_f32(d1.data_ptr(), d2.data_ptr(), *fp4, nf, w1.data_ptr(), w2.data_ptr(), *hp, 0,
+                                                        ew1.data_ptr(), ew2.data_ptr(), B, HW, LD, st))
+            assert torch.equal(q1, o1) and torch.equal(q2, o2)
+            assert all(torch.equal(g, h) for g, h in zip(gs, hs))
+            assert rel(dw1.cpu(), ew1.cpu()) < 1e-6 and rel(dw2.cpu(), ew2.cpu()) < 1e-6
+    with pytest.raises(_lib.GssdError):
+        _lib.check(lib.gssd_pixellink_final5_f32(*[f.data_ptr() for f in feats], 6, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                                                 b2.data_ptr(), o1.data_ptr(), o2.data_ptr(), B, HW, st))
+
+
+@pytest.mark.parametrize('H', [150, 256])
+def test_loss_large_maps_vs_oracle(dev, golden, H):
+    """PixelLinkLoss above 8192 pixels (radix select): the mined mask bit for bit and the four losses to 1e-6 against the oracle
+    (150 x 150: the reference fixture's inputs, with an image without positives and exact ties at the threshold); its backward against
+    float64 autograd through the oracle."""
+    from pixel_link.criterion import PixelLinkLoss
+    if H == 150:
+        o1, o2, pix, neg, posw, link = (torch.from_numpy(a) for a in R2.loss_inputs(11))
+    else:
+        gen = torch.Generator().manual_seed(256)
+        o1, o2 = torch.randn(3, 2, H, H, generator=gen) * 2, torch.randn(3, 16, H, H, generator=gen) * 2
+        pix, neg, posw, link = _loss_inputs(3, H, 12)
+    pp, pn, lp, ln, negw = PO.pixel_link_loss(o1, o2, pix, neg, posw, link)
+    crit = PixelLinkLoss()
+    h1, h2 = o1.to(dev).requires_grad_(), o2.to(dev).requires_grad_()
+    gp, gn = crit.pixel_loss(h1, pix.to(dev), neg.to(dev), posw.to(dev), link=(h2, link.to(dev)))
+    glp, gln = crit.link_loss(h2, link.to(dev))
+    assert torch.equal(crit.neg_pixel_weight.cpu().bool(), negw)
+    assert rel([float(gp), float(gn), float(glp), float(gln)], [pp, pn, lp, ln]) < 1e-6
+    if H == 150:
+        g = golden('pixellink2s')
+        assert np.array_equal(np.packbits(crit.neg_pixel_weight.cpu().numpy().astype(bool)), g['loss_neg_weight_bits'])
+        assert np.array_equal(crit.neg_area.cpu().numpy(), g['loss_neg_area'])
+        assert rel([float(gp), float(gn), float(glp), float(gln)], g['loss_vals']) < 1e-6
+    wts = (1.0, 0.7, 2.0, 0.3)
+    (wts[0] * gp + wts[1] * gn + wts[2] * glp + wts[3] * gln).backward()
+    a1, a2 = o1.double().requires_grad_(), o2.double().requires_grad_()
+    terms = PO.pixel_link_loss(a1, a2, pix, neg, posw, link, as_tensors=True)[:4]
+    sum(w * t for w, t in zip(wts, terms)).backward()
+    assert rel(h1.grad.cpu(), a1.grad) < 1e-5 and rel(h2.grad.cpu(), a2.grad) < 1e-5
+
+
+def test_decode_150_vs_oracle(dev, golden):
+    """Link decoding of 150 x 150 maps (the dynamic-LDS kernel): label maps and component counts equal to the oracle's and, modulo the
+    reference's uint8 numbering, to the reference fixture; a random map with hundreds of components as well."""
+    from pixel_link.postprocess import decode
+    d1, d2 = (torch.from_numpy(a) for a in R2.decode_inputs(21))
+    gen = torch.Generator().manual_seed(3)
+    e1, e2 = torch.randn(2, 2, 150, 150, generator=gen), torch.randn(2, 16, 150, 150, generator=gen) * 2.5
+    for a1, a2 in ((d1, d2), (e1, e2)):
+        want = PO.decode_links(a1, a2)
+        labels, comps, ncomp = decode(a1.to(dev), a2.to(dev))
+        assert np.array_equal(labels.cpu().numpy(), want)
+        assert np.array_equal(ncomp.cpu().numpy(), want.reshape(len(want), -1).max(1))
+        c = comps.cpu().numpy()
+        for b in range(len(want)):
+            n = min(int(want[b].max()), c.shape[1])
+            counts = np.bincount(want[b].ravel(), minlength=n + 1)[1:n + 1]
+            assert np.array_equal(c[b, :n, 0], counts)
+    g = golden('pixellink2s')
+    labels, _, _ = decode(d1.to(dev), d2.to(dev))
+    assert np.array_equal(labels.cpu().numpy().astype(np.uint8), g['dec_labels_u8'])
+    print("components per image", ncomp.tolist())
+
+
+def _flash_case(dev, B, H, P, seed):
+    """Inputs of the attention core of one Self_Attn(128) block in the plan's layouts, and float64 gradients."""
+    from gssd import _lib, ops
+    lib, st = _lib.lib, torch.cuda.current_stream().cuda_stream
+    D, C2 = 16, 64
+    N = H * H
+    Nk = P * P
+    Nkp = ops.round_up(Nk, 4)
+    gen = torch.Generator().manual_seed(seed)
+    tp = (torch.randn(B, N, 2 * D, generator=gen) * 0.5).to(dev)
+    if P == H:
+        keys, krow = tp[:, :, D:], 2 * D
+    else:
+        keys, krow = (torch.randn(B, Nk, D, generator=gen) * 0.5).to(dev), D
+    vals = torch.randn(B, Nk, C2, generator=gen).to(dev)
+    gT = torch.zeros(B, C2, Nkp, device=dev)
+    gT[:, :, :Nk] = vals.transpose(1, 2)
+    dag = torch.randn(B, N, C2, generator=gen).to(dev)
+    th64, k64, v64, dag64 = tp[:, :, :D].double(), keys.double(), vals.double(), dag.double()
+    S = th64 @ k64.transpose(1, 2)
+    lse64 = torch.logsumexp(S, -1)
+    A = torch.exp(S - lse64[..., None])
+    ag64 = A @ v64
+    dA = dag64 @ v64.transpose(1, 2)
+    Dv64 = (dag64 * ag64).sum(-1)
+    dS = A * (dA - Dv64[..., None])
+    want = (dS @ k64, dS.transpose(1, 2) @ th64, A.transpose(1, 2) @ dag64)
+    del S, A, dA, dS
+    lse, Dv = lse64.float().contiguous(), Dv64.float().contiguous()
+    dq = torch.full((B, N, 2 * D + C2), float('nan'), device=dev)
+    dkv = torch.full((B, Nk, D + C2), float('nan'), device=dev)
+    if P == H:
+        dk, dv, ld_kv = dq[:, :, D:], dq[:, :, 2 * D:], 2 * D + C2
+    else:
+        dk, dv, ld_kv = dkv[:, :, :D], dkv[:, :, D:], D + C2
+    _lib.check(lib.gssd_self_attn_flash_bwd_f32(tp.data_ptr(), 2 * D, keys.data_ptr(), krow, gT.data_ptr(), Nkp, dag.data_ptr(),
+                                                lse.data_ptr(), Dv.data_ptr(), dq.data_ptr(), 2 * D + C2, dk.data_ptr(), dv.data_ptr(), ld_kv,
+                                                B, N, Nk, D, C2, st))
+    got = (dq[:, :, :D], dk[:, :, :D], dv[:, :, :C2])
+    return got, want
+
+
+@pytest.mark.parametrize('B,H,P', [(1, 150, 150), (2, 150, 75), (2, 37, 37), (1, 37, 12)])
+def test_flash_backward_kernel_vs_float64(dev, B, H, P):
+    """gssd_self_attn_flash_bwd_f32 alone against float64: 150 x 150 unpooled (N = Nk = 22 500), pooled P = 75, and ragged token counts
+    (N = 1369, Nk = 144: neither a multiple of the 64-token tiles).  Measured on the MI355X: at most 1.5e-6 L2-relative (d theta, 150 x 150
+    unpooled), 5.0e-7 on the ragged maps.  The bound 2e-5 keeps a factor of ten over that for fp32 sums of up to 22 500 terms of mixed
+    sign in another order; the test prints the errors of every run."""
+    got, want = _flash_case(dev, B, H, P, seed=H * 1000 + P)
+    errs = [l2rel(g_, w_) for g_, w_ in zip(got, want)]
+    print(f'flash bwd B={B} N={H * H} Nk={P * P}: dq {errs[0]:.2e} dk {errs[1]:.2e} dv {errs[2]:.2e}')
+    assert all(torch.isfinite(g_).all() for g_ in got)
+    assert max(errs) < 2e-5, errs
+    got2, _ = _flash_case(dev, B, H, P, seed=H * 1000 + P)
+    assert all(torch.equal(a, b) for a, b in zip(got, got2))           # no atomics: bit-reproducible
+
+
+def test_sa_training_step_memory_bounded(dev):
+    """One SA-2s training step (SA + SA-base, max_pool_factor 1) at B = 4: the 150 x 150 blocks' backward runs on the flash kernel, the
+    peak allocation stays under 16 GB (the explicit attention maps alone would be about 32 GB)."""
+    import gc
+    from pixel_link.criterion import PixelLinkLoss
+    for n_, _ in _NETS.values():                 # drop the launch plans the other tests cached (one per batch size and mode)
+        n_.__dict__['_engine'] = None
+    gc.collect()
+    net, _ = net_of('sa')
+    net.train()
+    B = 4
+    x = synth.synth_images(B, seed=411).to(dev)
+    pix, neg, posw, link = (t.to(dev) for t in _loss_inputs(B, 150, 8))
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    o1, o2 = net(x)
+    crit = PixelLinkLoss()
+    pp, pn = crit.pixel_loss(o1, pix, neg, posw, link=(o2, link))
+    lp, ln = crit.link_loss(o2, link)
+    (pp + pn + lp + ln).backward()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated()
+    print(f'SA-2s step B=4: peak {peak / 2 ** 30:.2f} GiB ({(peak - base) / 2 ** 30:.2f} GiB above the start)')
+    assert peak < 16 * 2 ** 30
+    assert all(torch.isfinite(p.grad).all() for p in net.parameters() if p.grad is not None)
+    assert net.self_attn_base_list[0].snconv1x1_theta.weight_orig.grad is not None
+
+
+def test_end_to_end_training_from_device_augmentation(dev):
+    """SSDAugmentationCUDA(use_pixel_link=True, pixel_link_version="2s") -> PixelLink 2s -> PixelLinkLoss -> backward -> SGD, B = 4:
+    the losses stay finite and fall; mask_to_box runs on the output."""
+    from utils.augmentations import SSDAugmentationCUDA
+    from pixel_link.criterion import PixelLinkLoss
+    from pixel_link.postprocess import mask_to_box
+    import random
+    net, _ = net_of('plain')
+    net.train()
+    B = 4
+    studies = np.stack([synth.synth_study_u8(8100 + i, 4, 320) for i in range(B)])
+    boxes = [np.array([[0.2, 0.25, 0.45, 0.5, 0.], [0.55, 0.5, 0.8, 0.7, 0.]], np.float32) for _ in range(B)]
+    aug = SSDAugmentationCUDA(0.01, 1.5, 300, (49, 49, 49), use_normalize=True, use_pixel_link=True, pixel_link_version="2s")
+    x, t = aug(torch.from_numpy(studies).to(dev), boxes, py_rng=random.Random(4), np_rng=np.random.RandomState(4))
+    assert tuple(t['pixel_mask'].shape) == (B, 150, 150) and tuple(t['link_mask'].shape) == (B, 8, 150, 150)
+    crit = PixelLinkLoss()
+    losses, opt = [], None
+    for _ in range(4):
+        if opt is not None:
+            opt.zero_grad(set_to_none=True)
+        o1, o2 = net(x)
+        pp, pn = crit.pixel_loss(o1, t['pixel_mask'], t['neg_pixel_mask'], t['pixel_pos_weight'], link=(o2, t['link_mask']))
+        lp, ln = crit.link_loss(o2, t['link_mask'])
+        loss = pp + pn + lp + ln
+        loss.backward()
+        if opt is None:
+            g2 = sum(float((p.grad.double() ** 2).sum()) for p in net.parameters() if p.grad is not None)
+            opt = torch.optim.SGD(net.parameters(), lr=0.02 * float(loss) / g2)
+        opt.step()
+        losses.append(float(loss))
+    print('2s training losses', [round(v, 4) for v in losses])
+    assert all(np.isfinite(losses)) and losses[-1] < losses[0]
+    with torch.no_grad():
+        net.eval()
+        o1, o2 = net(x)
+    boxes_out = mask_to_box(o1, o2)
+    assert len(boxes_out) == B and all(isinstance(b, list) for b in boxes_out)

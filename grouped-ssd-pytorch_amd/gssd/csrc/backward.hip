@@ -4,12 +4,10 @@
 // Replaces autograd's native_batch_norm_backward / threshold_backward / max_pool2d_with_indices_backward chain behind
 // loss.backward() (train_lesion_multiphase_v2.py:247-248).
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
-typedef unsigned short u16;
 #ifndef BN_UNR
 #define BN_UNR 2
 #endif
@@ -32,7 +30,6 @@ __device__ __forceinline__ f32x4 ld4<u16>(const u16* p) {
                  __uint_as_float(v.y & 0xffff0000u)};
 }
 __device__ __forceinline__ void st4_bf16(u16* p, const f32x4 v) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     bf16x4 h;
 #pragma unroll
     for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];

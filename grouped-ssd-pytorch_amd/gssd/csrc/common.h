@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "gssd_hip.h"
 
 void gssd_set_error(const char* fmt, ...);
@@ -26,22 +27,40 @@ void gssd_set_error(const char* fmt, ...);
 
 static inline hipStream_t as_stream(gssd_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE: every call site keeps one "done" bit per device id, so a
-// process that touches several GPUs (tests on cuda:1, one-process multi-device callers) never launches a > 48 KB-LDS kernel
-// without it.  Launches come from two host threads (the forward from the caller's, the backward from autograd's): the bit is
-// published (gssd_attr_done, release) only AFTER hipFuncSetAttribute has returned success, so a thread that sees it set may
-// launch; two threads racing on an unset bit both set the attribute (idempotent), and a failed call is retried by the next launch.
-static inline bool gssd_attr_needed(unsigned* mask) {
+// Raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize; a launch with more than 48 KB needs it) once per
+// device.  The attribute is per DEVICE: `mask` is the launch site's own `static unsigned`, one "done" bit per device id, so a process
+// that touches several GPUs (tests on cuda:1, one-process multi-device callers) never launches a large-LDS kernel without it.  Launches
+// come from two host threads (the forward from the caller's, the backward from autograd's): the bit is published (release) only AFTER
+// hipFuncSetAttribute has returned success, so a thread that sees it set (acquire: the one atomic load of the steady state) may launch;
+// two threads racing on an unset bit both set the attribute (idempotent), and a failed call is retried by the next launch.
+// A launch site that picks one of two kernels at run time passes both and shares one mask.  Returns GSSD_OK or GSSD_ELAUNCH.
+template <typename K, typename K2 = void()>
+static inline int gssd_max_dynamic_lds(unsigned* mask, K* kernel, size_t bytes, K2* kernel2 = nullptr, size_t bytes2 = 0) {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 32) return true;
-    return (__atomic_load_n(mask, __ATOMIC_ACQUIRE) & (1u << dev)) == 0;
+    const bool tracked = dev >= 0 && dev < 32;
+    if (tracked && (__atomic_load_n(mask, __ATOMIC_ACQUIRE) & (1u << dev))) return GSSD_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", bytes);
+        return GSSD_ELAUNCH;
+    }
+    if (kernel2 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes2) != hipSuccess) {
+        gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", bytes2);
+        return GSSD_ELAUNCH;
+    }
+    if (tracked) (void)__atomic_fetch_or(mask, 1u << dev, __ATOMIC_RELEASE);
+    return GSSD_OK;
 }
-static inline void gssd_attr_done(unsigned* mask) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 32) (void)__atomic_fetch_or(mask, 1u << dev, __ATOMIC_RELEASE);
+
+// Environment switches are read once per process (function-local `static const` at the site that asks).  The common kind is ON unless
+// its value starts with '0' (unset, empty, "1", anything else: on); the presence-only and numeric switches are read where they are used.
+static inline bool gssd_env_off(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '0';
 }
+// GSSD_X6_F16=0 turns the fp16 planes of the fp32-equivalent kernels off everywhere: bf16 planes only (runtime.hip)
+bool gssd_x6_f16_enabled();
 
 // BatchNorm batch sums (gssd_conv_desc::stats) may be kept in `rep` replicas of [2 * Cout] doubles: a workgroup adds into replica
 // (workgroup id mod rep), the consumers (gssd_bn_finalize_*, gssd_bn_relu_pool_*, gssd_bn_bwd_finalize_f32) add the replicas up in a

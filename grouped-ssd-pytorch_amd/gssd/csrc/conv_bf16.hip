@@ -11,11 +11,7 @@
 //   (before rounding); everything after the accumulator (1/sigma, bias, gate, residual) is fp32, rounded once on store.
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 namespace {
 
@@ -23,26 +19,9 @@ constexpr int BK = 64;          // bf16 per tile row = 128 B = 8 DMA lanes
 
 __device__ __attribute__((aligned(16))) u16 g_zero_page_h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int BN>            // (instantiated with 16 where a wave owns ONE 16-channel tile: no pairing, identity)
-__device__ __forceinline__ int chan_of_row(int row) {        // LDS row of the weight tile -> output channel inside the BN tile
-    if (BN < 32) return row;
-    const int j = row >> 4, rho = row & 15;
-    return 32 * (j >> 1) + 8 * (rho >> 2) + 4 * (j & 1) + (rho & 3);
-}
-
-__device__ __forceinline__ float bf2f(u16 h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
-
-// (csrc/conv_igemm.hip: the counted wait of the NSTG >= 3 K loop -- no fence, the ring's younger pieces stay in flight)
-template <int N>
-__device__ __forceinline__ void wait_vm_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
+// chan_of_row of a BN-column tile (instantiated with 16 where a wave owns ONE 16-channel tile: no pairing, identity)
+template <int BN>
+__device__ __forceinline__ int tile_chan_of_row(int row) { return BN < 32 ? row : chan_of_row(row); }
 
 // NSTG: LDS stages of the K loop; 3 = the small-map form (32- / 64-row tiles, two chunks in flight), see csrc/conv_igemm.hip
 template <int BM, int BN, int WM, int WN, int NSTG>
@@ -119,7 +98,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_bf16_kernel(const gssd_conv
 #pragma unroll
     for (int j = 0; j < BR; ++j) {
         const int row = (j * NW + wave) * 8 + row_in;
-        const int ch = chan_of_row<(NT == 1 ? 16 : BN)>(row);
+        const int ch = tile_chan_of_row<(NT == 1 ? 16 : BN)>(row);
         b_ok[j] = (j * NW + wave) < BPIECES && (n0g + ch) < cout_g;
         b_off[j] = (n0g + ch) * p.wgt_row_stride + 8 * lq;
     }
@@ -417,14 +396,7 @@ int launch_cfg(const gssd_conv_desc& d, int M, int images, hipStream_t stream) {
     constexpr size_t smem_base = NSTG * (size_t)(BM + BN) * BK * sizeof(u16);
     const size_t smem = smem_base + (d.in_scale ? 2 * (size_t)d.cin_g * sizeof(float) : 0);
     auto kern = conv_bf16_kernel<BM, BN, WM, WN, NSTG>;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(smem_base + 8192)) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", smem_base + 8192);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem_base + 8192)) return rc;
     const int cout_g = d.Cout / d.groups;
     const int tiles = (cout_g + BN - 1) / BN;
     const int mtiles = (M + BM - 1) / BM;

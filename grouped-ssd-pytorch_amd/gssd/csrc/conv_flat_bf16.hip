@@ -29,11 +29,7 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 #ifdef FLAT_TIMING
 // debug build (scripts/flat_timing.py): wave 0 of every workgroup accumulates the shader clocks between its phase boundaries
@@ -53,27 +49,6 @@ namespace {
 
 __device__ __attribute__((aligned(16))) u16 g_zero_flat_h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// wait until at most N of this wave's vector-memory operations (LDS-DMA pieces) are outstanding, then the workgroup barrier --
-// NO fence: the DMA pieces of later ring stages stay in flight across it
-template <int N>
-__device__ __forceinline__ void wait_vm_barrier() {
-    // lgkmcnt(0): this wave's fragment reads of the previous slice have RETURNED (hipcc sinks their MFMAs below the barrier), so the
-    // DMA another wave issues right behind the barrier may overwrite that ring stage
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ void wait_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct FlatParams {
@@ -90,7 +65,7 @@ struct FlatParams {
 
 // XOR applied to the 16-byte unit index of window pixel pp (conflict-free ds_read_b128 for 16 consecutive pixels at any base)
 template <int UPR>
-__device__ __forceinline__ int swz(int pp) {
+__device__ __forceinline__ int swz_px(int pp) {
     return UPR == 8 ? (pp & 7) : ((pp ^ (pp >> 1)) & 3);
 }
 // weight ring rows are 64 bytes (4 units): unit kq of row rho sits at kq ^ wswz(rho >> 2)
@@ -271,7 +246,7 @@ __global__ __launch_bounds__(WMW * WNW * 64, WMW * WNW == 4 ? 2 : 1) void conv_f
             {
                 const int ninstr = (npp + PPI - 1) / PPI;
                 const int pp0 = lane / UPR;
-                const int lu = (lane % UPR) ^ swz<UPR>(pp0);
+                const int lu = (lane % UPR) ^ swz_px<UPR>(pp0);
                 const u16* src0 = in_g + ((long long)(qstart + pp0) * p.C + h * CP + lu * 8);
                 const long long adv = (long long)PPI * p.C;
                 for (int n = wave; n < ninstr; n += NW) {
@@ -293,8 +268,8 @@ __global__ __launch_bounds__(WMW * WNW * 64, WMW * WNW == 4 ? 2 : 1) void conv_f
                     const int pp2 = pp + NTHR / UPR;
                     const bool ok1 = (unsigned)(qstart + pp) < (unsigned)HW;
                     const bool ok2 = pp2 < npp && (unsigned)(qstart + pp2) < (unsigned)HW;
-                    u16* at1 = patch + pp * CP + (((tid % UPR) ^ swz<UPR>(pp)) << 3);
-                    u16* at2 = patch + (ok2 ? pp2 : pp) * CP + (((tid % UPR) ^ swz<UPR>(ok2 ? pp2 : pp)) << 3);
+                    u16* at1 = patch + pp * CP + (((tid % UPR) ^ swz_px<UPR>(pp)) << 3);
+                    u16* at2 = patch + (ok2 ? pp2 : pp) * CP + (((tid % UPR) ^ swz_px<UPR>(ok2 ? pp2 : pp)) << 3);
                     bf16x8 v1 = *reinterpret_cast<const bf16x8*>(at1), v2 = *reinterpret_cast<const bf16x8*>(at2);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
@@ -324,7 +299,7 @@ __global__ __launch_bounds__(WMW * WNW * 64, WMW * WNW == 4 ? 2 : 1) void conv_f
 #pragma unroll
                     for (int i = 0; i < MT; ++i) {
                         const int pl = pb0 + 16 * i + toff;
-                        u32x4 v = *reinterpret_cast<const u32x4*>(patch + pl * CP + (((cs * 4 + kq) ^ swz<UPR>(pl)) << 3));
+                        u32x4 v = *reinterpret_cast<const u32x4*>(patch + pl * CP + (((cs * 4 + kq) ^ swz_px<UPR>(pl)) << 3));
                         if constexpr (dx == 0) v = left[i] ? u32x4{0u, 0u, 0u, 0u} : v;
                         if constexpr (dx == 2) v = right[i] ? u32x4{0u, 0u, 0u, 0u} : v;
                         pf[i] = __builtin_bit_cast(bf16x8, v);
@@ -388,14 +363,7 @@ int launch_flat_n(const gssd_conv_desc& d, const FlatParams& p, size_t smem, hip
     }
     auto kern = conv_flat_bf16_kernel<CIN_G, COUT_T, XF, NSTG, WMW, WNW>;
     static unsigned attr_mask = 0;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (flat bf16 conv)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, 160 * 1024)) return rc;
     // persistent: one workgroup per resident slot (two 256-thread or one 512-thread workgroup per CU), never more than there are tiles;
     // GSSD_FLAT_PERSIST=0 launches one workgroup per tile instead (ablation: 15 .. 25 % slower, the slot waits for its own stores)
     static const bool persist = !(getenv("GSSD_FLAT_PERSIST") && atoi(getenv("GSSD_FLAT_PERSIST")) == 0);

@@ -22,26 +22,13 @@
 // see include/gssd_hip.h for the call-site map.
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
 constexpr int BK = 32;          // floats per tile row = 128 B = 8 DMA lanes
 
 __device__ __attribute__((aligned(16))) float g_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// wait until at most N of this wave's LDS-DMA pieces are outstanding and this wave's fragment reads have returned, then the workgroup
-// barrier -- NO fence (a __syncthreads() waits vmcnt(0) and would drain the ring of the NSTG >= 3 form)
-template <int N>
-__device__ __forceinline__ void wait_vm_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // NSTG = LDS stages of the K loop.  2: the chunk's DMA is issued one chunk ahead and every chunk ends in a __syncthreads() -- right for
 // the large layers, whose MFMAs per chunk cover the load latency.  3 (round 4, the small-map launches: <= 10 x 10 maps, M <= 3200): two
@@ -375,14 +362,7 @@ int launch_cfg(const gssd_conv_desc& d, int M, int images, hipStream_t stream) {
     constexpr size_t smem_base = NSTG * (size_t)(BM + BN) * BK * sizeof(float);
     const size_t smem = smem_base + (d.in_scale ? 2 * (size_t)d.cin_g * sizeof(float) : 0);
     auto kern = conv_igemm_kernel<BM, BN, WM, WN, NSTG>;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(smem_base + 4096)) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", smem_base + 4096);
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem_base + 4096)) return rc;
     const int cout_g = d.Cout / d.groups;
     const int tiles = (cout_g + BN - 1) / BN;
     const int mtiles = (M + BM - 1) / BM;

@@ -8,17 +8,11 @@
 // 16-channel blocks, the (tap, 16-input-channel) list.
 // MFMA: D[co][ci] += sum over 4 pixels dY[px][co] * X[px + tap][ci]   (v_mfma_f32_16x16x4_f32, k = 4 pixels).
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
 __device__ __attribute__((aligned(16))) float g_zero_page_pw[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct PatchWgradParams {
     const float* in;
@@ -159,14 +153,7 @@ int launch_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipS
     const size_t smem = ((size_t)((180 + PPI - 1) / PPI) * PPI * CIN_G + 128 * COUT_G) * sizeof(float);
     auto kern = conv_patch_wgrad_kernel<CIN_G, COUT_G, XF>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) !=
-            hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (patch wgrad)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, 80 * 1024)) return rc;
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     static int per_cu = 0;                                // resident workgroups per CU: 2 for the 64-channel variant, up to 4
     if (!per_cu) {                                        // for the small ones (they hide each other's staging latency)

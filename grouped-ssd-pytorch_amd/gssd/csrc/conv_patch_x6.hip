@@ -5,7 +5,7 @@
 // splits every input value nine times, once per tap.  Here an input value is loaded and split ONCE per 32-channel chunk:
 //   * a workgroup (four waves) owns an 8 x 16 output tile and all (<= 128) output channels, accumulators in registers for the whole K loop;
 //   * per chunk of 32 input channels the 10 x 18 patch is staged through registers (loads a chunk ahead), split into two fp16 planes (h, (x - h) * 2048:
-//     conv_thin_x6.hip) and written to LDS as [plane][pixel][32 channels], 16-byte units swizzled by the patch column;
+//     kernel_util.h, split2_pair) and written to LDS as [plane][pixel][32 channels], 16-byte units swizzled by the patch column;
 //   * the nine taps of the chunk are nine K steps of 32: the A fragment of (tap, output row) is a shifted 16-pixel window of the patch, the weight planes of
 //     (chunk, tap) -- packed once in LDS-image order -- arrive by LDS-DMA through a three-stage ring, two taps ahead; one barrier per tap;
 //   * wave w owns output channels 32 w .. 32 w + 31: per tap 16 activation + 4 weight fragment reads for 48 MFMAs (three per product: h h' into the main
@@ -13,14 +13,8 @@
 // Only launches the caller flags GSSD_CONV_F16_OK (include/gssd_hip.h) and points at the packed planes (gssd_conv_desc::wgt_patch): everything else stays
 // where it was.  GSSD_PATCH_X6=0 switches it off.
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
 
 namespace {
 
@@ -36,19 +30,6 @@ constexpr int NLD = NPAD * (CK / 4) / NTHR;       // 16-byte loads per thread an
 
 // 64-byte pixels: bit 2 of the patch column into bit 1 of the 16-byte unit (conv_thin_x6.hip: conflict-free for the lane groups of a ds_read_b128)
 __device__ __forceinline__ int swz_a(int col) { return (col >> 1) & 2; }
-// 64-byte weight rows (dcn_x6.hip)
-__device__ __host__ __forceinline__ int swz_b(int row) { return (row & 8) ? 3 : 0; }
-
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void split2_pair(const float a, const float b, unsigned& ph, unsigned& pl) {
-    const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
-    const f32x2 r = (f32x2{a, b} - __builtin_convertvector(h, f32x2)) * 2048.f;
-    ph = __builtin_bit_cast(unsigned, h);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-}
 
 struct PatchX6Params {
     const float* in;
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv_patch_x6_kernel(const PatchX6Par
     write_planes();
     if (nchunks > 1) load_chunk(1);
 
-    const int boff = (32 * wave + r) * CK + ((kq ^ swz_b(r)) << 3);       // this lane's weight fragment of column tile 0 (tile 1: + 16 rows)
+    const int boff = (32 * wave + r) * CK + ((kq ^ swz64(r)) << 3);       // this lane's weight fragment of column tile 0 (tile 1: + 16 rows)
     for (int s = 0; s < nsteps; ++s) {
         const int cc = s / 9, tap = s - cc * 9;
         const int dy = tap / 3, dx = tap - dy * 3;
@@ -197,7 +178,7 @@ __global__ void conv_patch_x6_pack_kernel(const float* __restrict__ w, u16* __re
         const int e = (int)(i & 7), slot = (int)((i >> 3) & 3), row = (int)((i >> 5) & (BN - 1));
         const long long s = i >> 12;                      // K step = chunk * 9 + tap (WPLANE = 4096 elements per plane and step)
         const int cc = (int)(s / 9), tap = (int)(s - 9 * (long long)cc);
-        const int c = cc * CK + ((slot ^ swz_b(row)) << 3) + e;
+        const int c = cc * CK + ((slot ^ swz64(row)) << 3) + e;
         const float v = row < Cout ? w[(size_t)row * row_stride + (size_t)tap * C + c] : 0.f;
         const _Float16 h = (_Float16)v;
         wp[s * WSTAGE + (i & (WPLANE - 1))] = __builtin_bit_cast(u16, h);
@@ -206,11 +187,7 @@ __global__ void conv_patch_x6_pack_kernel(const float* __restrict__ w, u16* __re
 }
 
 bool px6_enabled() {
-    static const bool on = [] {
-        const char* a = getenv("GSSD_PATCH_X6");
-        const char* b = getenv("GSSD_X6_F16");
-        return !(a && a[0] == '0') && !(b && b[0] == '0');
-    }();
+    static const bool on = !gssd_env_off("GSSD_PATCH_X6") && gssd_x6_f16_enabled();
     return on;
 }
 
@@ -264,13 +241,7 @@ int gssd_try_conv_patch_x6(const gssd_conv_desc& d, hipStream_t stream) {
     p.relu = d.relu;
     static unsigned attr_mask = 0;
     auto kern = conv_patch_x6_kernel;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", LDS_BYTES);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, LDS_BYTES)) return rc;
     const int ntiles = p.B * p.tiles_y * p.tiles_x;
     const int per = (ntiles + 7) / 8;
     hipLaunchKernelGGL(kern, dim3(per * 8), dim3(NTHR), LDS_BYTES, stream, p);

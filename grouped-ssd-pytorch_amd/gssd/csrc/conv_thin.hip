@@ -19,17 +19,11 @@
 // to accumulation-order rounding.  Reference call sites: models/ssd_multiphase_custom_group.py:444.
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
 __device__ __attribute__((aligned(16))) float g_zero_page_thin[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct ThinParams {
     const float* in;
@@ -325,14 +319,7 @@ int launch_thin_impl(const gssd_conv_desc& d, hipStream_t stream) {
     const size_t smem = work + 2 * COUT * sizeof(double);
     auto kern = conv_thin_kernel<CIN_G, COUT_G, FIXED, XF>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                96 * 1024) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (thin conv)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, 96 * 1024)) return rc;
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     const int per_cu = smem > 60 * 1024 ? 2 : 3;
     int grid = 256 * per_cu;
@@ -365,7 +352,7 @@ int gssd_try_conv_thin(const gssd_conv_desc& d, hipStream_t stream) {
     if (d.cin_g == 16 && cout_g == 16) return launch_thin<16, 16>(d, stream);
     // conv2_1 with Winograd weights goes to conv_wino<32> (round 4: this direct kernel is pipe-bound -- fp32 MFMA + VALU 93 % busy -- at
     // 2.25 x the MACs of the Winograd form: 300 -> 262 us at B = 32); GSSD_CONV21_WINO=0 keeps it here
-    static const bool c21_wino = []() { const char* e = getenv("GSSD_CONV21_WINO"); return !(e && e[0] == '0'); }();
+    static const bool c21_wino = !gssd_env_off("GSSD_CONV21_WINO");
     if (d.cin_g == 16 && cout_g == 32) return (c21_wino && d.wgt_wino) ? 1 : launch_thin<16, 32>(d, stream);
     return 1;
 }

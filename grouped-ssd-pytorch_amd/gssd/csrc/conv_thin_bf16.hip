@@ -46,11 +46,7 @@
 // 217 / 192 us -- its 2 x 11 registers cost more (three workgroups per CU leave 170 VGPRs) than the ~300 VALU instructions per tile save.
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 #ifdef THIN_TIMING
 __device__ unsigned long long g_thin_timing[8];
@@ -75,11 +71,6 @@ namespace {
 
 __device__ __attribute__((aligned(16))) u16 g_zero_thin_h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 struct ThinBfParams {
     const u16* in;
     const u16* wgt;      // packed bf16 [Cout][9*CIN_G]
@@ -94,7 +85,7 @@ struct ThinBfParams {
 };
 
 template <int UPR>
-__device__ __forceinline__ int swz(int col) {
+__device__ __forceinline__ int swz_col(int col) {
     return UPR >= 8 ? (col & (UPR - 1)) & 15 : ((col ^ (col >> 2)) & (UPR - 1));
 }
 
@@ -165,7 +156,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
         if (dx > 2) dx = 2;
         const int col = r + dx;
         const int unit = (g * CIN_G + coff) >> 3;
-        foff[kk] = col * CIN + ((unit ^ swz<UPR>(col)) << 3);
+        foff[kk] = col * CIN + ((unit ^ swz_col<UPR>(col)) << 3);
     }
 
     float ssum[CPL], ssq[CPL];
@@ -194,7 +185,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
         for (int i = g; i < NINSTR; i += 4) {
             const int pp = i * PPI + lane / UPR;
             const int py = pp / PW, pxx = pp - py * PW;
-            const int lu = (THIN_KO & 128) ? (lane % UPR) : (lane % UPR) ^ swz<UPR>(pxx);
+            const int lu = (THIN_KO & 128) ? (lane % UPR) : (lane % UPR) ^ swz_col<UPR>(pxx);
             const int iy = y0 - 1 + py, ix = x0 - 1 + pxx;
             const bool ok = pp < NPATCH && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
             const u16* src = ok ? p.in + ((size_t)(b * p.H + iy) * p.W + ix) * CIN + lu * 8 : g_zero_thin_h;
@@ -217,21 +208,17 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
             for (; pp < NPATCH; pp += STEP) {
                 const int iy = y0 - 1 + py, ix = x0 - 1 + pxx;
                 if (inside || ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W)) {
-                    u16* at = patch + (pp * UPR + ((tid % UPR) ^ swz<UPR>(pxx))) * 8;
-                    typedef unsigned u32x4t __attribute__((ext_vector_type(4)));
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    typedef short s16x2 __attribute__((ext_vector_type(2)));
-                    u32x4t v = *reinterpret_cast<const u32x4t*>(at);
+                    u16* at = patch + (pp * UPR + ((tid % UPR) ^ swz_col<UPR>(pxx))) * 8;
+                    u32x4 v = *reinterpret_cast<const u32x4*>(at);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         f32x2 x = {__builtin_bit_cast(float, v[e] << 16), __builtin_bit_cast(float, v[e] & 0xffff0000u)};
                         x = __builtin_elementwise_fma(x, f32x2{xs[2 * e], xs[2 * e + 1]}, f32x2{xh[2 * e], xh[2 * e + 1]});
-                        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                         const bf16x2 h = {(__bf16)x[0], (__bf16)x[1]};
                         const s16x2 z = __builtin_elementwise_max(__builtin_bit_cast(s16x2, h), s16x2{0, 0});
                         v[e] = __builtin_bit_cast(unsigned, z);
                     }
-                    *reinterpret_cast<u32x4t*>(at) = v;
+                    *reinterpret_cast<u32x4*>(at) = v;
                 }
                 py += SY;
                 pxx += SX;
@@ -453,7 +440,6 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
                     }
                     const int y = y0 + rb + i + (kq & 1);
                     if (y < p.H && x < p.W) {
-                        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                         u16* dst = p.out + ((size_t)(b * p.H + y) * p.W + x) * COUT + g * COUT_G + 4 * (kq & ~1);
                         if (!(THIN_KO & 16)) *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
                     }

@@ -6,17 +6,11 @@
 // lifetime of the persistent workgroup and is flushed with fp32 atomics once at the end.
 // MFMA: D[co][ci] += sum over 4 pixels dY[px][co] * X[px + tap][ci]  (v_mfma_f32_16x16x4_f32, k = 4 pixels).
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
 __device__ __attribute__((aligned(16))) float g_zero_page_tw[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct ThinWgradParams {
     const float* in;
@@ -165,14 +159,7 @@ int launch_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipSt
     const size_t smem = ((size_t)((180 + PPI - 1) / PPI) * PPI * CIN + 128 * 64) * sizeof(float);
     auto kern = conv_thin_wgrad_kernel<CIN_G, XF>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                96 * 1024) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (thin wgrad)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, 96 * 1024)) return rc;
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     int grid = 512;
     if (ntiles < grid) grid = (int)ntiles;

@@ -11,17 +11,11 @@
 // than the direct form; the layer becomes HBM-bound (1.47 GB in + out per launch).  The epilogue is conv_thin.hip's: output
 // transform in registers, transpose through LDS, whole-row NHWC stores, fp64 batch sums per workgroup.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
 __device__ __attribute__((aligned(16))) float g_zero_page_tw2[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct ThinWinoParams {
     const float* in;
@@ -270,14 +264,7 @@ int launch_thin_wino(const gssd_conv_desc& d, hipStream_t stream) {
     constexpr size_t smem = ((size_t)TW_PATCH_F + TW_STAGE_F) * sizeof(float) + 2 * TW_COUT * sizeof(double);
     auto kern = conv_thin_wino_kernel<XF>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-            hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (thin winograd)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     int grid = 512;                                       // two resident workgroups per CU (80 KB of LDS, <= 256 VGPRs each)
     if (ntiles < grid) grid = (int)ntiles;

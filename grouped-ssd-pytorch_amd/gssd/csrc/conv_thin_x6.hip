@@ -28,15 +28,7 @@
 #include <atomic>
 #include <mutex>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 #ifndef TX6_FENCE
 #define TX6_FENCE 1
@@ -74,7 +66,7 @@ constexpr int slab_channels(int cin_g, int cout_g) { return (cin_g == 16 && cout
 // 128-byte pixels: col & 7 (conv_thin_bf16.hip's); 64-byte pixels: bit 2 of the column into bit 1 of the unit.  [(col >> 1) & 7 and
 // (col >> 2) & 3, which are conflict-free for 16 CONSECUTIVE lanes, are 2-way conflicts for the real groups.]
 template <int UPS>
-__device__ __forceinline__ int swz(int col) { return UPS == 8 ? (col & 7) : ((col >> 1) & 2); }
+__device__ __forceinline__ int swz_col(int col) { return UPS == 8 ? (col & 7) : ((col >> 1) & 2); }
 
 struct ThinX6Params {
     const float* in;
@@ -91,29 +83,8 @@ struct ThinX6Params {
     int* ctr;                // [slabs][8 XCDs] tile counters, zero before the launch (NULL: static tile shares)
 };
 
-// the split of TWO values at once, planes as packed bf16 pairs (a in the low half): conv_x6.hip::split3_pair
-__device__ __forceinline__ void split3_pair(const float a, const float b, unsigned& ph, unsigned& pm, unsigned& pl) {
-    ph = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
-    const float ra = a - __builtin_bit_cast(float, ph << 16), rb = b - __builtin_bit_cast(float, ph & 0xffff0000u);
-    pm = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ra, rb}, bf16x2));
-    const float sa = ra - __builtin_bit_cast(float, pm << 16), sb = rb - __builtin_bit_cast(float, pm & 0xffff0000u);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{sa, sb}, bf16x2));
-}
-
-// F16 form (round 6; launches with the fused producer BatchNorm + ReLU, i.e. operands that are normalised activations): TWO fp16 planes per operand,
-// x = h + l' / 2048 with h = fp16(x), l' = fp16((x - h) * 2048) -- round to nearest twice, |x - h - l' / 2048| <= 2^-24 |x|: what fp32 itself keeps --
-// and THREE v_mfma_f32_16x16x32_f16 per product: h h' into one accumulator, h l' + l' h' into a second one that enters with the factor 1 / 2048 (the
-// l' l'' term is below 2^-24).  Half the matrix instructions and LDS fragment reads, a split of 3 instead of 5.5 vector instructions per value.
-// The residual is scaled because fp16 has no exponent range to spare (unscaled it would be a subnormal for |x| < 0.25); h overflows above 65 504,
-// which a BatchNorm + ReLU output does not reach; values below 6e-5 lose relative, not absolute, accuracy.  Accuracy against float64: that of an
-// fp32 FMA chain (4e-7 of the output scale; the three-plane bf16 form: 1.5e-7).  GSSD_X6_F16=0: the bf16 planes everywhere.
-__device__ __forceinline__ void split2_pair(const float a, const float b, unsigned& ph, unsigned& pl) {
-    const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
-    const f32x2 r = (f32x2{a, b} - __builtin_convertvector(h, f32x2)) * 2048.f;
-    ph = __builtin_bit_cast(unsigned, h);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-}
-
+// Operand planes (kernel_util.h): three bf16 planes (split3_pair) or, round 6, for launches with the fused producer BatchNorm + ReLU (operands that
+// are normalised activations), the two-plane fp16 form (split2_pair, where its derivation and valid range are).  GSSD_X6_F16=0: the bf16 planes everywhere.
 template <int CIN_G, int COUT_G, bool XF, bool POOL, bool F16>
 __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params p) {
     constexpr int NPL = F16 ? 2 : 3;
@@ -201,7 +172,7 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
         if (dx > 2) dx = 2;
         const int col = r + dx;
         const int un = (gi * CIN_G + coff) >> 3;
-        foff[kk] = col * CW + ((un ^ swz<UPS>(col)) << 3);
+        foff[kk] = col * CW + ((un ^ swz_col<UPS>(col)) << 3);
     }
 
     // ---- staging roles: thread -> (16-byte unit su of the slab, patch pixel sp + PPP it)
@@ -321,7 +292,7 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
 #pragma unroll
                 for (int e = 0; e < 4; ++e) split3_pair(v[2 * e], v[2 * e + 1], q[0][e], q[1][e], q[2][e]);
             }
-            const int at = ((sp + PPP * it) * UPS + (su ^ swz<UPS>(s_px[it]))) * 8;
+            const int at = ((sp + PPP * it) * UPS + (su ^ swz_col<UPS>(s_px[it]))) * 8;
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) *reinterpret_cast<u32x4*>(planes + pl * PLANE + at) = u32x4{q[pl][0], q[pl][1], q[pl][2], q[pl][3]};
         }
@@ -519,7 +490,7 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
 // launch outside a stream capture; a launch takes the next slot, and its last workgroup leaves the slot zeroed for the next user (a replayed graph
 // always finds its own slot at zero).  GSSD_TX6_DYNAMIC=0, or no pool yet while capturing: NULL = static tile shares.
 int* tx6_counters(hipStream_t stream) {
-    static const bool off = [] { const char* e = getenv("GSSD_TX6_DYNAMIC"); return e && e[0] == '0'; }();
+    static const bool off = gssd_env_off("GSSD_TX6_DYNAMIC");
     if (off) return nullptr;
     constexpr int SLOTS = 1024;
     static int* pool[32] = {};
@@ -569,13 +540,7 @@ int launch_thin_x6_impl(const gssd_conv_desc& d, hipStream_t stream) {
     constexpr size_t smem = (size_t)NPL * NPAD * CW * sizeof(u16) + 2 * CW * sizeof(float) + 16;
     auto kern = conv_thin_x6_kernel<CIN_G, COUT_G, XF, POOL, F16>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (thin x6 conv)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     constexpr int NGI = 4 / (CW / CIN_G);
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     long long grid = 512;                                 // two workgroups per CU
@@ -590,8 +555,7 @@ int launch_thin_x6_impl(const gssd_conv_desc& d, hipStream_t stream) {
 // the two-plane fp16 form for launches the caller flags GSSD_CONV_F16_OK (operands inside fp16's range; never inferred from the descriptor); GSSD_X6_F16=0: bf16 planes everywhere
 template <int CIN_G, int COUT_G, bool XF, bool POOL>
 int launch_thin_x6(const gssd_conv_desc& d, hipStream_t stream) {
-    static const bool f16_off = [] { const char* e = getenv("GSSD_X6_F16"); return e && e[0] == '0'; }();
-    if (!f16_off && (d.flags & GSSD_CONV_F16_OK)) return launch_thin_x6_impl<CIN_G, COUT_G, XF, POOL, true>(d, stream);
+    if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) return launch_thin_x6_impl<CIN_G, COUT_G, XF, POOL, true>(d, stream);
     return launch_thin_x6_impl<CIN_G, COUT_G, XF, POOL, false>(d, stream);
 }
 
@@ -599,21 +563,14 @@ int launch_thin_x6(const gssd_conv_desc& d, hipStream_t stream) {
 
 // GSSD_THIN_X6=0: the round-5 kernels (conv_thin_wino.hip / conv_wino.hip / conv_thin.hip) keep these layers (ablation / A-B)
 static bool thin_x6_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("GSSD_THIN_X6");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = !gssd_env_off("GSSD_THIN_X6");
     return on;
 }
 
 // conv3_1 (32 -> 64 channels per group, 75 x 75; round 6, late): four waves = the group's four 16-channel output tiles; GSSD_THIN_X6_CONV31=0: conv_wino_x6
 // (fp16 planes only -- flagged launches: the three-plane bf16 instance of this shape spills)
 static bool thin_x6_conv31() {
-    static const bool on = [] {
-        const char* e = getenv("GSSD_THIN_X6_CONV31");
-        const char* f = getenv("GSSD_X6_F16");
-        return !(e && e[0] == '0') && !(f && f[0] == '0');
-    }();
+    static const bool on = !gssd_env_off("GSSD_THIN_X6_CONV31") && gssd_x6_f16_enabled();
     return on;
 }
 

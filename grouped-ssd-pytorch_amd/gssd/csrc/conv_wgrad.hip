@@ -15,19 +15,13 @@
 // train_lesion_multiphase_v2.py:247-248).
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
 constexpr int BP = 32;      // pixels per K-chunk
 
 __device__ __attribute__((aligned(16))) float g_zero_page_w[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct WgradParams {
     const float* in;       // forward input (NHWC), possibly raw with in_scale/in_shift/in_pad
@@ -246,14 +240,7 @@ int launch_wgrad(WgradParams& p, hipStream_t stream) {
     constexpr size_t smem = 2 * (size_t)BP * (BMW + BNW) * sizeof(float);
     auto kern = conv_wgrad_kernel<MT, WM, WN>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (wgrad)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     hipLaunchKernelGGL(kern, dim3(gx, (unsigned)tiles), dim3(256), smem, stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;

@@ -16,27 +16,13 @@
 // staged element in LDS (fp32 math, rounded to bf16 like the forward's staging does), not per fragment: beside bf16 MFMAs 24 VALU
 // instructions per fragment would cost more than the MFMAs they feed.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 namespace {
 
 constexpr int SCHED_EVERY = 4;         // entries between two scheduling barriers of the k-step (bounds the fragment reads in flight)
 
 __device__ __attribute__((aligned(16))) u16 g_zero_page_wb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ s16x4 tr_read(const u16* lds_ptr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)lds_ptr);
-}
 
 struct WgBfParams {
     const u16* in;
@@ -53,7 +39,7 @@ struct WgBfParams {
 
 // swizzle of the 32-byte chunk index by the pixel column: NC chunks per pixel
 template <int NC>
-__device__ __forceinline__ int swz(int col) {
+__device__ __forceinline__ int swz_col(int col) {
     if constexpr (NC >= 8) return col & 7;
     else if constexpr (NC == 4) return (col >> 1) & 3;
     else if constexpr (NC == 2) return (col >> 2) & 1;
@@ -115,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgBfParam
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int col = 8 * t + 4 * (kq & 1) + sj;
-        a_addr[t] = ((((kq >> 1) * TW + col) * NCD) * 16 + (swz<NCD>(col) << 4) + sq * 4) ^ (((gl * WCO + wc) * COB) << 4);
+        a_addr[t] = ((((kq >> 1) * TW + col) * NCD) * 16 + (swz_col<NCD>(col) << 4) + sq * 4) ^ (((gl * WCO + wc) * COB) << 4);
     }
     // B (patch): column 8 t + 4 (kq & 1) + sj + dx, row 2 s + (kq >> 1) + dy
     int b_addr[NDX][2];
@@ -124,7 +110,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgBfParam
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int col = 8 * t + 4 * (kq & 1) + sj + dx;
-            b_addr[dx][t] = ((((kq >> 1) * PW + col) * NC) * 16 + (swz<NC>(col) << 4) + sq * 4) ^ ((gl * NCI + we * CPW) << 4);
+            b_addr[dx][t] = ((((kq >> 1) * PW + col) * NC) * 16 + (swz_col<NC>(col) << 4) + sq * 4) ^ ((gl * NCI + we * CPW) << 4);
         }
 
     f32x4 acc[COB][EPW];
@@ -143,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgBfParam
             const int pp = i * PPI + lane / UP;
             const int py = pp / PW, pxx = pp - py * PW;
             const int u = lane % UP;
-            const int ch = (((u >> 1) ^ swz<NC>(pxx)) << 4) + ((u & 1) << 3);
+            const int ch = (((u >> 1) ^ swz_col<NC>(pxx)) << 4) + ((u & 1) << 3);
             const int iy = y0 - HALO + py, ix = x0 - HALO + pxx;
             const bool ok = pp < NPATCH && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
             const u16* src = ok ? in_g + ((size_t)(b * p.H + iy) * p.W + ix) * p.in_stride + ch : zero;
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgBfParam
         for (int i = wv; i < NDY; i += 4) {
             const int px = i * PDY + lane / UD;
             const int u = lane % UD;
-            const int chl = (((u >> 1) ^ swz<NCD>(px & 15)) << 4) + ((u & 1) << 3);      // channel inside the workgroup's NG * NCOW
+            const int chl = (((u >> 1) ^ swz_col<NCD>(px & 15)) << 4) + ((u & 1) << 3);      // channel inside the workgroup's NG * NCOW
             const int y = y0 + (px >> 4), x = x0 + (px & 15);
             const bool ok = y < p.H && x < p.W && (cs * NCOW + (NG > 1 ? 0 : chl)) < p.cout_g;
             const u16* src = ok ? dy_g + ((size_t)(b * p.H + y) * p.W + x) * p.Cout + chl : zero;
@@ -167,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgBfParam
                 const int py = pp / PW, pxx = pp - py * PW;
                 const int iy = y0 - HALO + py, ix = x0 - HALO + pxx;
                 if ((unsigned)iy >= (unsigned)p.H || (unsigned)ix >= (unsigned)p.W) continue;
-                const int ch = (((u >> 1) ^ swz<NC>(pxx)) << 4) + ((u & 1) << 3);
+                const int ch = (((u >> 1) ^ swz_col<NC>(pxx)) << 4) + ((u & 1) << 3);
                 uint4* q = reinterpret_cast<uint4*>(patch + pp * NC * 16 + u * 8);
                 uint4 v = *q;
                 unsigned w[4] = {v.x, v.y, v.z, v.w};
@@ -177,7 +163,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgBfParam
                 for (int e = 0; e < 4; ++e) {
                     const float lo = fmaxf(__uint_as_float(w[e] << 16) * sc[2 * e] + sh[2 * e], 0.f);
                     const float hi = fmaxf(__uint_as_float(w[e] & 0xffff0000u) * sc[2 * e + 1] + sh[2 * e + 1], 0.f);
-                    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                     bf16x2 h;
                     h[0] = (__bf16)lo;
                     h[1] = (__bf16)hi;
@@ -269,14 +254,7 @@ int launch_wgrad_bf16(const gssd_conv_desc& d, const void* dy, float* dw, hipStr
     const size_t smem = ((size_t)NPI * PPI * NC * 16 + 128 * NCD * 16) * sizeof(u16) + 2 * NG * CIN_G * sizeof(float);
     auto kern = conv_wgrad_bf16_kernel<CIN_G, NG, COB, WCO, WEN, XF, NTAP>;
     static unsigned attr_mask = 0;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) !=
-            hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (bf16 wgrad)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, 80 * 1024)) return rc;
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     const int gy = nblk / NG * p.co_splits;
     int gx = 512 / gy;                                    // two resident workgroups per CU

@@ -16,10 +16,8 @@
 // b128 trick of the wgrad kernel.  Accumulators: 16 xi x NB/16 tiles of 16x16 = 256 VGPRs for NB = 64 (one wave per SIMD;
 // the unified 512-entry register file of gfx950 is what makes this tiling possible).
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifdef WINO_TIMING
 // debug build (scripts/wino_timing.py): wave 0 of every workgroup accumulates the shader clocks between its phase boundaries
@@ -38,11 +36,6 @@ extern "C" int gssd_wino_timing_read(unsigned long long* out8) {
 namespace {
 
 __device__ __attribute__((aligned(16))) float g_zero_page_wino[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct WinoParams {
     const float* in;
@@ -525,14 +518,7 @@ int launch_wino(const gssd_conv_desc& d, hipStream_t stream) {
     }
     auto kern = conv_wino_kernel<NB, XF, PERSIST, EPI>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-            hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (winograd)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     const int nitems = (p.ntiles + 63) / 64;
     static int per_cu = 0;                                // resident workgroups per CU (registers / LDS decide: 1 or 2)
     if (!per_cu) {

@@ -25,13 +25,8 @@
 //   * per block two barriers: A -- the block's planes are in LDS and its U planes have landed; B -- the consumers hold the planes in registers,
 //     the producers may write the next block's.  U stages (4 xi x 3 planes x NB x 32 bf16) are double buffered.
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
 
 #ifndef WX6_KO
 #define WX6_KO 0              // knock-outs (scripts/wino_x6_knockout.sh; results wrong by construction): 1 no vector work (transform / split), 2 no MFMAs,
@@ -44,48 +39,13 @@ namespace {
 
 constexpr int NP = 3, XG = 4;
 
-__device__ __host__ __forceinline__ int swz(int row) { return (row & 8) ? 3 : 0; }       // 64-byte rows: conflict-free ds_read_b128 (conv_x6.hip)
-
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// the split of TWO values at once, planes as packed bf16 pairs (a in the low half): one v_cvt_pk_bf16_f32 per plane and pair (the element-wise
-// form costs one per element: the compiler does not pair the converts of two chains), and the packed result IS the operand dword
-__device__ __forceinline__ void split3_pair(const float a, const float b, unsigned& ph, unsigned& pm, unsigned& pl) {
-    ph = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
-    const float ra = a - __builtin_bit_cast(float, ph << 16), rb = b - __builtin_bit_cast(float, ph & 0xffff0000u);
-    pm = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ra, rb}, bf16x2));
-    const float sa = ra - __builtin_bit_cast(float, pm << 16), sb = rb - __builtin_bit_cast(float, pm & 0xffff0000u);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{sa, sb}, bf16x2));
-}
-
-// The two-plane fp16 form (round 6, conv_thin_x6.hip): x = h + l' / 2048, h = fp16(x), l' = fp16((x - h) * 2048) -- |x - h - l' / 2048| <= 2^-24 |x| --
-// and three v_mfma_f32_16x16x32_f16 per product (h h'; h l' + l' h' into a sum that enters with 1 / 2048).  For launches whose input is a BatchNorm +
-// ReLU output (the fused producer transform: the trunk's forward convs) or that the caller marks GSSD_CONV_F16_OK (bounded activations: the DCN
-// offset conv); data gradients keep the bf16 planes (fp16 has no exponent range for them).  GSSD_X6_F16=0: bf16 planes everywhere.
-__device__ __forceinline__ void split2_pair(const float a, const float b, unsigned& ph, unsigned& pl) {
-    const f16x2 h = __builtin_convertvector(f32x2{a, b}, f16x2);
-    const f32x2 r = (f32x2{a, b} - __builtin_convertvector(h, f32x2)) * 2048.f;
-    ph = __builtin_bit_cast(unsigned, h);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-}
-
+// Operand planes (kernel_util.h): three bf16 planes (split3_pair) or the two-plane fp16 form (split2_pair: three v_mfma_f32_16x16x32_f16 per product,
+// h h'; h l' + l' h' into a sum that enters with 1 / 2048) for launches whose input is a BatchNorm + ReLU output (the fused producer transform: the
+// trunk's forward convs) or that the caller marks GSSD_CONV_F16_OK (bounded activations: the DCN offset conv); data gradients keep the bf16 planes.
+// GSSD_X6_F16=0: bf16 planes everywhere.
 struct WinoX6Params {
     const float* in;
-    const u16* Ux;           // [groups][cout blocks][chunks][16 xi][3 planes][NB co][32 slots], slot groups swizzled (swz)
+    const u16* Ux;           // [groups][cout blocks][chunks][16 xi][3 planes][NB co][32 slots], slot groups swizzled (swz64)
     const float* bias;
     float* out;
     const float* resid;
@@ -348,7 +308,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
 #pragma unroll
         for (int nb = 0; nb < NBT; ++nb) ssum[nb] = ssq[nb] = zero4;
         const bool vec = ((p.out_stride | p.out_ch_off | p.cout_g) & 3) == 0 && p.vec_ok;
-        const int fo = r * 32 + ((kq ^ swz(r)) << 3);          // fragment offset inside a 16-row block of a tile
+        const int fo = r * 32 + ((kq ^ swz64(r)) << 3);          // fragment offset inside a 16-row block of a tile
         // U planes of (chunk c, Winograd row i) -> LDS slot: XG * NPX * TILE / 512 pieces of 1 KB, consumer wave w moves pieces w, w + 4, ..
         auto stage_U_part = [&](const int c, const int i, const int slot, const int part) {      // part of NBT (-1: all)
             if (WX6_KO & 4) return;
@@ -464,7 +424,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
 #pragma unroll
                     for (int nb = 0; nb < NBT; ++nb) Y[a][b2][nb] = zero4;
         };
-
 
         // the four xi of Winograd row I: 24 NBT MFMAs from the row's planes and LDS slot `slot`, folded into the 2 x 2 outputs right away
         // (Y = A^T M A is linear in M: Y[a][b] += A[I][a] (M_I. A)[b]; A^T = [1 1 1 0; 0 1 -1 -1])
@@ -658,9 +617,9 @@ __global__ void wino_x6_weight_kernel(const float* __restrict__ w, u16* __restri
     const int cb = cg / NB, row = cg % NB;
     const int c = ci / 32, wi = ci % 32;
     const int sub = wi >> 4, kq = (wi & 15) >> 2, e = wi & 3;
-    const size_t base = ((size_t)(g * ncb + cb) * nchunks + c) * CHUNK + row * 32 + ((kq ^ swz(row & 15)) << 3) + 4 * sub + e;
+    const size_t base = ((size_t)(g * ncb + cb) * nchunks + c) * CHUNK + row * 32 + ((kq ^ swz64(row & 15)) << 3) + 4 * sub + e;
     const size_t f16_base = (size_t)groups * ncb * nchunks * CHUNK;          // behind the bf16 planes
-    const size_t base16 = ((size_t)(g * ncb + cb) * nchunks + c) * (16 * 2 * TILE) + row * 32 + ((kq ^ swz(row & 15)) << 3) + 4 * sub + e;
+    const size_t base16 = ((size_t)(g * ncb + cb) * nchunks + c) * (16 * 2 * TILE) + row * 32 + ((kq ^ swz64(row & 15)) << 3) + 4 * sub + e;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {                         // (G g) G^T
         const float u[4] = {t[a][0], 0.5f * (t[a][0] + t[a][1] + t[a][2]), 0.5f * (t[a][0] - t[a][1] + t[a][2]), t[a][2]};
@@ -726,13 +685,7 @@ int launch_wino_x6_impl(const gssd_conv_desc& d, const u16* Ux, hipStream_t stre
     constexpr size_t smem = (2 * (size_t)XG * NPX * NB * 32 + 4 * (size_t)XG * NPX * 512) * sizeof(u16);      // two U stages + the planes of a block
     auto kern = conv_wino_x6_kernel<NBT, XF, EPI, PSEL, F16>;
     static unsigned attr_mask = 0;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (winograd x6)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     const int nitems = (p.ntiles + 63) / 64;
     int gx = 256 / p.npairs;                              // one workgroup per CU
     if (gx < 1) gx = 1;
@@ -746,9 +699,8 @@ int launch_wino_x6_impl(const gssd_conv_desc& d, const u16* Ux, hipStream_t stre
 // the two-plane fp16 form: launches marked GSSD_CONV_F16_OK by the caller (operands inside fp16's range; never inferred); never a data gradient (EPI 1)
 template <int NBT, bool XF, int EPI, bool PSEL>
 int launch_wino_x6_sel(const gssd_conv_desc& d, const u16* Ux, hipStream_t stream) {
-    static const bool f16_off = [] { const char* e = getenv("GSSD_X6_F16"); return e && e[0] == '0'; }();
     if constexpr (EPI != 1) {
-        if (!f16_off && (d.flags & GSSD_CONV_F16_OK)) {
+        if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) {
             const int cout_g = d.Cout / d.groups;
             const long long nb = cout_g > 32 ? 64 : 32, ncb = (cout_g + nb - 1) / nb, nchunks = (d.cin_g + 31) / 32;
             return launch_wino_x6_impl<NBT, XF, EPI, PSEL, true>(d, Ux + (long long)d.groups * ncb * nchunks * 16 * NP * nb * 32, stream);

@@ -17,10 +17,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 namespace {
 
@@ -39,51 +36,10 @@ constexpr int BM = 128, BKC = 32;
 constexpr int NP = 3;
 constexpr int A_STAGE = BM * BKC;                     // u16 elements per plane
 
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __host__ __forceinline__ int swz(int row) { return (row & 8) ? 3 : 0; }       // 64-byte rows: conflict-free ds_read_b128
-
-__device__ __host__ __forceinline__ int chan_of_row(int row) {        // LDS row of the weight tile -> output channel inside the BN tile
-    const int j = row >> 4, rho = row & 15;
-    return 32 * (j >> 1) + 8 * (rho >> 2) + 4 * (j & 1) + (rho & 3);
-}
-
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// the same split of TWO values at once, planes as packed bf16 pairs (a in the low half): one v_cvt_pk_bf16_f32 per plane and pair
-__device__ __forceinline__ void split3_pair(const float a, const float b, unsigned& ph, unsigned& pm, unsigned& pl) {
-    ph = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
-    const float ra = a - __builtin_bit_cast(float, ph << 16), rb = b - __builtin_bit_cast(float, ph & 0xffff0000u);
-    pm = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ra, rb}, bf16x2));
-    const float sa = ra - __builtin_bit_cast(float, pm << 16), sb = rb - __builtin_bit_cast(float, pm & 0xffff0000u);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{sa, sb}, bf16x2));
-}
-
-// Round 6, the three-MFMA form for FORWARD launches on bounded activations (GSSD_CONV_F16_OK set by the
-// caller): three fp16 planes per operand -- h = fp16(x), h6 = h / 64, l6 = fp16((x - h) * 64), x = h + l6 / 64 to 2^-24 |x| -- and the products
-// h h' + l6 h6' + h6 l6' (dcn_x6.hip).  Same planes, LDS images and DMA pieces as the bf16 form, half the matrix instructions.  The packed weights
-// hold both forms (the bf16 planes, then the fp16 planes); data gradients keep the bf16 planes.  GSSD_X6_F16=0: bf16 everywhere.
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void split3h_pair(const float a, const float b, unsigned& ph, unsigned& p6, unsigned& pl) {
-    const f16x2_t h = __builtin_convertvector(f32x2{a, b}, f16x2_t);
-    const f32x2 r = (f32x2{a, b} - __builtin_convertvector(h, f32x2)) * 64.f;
-    ph = __builtin_bit_cast(unsigned, h);
-    p6 = __builtin_bit_cast(unsigned, h * f16x2_t{(_Float16)0.015625f, (_Float16)0.015625f});
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2_t));
-}
+// Round 6, the three-MFMA form for FORWARD launches on bounded activations (GSSD_CONV_F16_OK set by the caller): three fp16 planes per operand and
+// the products h h' + l6 h6' + h6 l6' (kernel_util.h: split3h_pair).  Same planes, LDS images and DMA pieces as the bf16 form, half the matrix
+// instructions.  The packed weights hold both forms (the bf16 planes, then the fp16 planes); data gradients keep the bf16 planes.
+// GSSD_X6_F16=0: bf16 everywhere.
 
 #ifndef X6_V2
 #define X6_V2 1             // round 5's K loop for the 64- / 128-column tiles (conv_x6_v2_kernel); 0: round 4's (conv_x6_kernel, also the 256-column sweep instance)
@@ -139,8 +95,8 @@ __global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_c
 
     // gather roles: thread -> (pixel row gp + 64 j, 8-channel slot gq)
     const int gq = tid & 3, gp = tid >> 2;
-    const int a_wr0 = gp * BKC + ((gq ^ swz(gp)) << 3);
-    const int fo = r * BKC + ((kq ^ swz(r)) << 3);
+    const int a_wr0 = gp * BKC + ((gq ^ swz64(gp)) << 3);
+    const int fo = r * BKC + ((kq ^ swz64(r)) << 3);
     int g_iy0[2], g_ix0[2], g_off[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -153,7 +109,6 @@ __global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_c
         g_ix0[j] = ox * p.stride - p.pad;
         g_off[j] = ((b * p.H + oy * p.stride - p.pad) * p.W + g_ix0[j]) * p.in_stride + gq * 8;
     }
-
 
     // ---- the K loop, one instruction stream per chunk ------------------------------------------------------------------------------
     // chunk ch: fragments of chunk ch -> registers; global loads of chunk ch + 2's activations (registers) and the LDS-DMA of chunk ch + 1's
@@ -210,7 +165,6 @@ __global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_c
         }
     };
     // quarter `part` (pixel j = part >> 1, channel half hh = part & 1) of this thread's 16 values: transform, split into the planes
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     auto finish_part = [&](int part, const f32x4 (&gv)[2][2], const bool (&gok)[2], int buf) {
         if (X6_KO & 1) return;
         const int j = part >> 1, hh = part & 1;
@@ -534,8 +488,8 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
 
     // gather roles: thread -> (pixel rows gp and gp + 64, 8-channel slot gq)
     const int gq = tid & 3, gp = tid >> 2;
-    const int a_wr0 = gp * BKC + ((gq ^ swz(gp)) << 3);
-    const int fo = r * BKC + ((kq ^ swz(r)) << 3);
+    const int a_wr0 = gp * BKC + ((gq ^ swz64(gp)) << 3);
+    const int fo = r * BKC + ((kq ^ swz64(r)) << 3);
     int g_iy0[2], g_ix0[2], g_off[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -640,9 +594,9 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
     // F16: LDS planes (h, l6) -> registers [0] and [2]; [1] = h / 64 (exact; where it leaves fp16's normal range the product it enters is below
     // 2^-24 of the leading one)
     auto derive = [&](bf16x8& h6, const bf16x8& h) {
-        const f16x8_t sc = {(_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f,
-                            (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f};
-        h6 = __builtin_bit_cast(bf16x8, __builtin_bit_cast(f16x8_t, h) * sc);
+        const f16x8 sc = {(_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f,
+                          (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f};
+        h6 = __builtin_bit_cast(bf16x8, __builtin_bit_cast(f16x8, h) * sc);
     };
     auto a_load_row = [&](int i) {
         const u16* Ab = As + (wm * WTM + i * 16) * BKC + fo;
@@ -698,9 +652,9 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
 #endif
         if constexpr (F16) {
             // planes 0: h, 1: h / 64, 2: (x - h) * 64 -- l6 h6', h6 l6', h h'
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, breg[which][2]), __builtin_bit_cast(f16x8_t, areg[i][1]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, breg[which][1]), __builtin_bit_cast(f16x8_t, areg[i][2]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, breg[which][0]), __builtin_bit_cast(f16x8_t, areg[i][0]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, breg[which][2]), __builtin_bit_cast(f16x8, areg[i][1]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, breg[which][1]), __builtin_bit_cast(f16x8, areg[i][2]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, breg[which][0]), __builtin_bit_cast(f16x8, areg[i][0]), c, 0, 0, 0);
         } else {
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(breg[which][1], areg[i][1], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(breg[which][2], areg[i][0], c, 0, 0, 0);
@@ -960,7 +914,7 @@ __global__ void conv_x6_pack_kernel(const float* __restrict__ w, u16* __restrict
         const int chunk = (int)(t % nchunks);
         t /= nchunks;
         const int nt = (int)(t % ntn), g = (int)(t / ntn);
-        const int q = slot ^ swz(row);
+        const int q = slot ^ swz64(row);
         const int tap = chunk % taps, c32 = chunk / taps;
         const int c = c32 * BKC + q * 8 + e;
         const int ng = nt * BN + chan_of_row(row);
@@ -982,13 +936,7 @@ template <int BN, bool XF>
 int launch(const gssd_conv_desc& d, int M, hipStream_t stream) {
     static unsigned attr_mask = 0;
     auto kern = conv_x6_kernel<BN, XF>;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<BN>::LDS_BYTES + 4096) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", Cfg<BN>::LDS_BYTES + 4096);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, Cfg<BN>::LDS_BYTES + 4096)) return rc;
     const int cout_g = d.Cout / d.groups;
     const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
     const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
@@ -1003,13 +951,7 @@ int launch2_impl(const gssd_conv_desc& d, int M, hipStream_t stream) {
     static unsigned attr_mask = 0;
     auto kern = conv_x6_v2_kernel<BN, XF, F16>;
     constexpr int lds = Cfg2<BN>::LDS_BYTES;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds + 4096) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", lds + 4096);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, lds + 4096)) return rc;
     const int cout_g = d.Cout / d.groups;
     const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
     const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
@@ -1020,8 +962,7 @@ int launch2_impl(const gssd_conv_desc& d, int M, hipStream_t stream) {
 // the three-MFMA fp16 form: only launches the CALLER flags GSSD_CONV_F16_OK (operands inside fp16's range: include/gssd_hip.h) -- never inferred
 template <int BN, bool XF>
 int launch2(const gssd_conv_desc& d, int M, hipStream_t stream) {
-    static const bool f16_off = [] { const char* e = getenv("GSSD_X6_F16"); return e && e[0] == '0'; }();
-    if (!f16_off && (d.flags & GSSD_CONV_F16_OK)) return launch2_impl<BN, XF, true>(d, M, stream);
+    if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) return launch2_impl<BN, XF, true>(d, M, stream);
     return launch2_impl<BN, XF, false>(d, M, stream);
 }
 #endif

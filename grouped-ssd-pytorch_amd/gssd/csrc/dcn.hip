@@ -6,12 +6,11 @@
 // access is a contiguous 16 B x 64 lane burst in NHWC.  The contraction with the weights is a plain
 // 1x1 implicit GEMM over the columns (conv_igemm.hip).
 #include "common.h"
+#include "kernel_util.h"
 
 #ifndef COL2IM_KO
 #define COL2IM_KO 0      // scripts/col2im_knockout.sh
 #endif
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -31,7 +30,6 @@ __device__ __forceinline__ f32x4 ld4c<unsigned short>(const unsigned short* p, i
 }
 __device__ __forceinline__ void st4c(float* p, int c, const f32x4 v) { reinterpret_cast<f32x4*>(p)[c] = v; }
 __device__ __forceinline__ void st4c(unsigned short* p, int c, const f32x4 v) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     reinterpret_cast<bf16x4*>(p)[c] = bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
 }
 
@@ -135,11 +133,6 @@ constexpr int DC_CHP = 20;                                            // ... pad
 
 __device__ __attribute__((aligned(16))) float g_zero16_dcn[4] = {0.f, 0.f, 0.f, 0.f};
 
-__device__ __forceinline__ void dma16_dcn(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
@@ -226,7 +219,7 @@ __global__ __launch_bounds__(192) void dcn_col2im_kernel(const float* __restrict
             const int h = ty * TH + pl / TW, w = tx * TW + pl % TW;
             const bool ok = u < DC_CH && h < H && w < W;
             const float* src = ok ? dcb + ((size_t)(h * W + w) * 9 + tap) * C + f4 : g_zero16_dcn;
-            dma16_dcn(src, buf + j * 256);
+            dma16(src, buf + j * 256);
         }
     };
     // ---- prologue: x window (both waves), first d(cols) chunk, accumulator clear, geometry table --------------------------------
@@ -236,7 +229,7 @@ __global__ __launch_bounds__(192) void dcn_col2im_kernel(const float* __restrict
             const int px = i * 4 + q4;
             const int y = wy0 + px / WW, xx = wx0 + px % WW;
             const bool ok = px < WPX && (unsigned)y < (unsigned)H && (unsigned)xx < (unsigned)W;
-            dma16_dcn(ok ? xb + (size_t)(y * W + xx) * C + f4 : g_zero16_dcn, xw + i * 256);
+            dma16(ok ? xb + (size_t)(y * W + xx) * C + f4 : g_zero16_dcn, xw + i * 256);
         }
     }
     if (wave == 0) stage_chunk(0, gb[0]);

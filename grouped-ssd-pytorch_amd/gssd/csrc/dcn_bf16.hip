@@ -10,10 +10,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 #ifndef X6_KO
 #define X6_KO 0        // knock-outs of the round-5 kernel (as csrc/dcn_x6.hip): 1 no blend, 2 no MFMAs, 4 no weight DMA, 8 no x loads, 16 no fragment reads, 32 no barrier
@@ -25,18 +22,6 @@ constexpr int BM = 128, BN = 256, BKC = 32;          // tile; channels (bf16) pe
 constexpr int WTM = 64, WTN = 128, MT = WTM / 16, NT = WTN / 16;
 constexpr int A_STAGE = BM * BKC, B_STAGE = BN * BKC;            // u16 elements
 constexpr int LDS_BYTES = 2 * (A_STAGE + B_STAGE) * 2 + 9 * BM * 16 + 9 * BM * 4;
-
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int swz(int row) { return (row & 8) ? 3 : 0; }       // 64-byte rows: conflict-free ds_read_b128
-
-__device__ __forceinline__ int chan_of_row(int row) {        // LDS row of the weight tile -> output channel inside the BN tile
-    const int j = row >> 4, rho = row & 15;
-    return 32 * (j >> 1) + 8 * (rho >> 2) + 4 * (j & 1) + (rho & 3);
-}
 
 // wp: [n_tiles][chunks][BN rows in staging order][32] bf16 (slot-swizzled), chunk = (d * cpg/32 + c32) * 9 + tap
 __global__ __launch_bounds__(256, 2) void dcn_bf16_kernel(const u16* __restrict__ x, const float* __restrict__ om,
@@ -80,8 +65,8 @@ __global__ __launch_bounds__(256, 2) void dcn_bf16_kernel(const u16* __restrict_
 
     // gather roles: thread -> (pixel row pl = (tid >> 2) + 64*j, 8-channel slot q = tid & 3)
     const int gq = tid & 3, gp = tid >> 2;
-    const int a_wr0 = gp * BKC + ((gq ^ swz(gp)) << 3);
-    const int fo = r * BKC + ((kq ^ swz(r)) << 3);
+    const int a_wr0 = gp * BKC + ((gq ^ swz64(gp)) << 3);
+    const int fo = r * BKC + ((kq ^ swz64(r)) << 3);
 
     auto setups = [&](int d) {
         for (int e = tid; e < 9 * BM; e += 256) {
@@ -312,7 +297,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
         // gather roles: thread -> (pixel rows gp (+ 64 with four loader waves), 8-channel slot gq)
         const int gq = lt & 3, gp = lt >> 2;
         constexpr int CSTEP = BM / NC;                       // row distance of a thread's cells
-        const int a_wr0 = gp * BKC + ((gq ^ swz(gp)) << 3);
+        const int a_wr0 = gp * BKC + ((gq ^ swz64(gp)) << 3);
         // sampling table of one deformable group (9 taps x BM rows)
         float t_dy[TPT], t_dx[TPT], t_ml[TPT];
         auto tab_load = [&](int d) {
@@ -533,7 +518,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
         // ================================================ the matrix side: eight waves ===================================================
         const int wm = wave >> 2, wn = wave & 3;
         const int r = lane & 15, kq = lane >> 4;
-        const int fo = r * BKC + ((kq ^ swz(r)) << 3);
+        const int fo = r * BKC + ((kq ^ swz64(r)) << 3);
         f32x4 acc[MT][NT];
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -658,7 +643,7 @@ __global__ void dcn_pack_weight_bf16_kernel(const float* __restrict__ w, u16* __
         const long long t = (i >> 5) / BN;
         const int chunk = (int)(t % nchunks);
         const int nt = (int)(t / nchunks);
-        const int q = slot ^ swz(row);
+        const int q = slot ^ swz64(row);
         const int tap = chunk % 9, cc = chunk / 9;
         const int c = cc * BKC + q * 8 + e;
         const int n = nt * BN + chan_of_row(row);
@@ -706,16 +691,7 @@ extern "C" int gssd_dcn_forward_bf16(const void* x, const float* om, const void*
     // corner wait -> blend -> addresses -> requests] is the bound, 510-560 of 850 ns; eight loader waves with one cell per thread instead of
     // four with two: the same 746 us -- the memory side alone takes 0.68 ms; scripts/dcn_bf16_ab.sh, scripts/dcn_bf16_timing.sh)
     static const bool use_v3 = getenv("GSSD_DCN_BF16_V3") && atoi(getenv("GSSD_DCN_BF16_V3")) == 1;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(dcn_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(v3::dcn_bf16_v3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                v3::LDS_BYTES) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", LDS_BYTES);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, dcn_bf16_kernel, LDS_BYTES, v3::dcn_bf16_v3_kernel, v3::LDS_BYTES)) return rc;
     int blocks;
     if (8 % ntn == 0) {
         const int per = 8 / ntn;

@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "kernel_util.h"
 
 #ifndef DCN_B_DMA
 #define DCN_B_DMA 1
@@ -40,8 +41,6 @@
 #define LD_EVERY 4
 #endif
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int BM = 128, BN = 256, BKC = 32;          // tile, channels per K chunk (one tap, 128 B per pixel)
@@ -49,21 +48,6 @@ constexpr int WTM = 64, WTN = 128, MT = WTM / 16, NT = WTN / 16;
 constexpr int A_STAGE = BM * BKC, B_STAGE = BN * BKC;            // floats
 constexpr int SET_FLOATS = 9 * BM * 8;                           // per (tap, pixel): 4 weights + 4 corner byte offsets
 constexpr int LDS_FLOATS = 2 * (A_STAGE + B_STAGE) + SET_FLOATS;
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 // wp: [n_tiles][chunks][BN][32] (slot-swizzled rows), chunk = (d * cpg/32 + c32) * 9 + tap
 //
@@ -652,16 +636,7 @@ extern "C" int gssd_dcn_forward_f32(const float* x, const float* om, const float
     int dev = 0;
     (void)hipGetDevice(&dev);
     constexpr int smem = LDS_FLOATS * (int)sizeof(float);
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(dcn_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dcn_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem) !=
-                hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", smem);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, dcn_fused_kernel<false>, smem, dcn_fused_kernel<true>, smem)) return rc;
     // grid: ids round-robin over the 8 XCDs; slots cover ceil(mtiles / (8 / ntn)) groups when ntn divides 8
     int blocks;
     if (8 % ntn == 0) {
@@ -673,7 +648,7 @@ extern "C" int gssd_dcn_forward_f32(const float* x, const float* om, const float
     // Stream-K form (one persistent workgroup per CU, equal spans of the (tile, chunk) space): taken when every XCD has at least as
     // many tiles as workgroups (a tile then straddles at most one span boundary) and the tile count does not already fill whole rounds.
     // GSSD_DCN_STREAMK=0 keeps one tile per workgroup.  Per-device state (placement probe, flag pool, error word): SkDev above.
-    static const bool sk_off = []() { const char* e = getenv("GSSD_DCN_STREAMK"); return e && e[0] == '0'; }();
+    static const bool sk_off = gssd_env_off("GSSD_DCN_STREAMK");
     bool sk = (g_dcn_sk_force < 0 ? !sk_off : g_dcn_sk_force == 1) && dev >= 0 && dev < 16;
     if (sk) {
         std::lock_guard<std::mutex> sk_lock(g_sk_mu);

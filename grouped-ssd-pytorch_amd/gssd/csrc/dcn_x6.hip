@@ -29,11 +29,8 @@
 // 1.76 ms per launch at the GSSD++ shape (2.12 in round 4); what bounds it now: memory side alone 1.33 ms, MFMAs alone 1.08 ms, together
 // 1.76 (the two sides share LDS and the issue ports; scripts/dcn_x6_knockout.sh, scripts/dcn_x6_timing.sh).
 #include "common.h"
+#include "kernel_util.h"
 #include <type_traits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 #ifndef X6_KO
 #define X6_KO 0        // knock-outs (scripts/dcn_x6_knockout.sh): 1 no blend / split VALU, 2 no MFMAs, 4 no weight DMA, 8 no x loads, 16 no fragment reads,
@@ -49,55 +46,10 @@ constexpr int A_STAGE = BM * BKC, B_STAGE = BN * BKC;            // u16 elements
 #ifndef X6_DMA_AUX
 #define X6_DMA_AUX 0       // cache policy bits of the weight DMA (experiments: 2 = nt)
 #endif
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, X6_DMA_AUX);
-}
 
-__device__ __forceinline__ int swz(int row) { return (row & 8) ? 3 : 0; }       // 64-byte rows (a four-way swizzle (row >> 2) & 3 measured 1.5 % slower)
-
-__device__ __forceinline__ int chan_of_row(int row) {        // LDS row of the weight tile -> output channel inside the BN tile
-    const int j = row >> 4, rho = row & 15;
-    return 32 * (j >> 1) + 8 * (rho >> 2) + 4 * (j & 1) + (rho & 3);
-}
-
-// x = h + m + l, each bf16 (round to nearest even); exact to 2^-25 |x|
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// the same split of TWO values at once, planes as packed bf16 pairs (a in the low half): one v_cvt_pk_bf16_f32 per plane and PAIR, and the
-// packed result is the operand dword (the element-wise form converts every element alone and then once more to pack: 7 converts per pair)
-// Round 6, the three-MFMA form (conv_thin_x6.hip) for a kernel whose accumulator count leaves no room for a second set: THREE fp16 planes per
-// operand -- h = fp16(x), h6 = h / 64 (exact), l6 = fp16((x - h) * 64): x = h + l6 / 64 to 2^-24 |x| -- and the three products
-// h h' + l6 h6' + h6 l6' into ONE accumulator (the scale 2^6 sits half on either operand of the two cross terms, so that neither a residual nor a
-// down-scaled leading plane leaves fp16's normal range for operands between 4e-3 and 1e3; below that the ABSOLUTE error stays under 5e-10).
-// Same planes, same LDS images, same DMA pieces as the bf16 form; half the matrix instructions.  GSSD_X6_F16=0: the bf16 planes.
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void split3h_pair(const float a, const float b, unsigned& ph, unsigned& p6, unsigned& pl) {
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f16x2_t h = __builtin_convertvector(f32x2_t{a, b}, f16x2_t);
-    const f32x2_t r = (f32x2_t{a, b} - __builtin_convertvector(h, f32x2_t)) * 64.f;
-    ph = __builtin_bit_cast(unsigned, h);
-    p6 = __builtin_bit_cast(unsigned, h * f16x2_t{(_Float16)0.015625f, (_Float16)0.015625f});
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2_t));
-}
-
-__device__ __forceinline__ void split3_pair(const float a, const float b, unsigned& ph, unsigned& pm, unsigned& pl) {
-    ph = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
-    const float ra = a - __builtin_bit_cast(float, ph << 16), rb = b - __builtin_bit_cast(float, ph & 0xffff0000u);
-    pm = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ra, rb}, bf16x2));
-    const float sa = ra - __builtin_bit_cast(float, pm << 16), sb = rb - __builtin_bit_cast(float, pm & 0xffff0000u);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{sa, sb}, bf16x2));
-}
+// Operand planes (kernel_util.h): three bf16 planes (split3_pair, six MFMAs per product) or, round 6, the three-fp16-plane form (split3h_pair,
+// three MFMAs into ONE accumulator: this kernel's accumulator count leaves no room for the second set the two-plane form needs).  Same planes,
+// same LDS images, same DMA pieces in both forms.  GSSD_X6_F16=0: the bf16 planes.
 
 // wp: [3 planes][n_tiles][chunks][BN rows in staging order][32] bf16 (slot-swizzled), chunk = (d * cpg / 32 + c32) * 9 + tap
 #ifndef X6_MW
@@ -187,7 +139,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         __builtin_amdgcn_s_setprio(X6_LPRIO);                // the youngest waves of the SIMD would otherwise issue last
         // gather roles: thread -> (pixel rows gp and gp + 64, 8-channel slot gq)
         const int gq = lt & 3, gp = lt >> 2;
-        const int a_wr0 = gp * BKC + ((gq ^ swz(gp)) << 3);
+        const int a_wr0 = gp * BKC + ((gq ^ swz64(gp)) << 3);
         // sampling table of one deformable group (9 taps x BM rows)
         float t_dy[TPT], t_dx[TPT], t_ml[TPT];
         auto tab_load = [&](int d) {
@@ -359,7 +311,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
                 const int p = q * LW + lwave;                // piece 0..23
                 const int pl = p >> 3, g8 = p & 7;
                 const int G = (g8 / NTH) * NT + half * NTH + (g8 % NTH);   // 16-row group of the plane's [BN][32] tile
-                dma16(src + (size_t)pl * plane_elems + G * 512, dst + pl * HB_PLANE + g8 * 512);
+                dma16<X6_DMA_AUX>(src + (size_t)pl * plane_elems + G * 512, dst + pl * HB_PLANE + g8 * 512);
             }
         };
         constexpr int ND = (X6_KO & 4) ? 0 : DPH, NL = (X6_KO & 8) ? 0 : 16;
@@ -432,7 +384,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         // ================================================ the matrix side: eight waves ===================================================
         const int wm = wave / WCOLS, wn = wave % WCOLS;
         const int r = lane & 15, kq = lane >> 4;
-        const int fo = r * BKC + ((kq ^ swz(r)) << 3);
+        const int fo = r * BKC + ((kq ^ swz64(r)) << 3);
         f32x4 acc[MT][NT];
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -442,9 +394,9 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         // F16: LDS planes (h, l6) -> registers [0] and [2]; [1] = h / 64 (exact: a power of two; below fp16's normal range the product it enters
         // is below 2^-24 of the leading one anyway)
         auto derive = [&](bf16x8& h6, const bf16x8& h) {
-            const f16x8_t s = {(_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f,
-                               (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f};
-            h6 = __builtin_bit_cast(bf16x8, __builtin_bit_cast(f16x8_t, h) * s);
+            const f16x8 s = {(_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f,
+                             (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f, (_Float16)0.015625f};
+            h6 = __builtin_bit_cast(bf16x8, __builtin_bit_cast(f16x8, h) * s);
         };
         auto a_load_row = [&](int i) {
             const u16* Ab = As + (wm * WTM + i * 16) * BKC + fo;
@@ -490,9 +442,9 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
             f32x4 c = acc[i][j];
             if constexpr (F16) {
                 // planes 0: h, 1: h / 64, 2: (x - h) * 64 -- l6 h6', h6 l6', h h'
-                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, breg[which][2]), __builtin_bit_cast(f16x8_t, areg[i][1]), c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, breg[which][1]), __builtin_bit_cast(f16x8_t, areg[i][2]), c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, breg[which][0]), __builtin_bit_cast(f16x8_t, areg[i][0]), c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, breg[which][2]), __builtin_bit_cast(f16x8, areg[i][1]), c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, breg[which][1]), __builtin_bit_cast(f16x8, areg[i][2]), c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, breg[which][0]), __builtin_bit_cast(f16x8, areg[i][0]), c, 0, 0, 0);
             } else {
                 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(breg[which][1], areg[i][1], c, 0, 0, 0);
                 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(breg[which][2], areg[i][0], c, 0, 0, 0);
@@ -604,7 +556,7 @@ __global__ void dcn_pack_weight_x6_kernel(const float* __restrict__ w, u16* __re
         const long long t = (i >> 5) / BN;
         const int chunk = (int)(t % nchunks);
         const int nt = (int)(t / nchunks);
-        const int q = slot ^ swz(row);
+        const int q = slot ^ swz64(row);
         const int tap = chunk % 9, cc = chunk / 9;                                // chunk = ((group * cpc + channel block) * 9 + tap)
         const int c = cc * BKC + q * 8 + e;
         const int n = nt * BN + chan_of_row(row);
@@ -633,12 +585,6 @@ extern "C" int gssd_dcn_x6_timing_read(unsigned long long* out8) {       // debu
 }
 #endif
 
-// GSSD_X6_F16=0: bf16 planes and six MFMAs per product; read once -- the packed weights and the kernel instance have to agree
-static bool dcn_x6_f16() {
-    static const bool on = [] { const char* e = getenv("GSSD_X6_F16"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 extern "C" long long gssd_dcn_packed_weight_elems_x6(int Cout, int C) {          // 16-bit elements: three bf16 planes, then two fp16 planes
     if (Cout <= 0 || C <= 0 || C % BKC != 0) return -1;
     return 5ll * ((Cout + BN - 1) / BN) * BN * 9 * C;
@@ -657,7 +603,8 @@ extern "C" int gssd_dcn_pack_weight_x6(const float* w_oihw, void* w_packed, int 
 // caller's promise, e.g. activations behind a train-mode BatchNorm: three fp16 MFMAs per product instead of six bf16 ones.  Never inferred.
 extern "C" int gssd_dcn_forward_x6_ex(const float* x, const float* om, const void* w_packed, const float* bias, float* out, int B, int H,
                                       int W, int C, int dg, int om_stride, int Cout, int flags, gssd_stream_t stream) {
-    const bool f16 = dcn_x6_f16() && (flags & GSSD_CONV_F16_OK);
+    // GSSD_X6_F16=0: bf16 planes and six MFMAs per product; read once -- the packed weights and the kernel instance have to agree
+    const bool f16 = gssd_x6_f16_enabled() && (flags & GSSD_CONV_F16_OK);
     GSSD_CHECK_ARG(x && om && w_packed && out && B > 0 && H > 0 && W > 0 && C > 0 && dg > 0 && Cout > 0 && Cout % 8 == 0);
     GSSD_CHECK_ARG(C % dg == 0 && (C / dg) % BKC == 0 && om_stride >= 27 * dg);
     GSSD_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)w_packed % 16) == 0 && ((uintptr_t)out % 16) == 0);
@@ -670,7 +617,7 @@ extern "C" int gssd_dcn_forward_x6_ex(const float* x, const float* om, const voi
     // two parts per tile while ONE round of the CUs holds them all (GSSD_DCN_X6_SPLITK=0: one part).  Measured (scripts/bench_dcn_x6.py): batch 4,
     // 46 tiles: 0.79 -> 0.38 ms with four parts (not used: run-to-run bits); batch 32, 361 tiles = 1.41 rounds: two parts (2.82 rounds) are 5 % SLOWER, 1.82 against 1.72 ms --
     // the launch is bound by the request rate of the shared vector-memory / L2 path, not by the CUs of the half-empty second round.
-    static const bool no_split = [] { const char* e = getenv("GSSD_DCN_X6_SPLITK"); return e && e[0] == '0'; }();
+    static const bool no_split = gssd_env_off("GSSD_DCN_X6_SPLITK");
     int ksplit = 1;
     if (!no_split && X6_MAP) {
         int dev = 0, ncu = 256;
@@ -684,14 +631,7 @@ extern "C" int gssd_dcn_forward_x6_ex(const float* x, const float* om, const voi
     }
     const auto kernel = ksplit == 2 ? (f16 ? dcn_x6_kernel<true, 2> : dcn_x6_kernel<false, 2>) : (f16 ? dcn_x6_kernel<true, 1> : dcn_x6_kernel<false, 1>);
     const int ai = (f16 ? 1 : 0) + 2 * (ksplit - 1);
-    if (gssd_attr_needed(&attr_mask[ai])) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
-            hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", LDS_BYTES);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask[ai]);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask[ai], kernel, LDS_BYTES)) return rc;
     int blocks;
     if (X6_MAP) {
         blocks = (mtiles + 7) / 8 * 8 * ntn * ksplit;

@@ -2,8 +2,7 @@
 // BatchNorm(train|eval)+ReLU+max-pool, L2Norm, row softmax, slice_and_cat, spectral norm.
 // All are written for 16-byte coalesced NHWC access and 64-lane wave reductions.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
@@ -416,7 +415,6 @@ __global__ __launch_bounds__(256) void reduce_max_kernel(const float* __restrict
     __syncthreads();
     if (threadIdx.x == 0) out[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
-
 
 // Deterministic split-K for the multibox heads: slice k of a head wrote its partial sums to ws[k] (same layout as the output);
 // out[b][p][c] = sum over k < splits[p] of ws[k][b][p][c], in slice order -- no atomics, run-to-run identical bits.

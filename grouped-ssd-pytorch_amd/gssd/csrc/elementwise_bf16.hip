@@ -1,10 +1,7 @@
 // bf16-storage variants of the HBM-bound passes (BASELINE.json configs[4]): bf16 NHWC in and out, all arithmetic in fp32,
 // one rounding on store.  16-byte accesses = 8 channels per lane.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 namespace {
 
@@ -15,8 +12,6 @@ inline int ew_blocks(long long work_items, int per_block = EW_THREADS, int cap =
     if (b > cap) b = cap;
     return (int)b;
 }
-
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 
 // NCHW fp32 -> NHWC bf16 with each group's channels padded from cpg_in to a multiple of 8 (zeros): one 16-byte store per (pixel, group,
 // 8-channel piece) -- one piece for 4 and 2 groups (3 and 6 channels), two for the ungrouped 12-channel input

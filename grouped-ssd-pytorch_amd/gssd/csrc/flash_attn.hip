@@ -20,17 +20,11 @@
 // ds_read_b128 fragment read conflict free; two workgroups share a CU (80 KB of LDS each) and hide each other's staging.
 #include <math.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
 __device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // Stage a [ROWS][QR quads] tile: lane L of a 1-KiB piece lands at (row_in = L / QR, slot = L % QR) and fetches logical quad
 // slot ^ (row & SW).  row_ptr(row) -> global pointer of that row's first float or nullptr (zero row); quad_ok(quad) masks columns.
@@ -173,7 +167,6 @@ __global__ __launch_bounds__(256, (C2 > 256 ? 1 : 2)) void flash_attn_kernel(con
     if (lse != nullptr && q < N && kq == 0) lse[(size_t)b * N + q] = m_run + logf(l_run);
     if (q < N) {
         if (out_bf16) {             // bf16 storage mode (configs[4]): the o conv reads bf16
-            typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
             unsigned short* dst = reinterpret_cast<unsigned short*>(out) + ((size_t)b * N + q) * out_stride + 4 * kq;
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
@@ -194,20 +187,13 @@ int launch(const float* tp, const float* kp, const float* gT, float* out, int B,
     constexpr int smem = (BKV * D + C2 * BKV) * (int)sizeof(float);
     static unsigned attr_mask = 0;
     auto kern = flash_attn_kernel<D, C2, BKV>;
-    if (gssd_attr_needed(&attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", smem);
-            return GSSD_ELAUNCH;
-        }
-        gssd_attr_done(&attr_mask);
-    }
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     const int qtiles = (N + 63) / 64;
     hipLaunchKernelGGL(kern, dim3(B * qtiles), dim3(256), smem, stream, tp, kp, gT, out, N, Nk, Np, qtiles, d_real, kstride, out_bf16, lse,
                        out_stride, g_batch_rows);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
-
 
 // ---- bf16 storage mode (configs[4]): fp32 logits, bf16 values -------------------------------------------------------------
 // theta / phi stay fp32 (a logit of magnitude ~50 rounded to bf16 would move its probability by tens of percent) and S^T = K . Q^T
@@ -216,8 +202,6 @@ int launch(const float* tp, const float* kp, const float* gT, float* out, int B,
 // of one bf16 MFMA if that MFMA's k index is DEFINED as k = 8 kq + e  <->  key 32 t + 16 (e >> 2) + 4 kq + (e & 3); the producer
 // conv writes g^T with the keys of every 32-block in that order (GSSD_CONV_OUTB_BF16_PERM32), so a lane's 8 values of V are one
 // contiguous 16-byte ds_read_b128.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 template <int D, int C2, int BKV>
 __global__ __launch_bounds__(256, 2) void flash_attn_mixed_kernel(const float* __restrict__ tp, const u16* __restrict__ gT,
@@ -334,7 +318,6 @@ __global__ __launch_bounds__(256, 2) void flash_attn_mixed_kernel(const float* _
     const float inv = 1.f / l_run;
     if (lse != nullptr && q < N && kq == 0) lse[(size_t)b * N + q] = m_run + logf(l_run);       // for the training step's backward
     if (q < N) {
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
         u16* dst = out + ((size_t)b * N + q) * out_stride + 4 * kq;
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
@@ -350,12 +333,7 @@ int launch_mixed(const float* tp, const u16* gT, u16* out, int B, int N, int Np3
     constexpr int smem = BKV * D * (int)sizeof(float) + C2 * BKV * (int)sizeof(u16);
     static unsigned attr_mask = 0;
     auto kern = flash_attn_mixed_kernel<D, C2, BKV>;
-    if (gssd_attr_needed(&attr_mask) &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-        gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", smem);
-        return GSSD_ELAUNCH;
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     const int qtiles = (N + 63) / 64;
     hipLaunchKernelGGL(kern, dim3(B * qtiles), dim3(256), smem, stream, tp, gT, out, N, Np32, qtiles, lse, out_stride, g_batch_rows);
     GSSD_CHECK_LAUNCH();

@@ -16,30 +16,13 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 namespace {
 
 constexpr int NP = 3;
 
 __device__ __attribute__((aligned(16))) u16 g_zero16_x6[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
 
 // rows x cols fp32 (row stride ld_in) -> three bf16 planes [rows][cols_out] (plane stride `plane`); perm32: column c of the output holds input
 // column 32 t + perm(c % 32) (the key order of the value product); columns >= cols are zero.  One thread = 8 output columns = 16 bytes per plane.
@@ -226,10 +209,7 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_x6_kernel(const u16* __
         bf16x8 pb[KB][NPX];
         if constexpr (F16) {
             // the probabilities go through the matrix cores scaled by 1024 (undone with the row sum at the end): fp16 keeps 11 bits only down to
-            // 6e-5, and a softmax over 1 444 keys has many smaller terms.  Pairs at a time, planes as packed dwords (conv_thin_x6.hip::split2_pair)
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+            // 6e-5, and a softmax over 1 444 keys has many smaller terms.  Pairs at a time, planes as packed dwords
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) {
                 u32x4 ph, pl;
@@ -239,10 +219,10 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_x6_kernel(const u16* __
                     psum += p0;
                     psum += p1;
                     const f32x2 ps = f32x2{p0, p1} * 1024.f;
-                    const f16x2 h = __builtin_convertvector(ps, f16x2);
-                    const f32x2 rr = (ps - __builtin_convertvector(h, f32x2)) * 2048.f;
-                    ph[e2] = __builtin_bit_cast(unsigned, h);
-                    pl[e2] = __builtin_bit_cast(unsigned, __builtin_convertvector(rr, f16x2));
+                    unsigned h, l;
+                    split2_pair(ps[0], ps[1], h, l);
+                    ph[e2] = h;
+                    pl[e2] = l;
                 }
                 pb[kb][0] = __builtin_bit_cast(bf16x8, ph);
                 pb[kb][1] = __builtin_bit_cast(bf16x8, pl);
@@ -321,12 +301,7 @@ int launch_x6(const u16* tpp, const u16* gp, float* out, int B, int N, int Np32,
     constexpr int smem = 2 * (F16 ? 2 : 3) * (BKV * D + C2 * BKV) * (int)sizeof(u16);      // two stages
     static unsigned attr_mask = 0;
     auto kern = flash_attn_x6_kernel<D, C2, BKV, NW, F16>;
-    if (gssd_attr_needed(&attr_mask) &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-        gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", smem);
-        return GSSD_ELAUNCH;
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     const int qtiles = (N + 16 * NW - 1) / (16 * NW);
     hipLaunchKernelGGL(kern, dim3(B * qtiles), dim3(64 * NW), smem, stream, tpp, gp, out, N, Np32, qtiles, (long long)B * N * 2 * D,
                        (long long)B * C2 * Np32, lse);

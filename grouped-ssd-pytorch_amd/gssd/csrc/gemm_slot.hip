@@ -20,8 +20,7 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
@@ -33,19 +32,6 @@ constexpr int A_STAGE = BM * BK;
 #endif
 
 __device__ __attribute__((aligned(16))) float g_zero_gs[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 // BN = 256: one workgroup per CU (96 KB of LDS, 128 accumulator registers per lane);  BN = 128: two per CU (64 KB, 64 registers) --
 // the second one's MFMAs cover the first one's prologue / epilogue, which is what short reductions (K <= 512) and grids of about one
@@ -437,12 +423,7 @@ static int launch_slot(const gssd_conv_desc& d, hipStream_t stream) {
     const int ntn = (d.Cout + BN - 1) / BN, mtiles = (int)((M + BM - 1) / BM);
     static unsigned attr_mask = 0;
     constexpr int smem = 2 * (A_STAGE + BN * BK) * (int)sizeof(float);
-    if (gssd_attr_needed(&attr_mask) &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_slot_kernel<BN, SWAP>), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-        gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", smem);
-        return GSSD_ELAUNCH;
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, gemm_slot_kernel<BN, SWAP>, smem)) return rc;
     int blocks;
     if (8 % ntn == 0) {
         const int per = 8 / ntn;

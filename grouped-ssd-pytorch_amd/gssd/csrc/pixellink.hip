@@ -946,14 +946,7 @@ extern "C" int gssd_pixellink_decode_f32(const float* out1, const float* out2, i
     } else {
         const size_t smem = pl_decode_lds_bytes(H * W);
         static unsigned attr_mask = 0;
-        if (gssd_attr_needed(&attr_mask)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(pl_decode_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)pl_decode_lds_bytes(PL_MAXPIX_LDS)) != hipSuccess) {
-                gssd_set_error("hipFuncSetAttribute failed (pixellink decode)");
-                return GSSD_ELAUNCH;
-            }
-        }
-        gssd_attr_done(&attr_mask);
+            if (const int rc = gssd_max_dynamic_lds(&attr_mask, pl_decode_lds_kernel, pl_decode_lds_bytes(PL_MAXPIX_LDS))) return rc;
         hipLaunchKernelGGL(pl_decode_lds_kernel, dim3(B), dim3(1024), smem, as_stream(stream), out1, out2, labels, comps, ncomp, H, W,
                            pixel_thr, link_thr, max_comp);
     }

@@ -12,6 +12,12 @@ void gssd_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+// the library's one read of GSSD_X6_F16 (common.h)
+bool gssd_x6_f16_enabled() {
+    static const bool on = !gssd_env_off("GSSD_X6_F16");
+    return on;
+}
+
 extern "C" int gssd_abi_version(void) { return 8; }
 extern "C" int gssd_conv_desc_size(void) { return (int)sizeof(gssd_conv_desc); }
 extern "C" const char* gssd_last_error(void) { return g_err; }

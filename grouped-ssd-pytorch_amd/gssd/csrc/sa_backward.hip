@@ -13,8 +13,7 @@
 //   gssd_rowdot_f32           D_i = <d(ag)_i, ag_i> = rowsum(A o dA)
 // The forward is flash-style and keeps no attention map, only the rows' log-sum-exp; the backward re-materialises A per block.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 

@@ -16,24 +16,12 @@
 // two tiles are packed into one bf16 k = 32 operand, and X^T comes out of the natural LDS image through ds_read_b64_tr_b16 (the same
 // transpose-read scheme as csrc/conv_wgrad_bf16.hip).  Accumulators leave as 16-byte rows of the token-major [theta | phi | g] gradient.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
+#include "kernel_util.h"
 
 namespace {
 
 __device__ __attribute__((aligned(16))) unsigned g_zero_page_fb[4] = {0, 0, 0, 0};
 
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ s16x4 tr_read(const u16* lds_ptr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)lds_ptr);
-}
 __device__ __forceinline__ bf16x8 tr_pair(const u16* p0, const u16* p1) {
     const s16x4 lo = tr_read(p0), hi = tr_read(p1);
     return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -278,15 +266,7 @@ int launch_fb(const FbParams& p0, int B, hipStream_t stream) {
     auto kk = x3 ? sa_flash_bwd_kernel<D, C2, true, true> : sa_flash_bwd_kernel<D, C2, true, false>;
     auto kq = x3 ? sa_flash_bwd_kernel<D, C2, false, true> : sa_flash_bwd_kernel<D, C2, false, false>;
     static unsigned attr_mask[2] = {0, 0};
-    unsigned* am = &attr_mask[x3 ? 1 : 0];
-    if (gssd_attr_needed(am)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_k) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kq), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_q) != hipSuccess) {
-            gssd_set_error("hipFuncSetAttribute failed (attention backward)");
-            return GSSD_ELAUNCH;
-        }
-    }
-    gssd_attr_done(am);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask[x3 ? 1 : 0], kk, smem_k, kq, smem_q)) return rc;
     hipLaunchKernelGGL(kk, dim3(B * p.own_blocks), dim3(256), smem_k, stream, p);
     GSSD_CHECK_LAUNCH();
     hipLaunchKernelGGL(kq, dim3(B * p.own_blocks), dim3(256), smem_q, stream, p);

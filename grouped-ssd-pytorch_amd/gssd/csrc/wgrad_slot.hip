@@ -13,8 +13,7 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
@@ -24,19 +23,6 @@ constexpr int A_STAGE = BK * BM, B_STAGE = BK * BN;
 constexpr int LDS_FLOATS = 2 * (A_STAGE + B_STAGE);
 
 __device__ __attribute__((aligned(16))) float g_zero_ws[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16(const float* src, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 struct WsParams {
     const float* dy;      // [R][Cout]
@@ -270,12 +256,7 @@ static int launch_ws(const WsParams& p, int groups, hipStream_t stream) {
     static unsigned attr_mask = 0;
     constexpr int smem = LDS_FLOATS * (int)sizeof(float);
     auto kern = wgrad_slot_kernel<CONV>;
-    if (gssd_attr_needed(&attr_mask) &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-        gssd_set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", smem);
-        return GSSD_ELAUNCH;
-    }
-    gssd_attr_done(&attr_mask);
+    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
     hipLaunchKernelGGL(kern, dim3(p.ntn * p.mtiles, groups, p.split), dim3(256), smem, stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;

@@ -60,6 +60,7 @@ class SnItem(C.Structure):
 
 OUT_NHWC, OUT_TRANSPOSED, OUT_HEADS, OUT_SPLIT_T = 0, 1, 2, 3
 CONV_OUT_F32, CONV_OUTB_BF16_PERM32, CONV_HEADS_SLICES, CONV_POOL2, CONV_RESID_F32, CONV_F16_OK = 1, 2, 4, 8, 16, 32
+CONV_IN_NCHW3, CONV_OUT_GROUPCAT = 64, 128
 
 # name -> (restype, argtypes); mirrors include/gssd_hip.h one to one
 SIGNATURES = {
@@ -82,6 +83,7 @@ SIGNATURES = {
     'gssd_conv_x6_takes': (c_i, [C.POINTER(ConvDesc)]),
     'gssd_conv_wino_x6_takes': (c_i, [C.POINTER(ConvDesc)]),
     'gssd_conv_thin_x6_takes': (c_i, [C.POINTER(ConvDesc)]),
+    'gssd_conv_thin_nchw3_takes': (c_i, [C.POINTER(ConvDesc)]),
     'gssd_plan_fn_count': (c_i, []),
     'gssd_plan_fn_name': (C.c_char_p, [c_i]),
     'gssd_plan_fn_index': (c_i, [C.c_char_p]),

@@ -384,7 +384,7 @@ extern "C" int gssd_conv2d_nhwc_f32(const gssd_conv_desc* dp, gssd_stream_t stre
     GSSD_CHECK_ARG(d.cin_g > 0 && d.cin_g % 4 == 0 && d.in_stride % 4 == 0 && d.in_ch_off % 4 == 0);
     GSSD_CHECK_ARG(d.KH > 0 && d.KW > 0 && d.stride > 0 && d.dil > 0 && d.pad >= 0);
     GSSD_CHECK_ARG(d.K == d.KH * d.KW * d.cin_g && d.wgt_row_stride >= d.K && d.wgt_row_stride % 4 == 0);
-    GSSD_CHECK_ARG(((uintptr_t)d.in % 16) == 0 && ((uintptr_t)d.wgt % 16) == 0);
+    GSSD_CHECK_ARG(((uintptr_t)d.in % ((d.flags & GSSD_CONV_IN_NCHW3) ? 4 : 16)) == 0 && ((uintptr_t)d.wgt % 16) == 0);
     GSSD_CHECK_ARG(d.out_mode >= 0 && d.out_mode <= 3);
     if (d.out_mode == GSSD_OUT_SPLIT_T) {
         GSSD_CHECK_ARG((d.m_per_image || (d.Ho * d.Wo) % 4 == 0) && d.groups == 1 && d.out_b && d.split_n > 0 && d.split_n < d.Cout &&
@@ -415,6 +415,18 @@ extern "C" int gssd_conv2d_nhwc_f32(const gssd_conv_desc* dp, gssd_stream_t stre
     const int M = (int)Mll;
     const int cout_g = d.Cout / d.groups;
     hipStream_t s = as_stream(stream);
+    if (d.flags & GSSD_CONV_IN_NCHW3) {                   // `in` is the NCHW image batch: only the patch-staged thin kernel reads that
+        const int rc = gssd_try_conv_thin(d, s);
+        if (rc != 1) return rc;
+        gssd_set_error("GSSD_CONV_IN_NCHW3: not conv1_1's shape (see gssd_conv_thin_nchw3_takes)");
+        return GSSD_EINVAL;
+    }
+    if (d.flags & GSSD_CONV_OUT_GROUPCAT) {               // grouped destination remap: an epilogue of csrc/conv_x6.hip only
+        const int rc = d.wgt_x6 ? gssd_try_conv_x6(d, s) : 1;
+        if (rc != 1) return rc;
+        gssd_set_error("GSSD_CONV_OUT_GROUPCAT: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)");
+        return GSSD_EINVAL;
+    }
     if (d.wgt_patch) {
         const int rc = gssd_try_conv_patch_x6(d, s);  // many input channels, <= 128 outputs, GSSD_CONV_F16_OK: patch-staged direct conv on fp16 planes (round 6)
         if (rc != 1) return rc;

@@ -42,8 +42,11 @@ struct ThinParams {
 };
 
 // FIXED: the 8 x 16 tile is a compile-time constant (all pixel <-> tile arithmetic folds; fragment offsets need 3 registers)
-template <int CIN_G, int COUT_G, bool FIXED, bool XF>
+// NCHW3 (conv1_1, GSSD_CONV_IN_NCHW3): p.in is the caller's [B][4 * 3][H][W] image batch; the patch is assembled from the three planes of
+// each phase group (fourth channel = 0) instead of being copied from a packed NHWC map -- same LDS contents, same MFMA loop and epilogue
+template <int CIN_G, int COUT_G, bool FIXED, bool XF, bool NCHW3 = false>
 __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_kernel(const ThinParams p) {
+    static_assert(!NCHW3 || (CIN_G == 4 && FIXED && !XF), "the NCHW staging is built for conv1_1");
     constexpr int CIN = 4 * CIN_G, COUT = 4 * COUT_G;
     constexpr int QPR = CIN / 4;                  // 16-byte quads per pixel row
     constexpr int PPI = 64 / QPR;                 // pixels per DMA wave instruction
@@ -134,6 +137,29 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_kernel(c
         const int y0 = tyi * TH, x0 = txi * TW;
 
         // ---- stage the (TH+2) x (TW+2) patch: pixel rows of CIN floats, quads XOR-swizzled by the patch row -----
+        if constexpr (NCHW3) {
+            // thread -> (patch pixel, 16-byte slot): three plane loads (coalesced along x: 16 pixels x 4 planes per wave instruction) and one
+            // 16-byte LDS store; the four slots of a pixel are consecutive lanes, so the stores of a wave are one contiguous 1 KB run
+            constexpr int NITEM = 10 * 18 * 4;
+            const int HW = p.H * p.W;
+#pragma unroll
+            for (int it = 0; it < (NITEM + 255) / 256; ++it) {
+                const int i = it * 256 + tid;
+                const int pp = i >> 2;
+                const int py = (int)(((unsigned)pp * inv_pw) >> 16), pxx = pp - py * PW;
+                const int lq = (i & 3) ^ (pxx & 3);         // phase group whose channels live in this slot
+                const int iy = y0 - 1 + py, ix = x0 - 1 + pxx;
+                const bool ok = i < NITEM && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (ok) {
+                    const float* src = p.in + (size_t)(b * 12 + lq * 3) * HW + iy * p.W + ix;
+                    v[0] = src[0];
+                    v[1] = src[HW];
+                    v[2] = src[2 * HW];
+                }
+                if (i < NITEM) *reinterpret_cast<f32x4*>(smem + i * 4) = v;
+            }
+        } else
         for (int i = g; i < ninstr; i += 4) {
             const int pp = i * PPI + lane / QPR;
             const int py = (int)(((unsigned)pp * inv_pw) >> 16), pxx = pp - py * PW;
@@ -282,7 +308,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_kernel(c
     }
 }
 
-template <int CIN_G, int COUT_G, bool FIXED, bool XF>
+template <int CIN_G, int COUT_G, bool FIXED, bool XF, bool NCHW3 = false>
 int launch_thin_impl(const gssd_conv_desc& d, hipStream_t stream) {
     constexpr int CIN = 4 * CIN_G, COUT = 4 * COUT_G;
     ThinParams p;
@@ -317,7 +343,7 @@ int launch_thin_impl(const gssd_conv_desc& d, hipStream_t stream) {
     const size_t work = patch_bytes > out_bytes ? patch_bytes : out_bytes;
     p.acc_off = (int)(work / sizeof(float));
     const size_t smem = work + 2 * COUT * sizeof(double);
-    auto kern = conv_thin_kernel<CIN_G, COUT_G, FIXED, XF>;
+    auto kern = conv_thin_kernel<CIN_G, COUT_G, FIXED, XF, NCHW3>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
     if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, 96 * 1024)) return rc;
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
@@ -337,17 +363,29 @@ int launch_thin(const gssd_conv_desc& d, hipStream_t stream) {
                       : launch_thin_impl<CIN_G, COUT_G, true, false>(d, stream);
 }
 
+bool thin_shape_ok(const gssd_conv_desc& d) {
+    return d.groups == 4 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.dil == 1 &&
+           d.in_stride == 4 * d.cin_g && d.in_ch_off == 0 && d.out_mode == GSSD_OUT_NHWC &&
+           d.out_stride == d.Cout && d.out_ch_off == 0 && !d.m_per_image && !d.relu && !d.gate &&
+           !d.resid && !d.alpha && d.split_k == 1 && d.wgt_row_stride == 9 * d.cin_g &&
+           d.H * d.W >= 75 * 75 && ((uintptr_t)d.out % 16) == 0 && !(d.flags & GSSD_CONV_POOL2);
+}
+
+// GSSD_CONV_IN_NCHW3: conv1_1's shape only, plain input (no producer BatchNorm), 32-bit element offsets into the image batch
+bool thin_nchw3_ok(const gssd_conv_desc& d) {
+    return thin_shape_ok(d) && d.cin_g == 4 && d.Cout == 64 && !d.in_scale && ((uintptr_t)d.in % 4) == 0 &&
+           (long long)d.B * 12 * d.H * d.W < (1ll << 31);
+}
+
 }  // namespace
+
+extern "C" int gssd_conv_thin_nchw3_takes(const gssd_conv_desc* d) { return (d && thin_nchw3_ok(*d)) ? 1 : 0; }
 
 // Eligibility + dispatch; called from gssd_conv2d_nhwc_f32 (conv_igemm.hip).  Returns 1 if not eligible.
 int gssd_try_conv_thin(const gssd_conv_desc& d, hipStream_t stream) {
     const int cout_g = d.Cout / d.groups;
-    const bool shape_ok = d.groups == 4 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.dil == 1 &&
-                          d.in_stride == 4 * d.cin_g && d.in_ch_off == 0 && d.out_mode == GSSD_OUT_NHWC &&
-                          d.out_stride == d.Cout && d.out_ch_off == 0 && !d.m_per_image && !d.relu && !d.gate &&
-                          !d.resid && !d.alpha && d.split_k == 1 && d.wgt_row_stride == 9 * d.cin_g &&
-                          d.H * d.W >= 75 * 75 && ((uintptr_t)d.out % 16) == 0;
-    if (!shape_ok || (d.flags & GSSD_CONV_POOL2)) return 1;      // (no pooled epilogue here: conv1_2 takes the Winograd thin kernel)
+    if (d.flags & GSSD_CONV_IN_NCHW3) return thin_nchw3_ok(d) ? launch_thin_impl<4, 16, true, false, true>(d, stream) : 1;
+    if (!thin_shape_ok(d)) return 1;                             // (no pooled epilogue here: conv1_2 takes the Winograd thin kernel)
     if (d.cin_g == 4 && cout_g == 16) return launch_thin<4, 16>(d, stream);
     if (d.cin_g == 16 && cout_g == 16) return launch_thin<16, 16>(d, stream);
     // conv2_1 with Winograd weights goes to conv_wino<32> (round 4: this direct kernel is pipe-bound -- fp32 MFMA + VALU 93 % busy -- at

@@ -326,12 +326,16 @@ __global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_c
     float* red = reinterpret_cast<float*>(smem_h);          // [2 wm][BN][2]
     const float gate = p.gate ? *p.gate : 0.f;
     const bool split_t = p.out_mode == GSSD_OUT_SPLIT_T && n0g >= p.split_n;      // workgroup-uniform: split_n is a multiple of the tile
+    const bool gcat = (p.flags & GSSD_CONV_OUT_GROUPCAT) != 0;
 #pragma unroll
     for (int u = 0; u < NT / 2; ++u) {
         const int nl = wn * WTN + 32 * u + 8 * kq;            // channel inside the tile
         const int ng = n0g + nl;                              // ... inside the group
         const bool n_ok = ng + 8 <= cout_g;
         const int n = g * cout_g + ng;
+        // GSSD_CONV_OUT_GROUPCAT: channel n lands behind the split_n-channel slabs in front of it once more (the per-group concatenation
+        // slice_and_cat would build); 8-channel vectors never straddle a slab
+        const int ncat = gcat ? (n / p.split_n) * p.split_n : 0;
         float bv[8], av[8], ssum[8], ssq[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -360,7 +364,8 @@ __global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_c
                 continue;
             }
             // conv_igemm's epilogue order: gate, second output, residual, ReLU
-            const size_t o = (size_t)m * p.out_stride + p.out_ch_off + n;
+            const size_t o = (size_t)m * p.out_stride + p.out_ch_off + n + ncat;
+            const size_t ro = gcat ? (size_t)m * p.Cout + n : o;      // (the residual keeps its own dense rows)
             if (p.gate) {
 #pragma unroll
                 for (int c = 0; c < 8; ++c) v[c] *= gate;
@@ -370,7 +375,7 @@ __global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_c
                 }
             }
             if (p.resid) {
-                const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + o), r1 = *reinterpret_cast<const f32x4*>(p.resid + o + 4);
+                const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + ro), r1 = *reinterpret_cast<const f32x4*>(p.resid + ro + 4);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     v[c] += r0[c];
@@ -813,12 +818,16 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
     float* red = reinterpret_cast<float*>(smem_h);          // [2 wm][BN][2]
     const float gate = p.gate ? *p.gate : 0.f;
     const bool split_t = p.out_mode == GSSD_OUT_SPLIT_T && n0g >= p.split_n;      // workgroup-uniform: split_n is a multiple of the tile
+    const bool gcat = (p.flags & GSSD_CONV_OUT_GROUPCAT) != 0;
 #pragma unroll
     for (int u = 0; u < NT / 2; ++u) {
         const int nl = wn * WTN + 32 * u + 8 * kq;            // channel inside the tile
         const int ng = n0g + nl;                              // ... inside the group
         const bool n_ok = ng + 8 <= cout_g;
         const int n = g * cout_g + ng;
+        // GSSD_CONV_OUT_GROUPCAT: channel n lands behind the split_n-channel slabs in front of it once more (the per-group concatenation
+        // slice_and_cat would build); 8-channel vectors never straddle a slab
+        const int ncat = gcat ? (n / p.split_n) * p.split_n : 0;
         float bv[8], av[8], ssum[8], ssq[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -847,7 +856,8 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
                 continue;
             }
             // conv_igemm's epilogue order: gate, second output, residual, ReLU
-            const size_t o = (size_t)m * p.out_stride + p.out_ch_off + n;
+            const size_t o = (size_t)m * p.out_stride + p.out_ch_off + n + ncat;
+            const size_t ro = gcat ? (size_t)m * p.Cout + n : o;      // (the residual keeps its own dense rows)
             if (p.gate) {
 #pragma unroll
                 for (int c = 0; c < 8; ++c) v[c] *= gate;
@@ -857,7 +867,7 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
                 }
             }
             if (p.resid) {
-                const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + o), r1 = *reinterpret_cast<const f32x4*>(p.resid + o + 4);
+                const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + ro), r1 = *reinterpret_cast<const f32x4*>(p.resid + ro + 4);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     v[c] += r0[c];
@@ -1008,7 +1018,13 @@ extern "C" int gssd_conv_x6_takes(const gssd_conv_desc* dp) {
     const gssd_conv_desc& d = *dp;
     if (!d.wgt_x6 || d.groups <= 0 || d.Cout % d.groups != 0) return 0;
     if (!shape_ok(d.cin_g, d.Cout / d.groups, d.groups)) return 0;
-    if (d.split_k > 1 || (d.flags & ~(GSSD_CONV_OUT_F32 | GSSD_CONV_F16_OK)) || (d.out2 && !d.gate)) return 0;
+    if (d.split_k > 1 || (d.flags & ~(GSSD_CONV_OUT_F32 | GSSD_CONV_F16_OK | GSSD_CONV_OUT_GROUPCAT)) || (d.out2 && !d.gate)) return 0;
+    if (d.flags & GSSD_CONV_OUT_GROUPCAT) {
+        // per-group concatenation written by the epilogue: one conv group, NHWC, whole slabs of 8-channel vectors, rows wide enough for both halves
+        if (d.out_mode != GSSD_OUT_NHWC || d.groups != 1 || d.m_per_image || d.relu || d.stats || d.split_n <= 0 || d.split_n % 8 != 0 ||
+            d.Cout % d.split_n != 0 || d.out_stride < 2 * d.Cout)
+            return 0;
+    }
     if (d.out_mode == GSSD_OUT_SPLIT_T) {
         // merged Self_Attn projection: columns [0, split_n) NHWC, the rest transposed per image; whole tiles on either side
         const int bn = gssd_conv_x6_tile(d.Cout / d.groups, d.groups, (long long)d.B * d.Ho * d.Wo);

@@ -298,7 +298,7 @@ class _Plan(_PlanBase, PlanGraphMixin, PlanOpsMixin, PlanExecMixin):
         self._finish_heads()
         self._place_sn_step()
         self._place_branch0()
-
+        self._fuse_input_pack()
 
     # ------------------------------------------------------------------------------------------------
     def _add(self, fn, args, keep=None, tag=None):

@@ -29,6 +29,12 @@ USE_GRAPH = os.environ.get('GSSD_NO_GRAPH', '0') != '1'
 USE_FLASH_X6 = os.environ.get('GSSD_FLASH_X6', '1') != '0'
 # GSSD_NO_BRANCH_STREAMS=1 captures the plan as one serial chain (ablation)
 USE_BRANCH_STREAMS = os.environ.get('GSSD_NO_BRANCH_STREAMS', '0') != '1'
+# conv1_1 of a no-backward fp32 plan reads the caller's NCHW batch itself (csrc/conv_thin.hip, GSSD_CONV_IN_NCHW3): no gssd_pack_input_nhwc
+# launch and no packed copy; GSSD_FUSE_PACK=0 keeps the pack launch (A-B in the same build)
+FUSE_PACK = os.environ.get('GSSD_FUSE_PACK', '1') != '0'
+# the o conv of Self_Attn-base 0 in a no-backward fp32 plan writes its two outputs straight into the per-group concatenation the DCN reads
+# (csrc/conv_x6.hip, GSSD_CONV_OUT_GROUPCAT): no gssd_slice_and_cat_f32 launch; GSSD_FUSE_CAT=0 keeps the copy pass
+FUSE_CAT = os.environ.get('GSSD_FUSE_CAT', '1') != '0'
 SN_STREAM = 9               # stream id of the spectral-norm launch inside a captured graph
 ALL_STREAMS = -1            # _Step.wait value: join every forked stream before this step
 

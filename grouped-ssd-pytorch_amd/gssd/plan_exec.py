@@ -66,7 +66,7 @@ class PlanExecMixin:
         loc = torch.empty(B, self.P, 4, device=dev, dtype=torch.float32)
         conf = torch.empty(B, self.P, self.nc, device=dev, dtype=torch.float32)
         self._set_outputs(loc, conf)
-        self.steps[self._pack_step].args[0] = x.data_ptr()
+        self._set_input(x.data_ptr())
         if self.training:
             self.stats.zero_()
         stream = torch.cuda.current_stream().cuda_stream
@@ -133,7 +133,7 @@ class PlanExecMixin:
             self._gloc = torch.zeros(B, self.P, 4, device=dev, dtype=torch.float32)
             self._gconf = torch.zeros(B, self.P, self.nc, device=dev, dtype=torch.float32)
         self._set_outputs(self._gloc, self._gconf)
-        self.steps[self._pack_step].args[0] = in_ptr if in_ptr is not None else self._gx.data_ptr()
+        self._set_input(in_ptr if in_ptr is not None else self._gx.data_ptr())
         groups, cur = [], []
         for st in self.steps:
             if only and st.tag is not None and st.tag[0] in only:

@@ -3,7 +3,7 @@ branches fork, where the heads reduce.  Mixin of engine._Plan; the per-op emitte
 import ctypes as C
 import os
 import torch
-from . import _lib, ops
+from . import _lib, ops, plan_common
 from ._lib import lib
 from .plan_common import ALL_STREAMS, FUSE_NAMES, SN_STREAM, VGG_CFG
 
@@ -37,6 +37,33 @@ class PlanGraphMixin:
         st = self.steps.pop(sn)                       # (sn == 0: registered before the pack step)
         self._pack_step -= 1
         self.steps.insert(self._pack_step + 2, st)    # behind pack_input and conv1_1; every later index is unchanged
+
+    def _fuse_input_pack(self):
+        """A plan no backward will read (conv1_1's weight gradient reads the packed copy) drops the input pack: conv1_1 -- the launch
+        right behind it -- stages its patches from the NCHW batch (include/gssd_hip.h: GSSD_CONV_IN_NCHW3; 93 us of a strict chain at
+        batch 32).  Whenever the library's patch-staged kernel declines the descriptor (bf16 storage, other group counts, the plain
+        graph's conv + ReLU launch) the pack step stays.  Called last: every step index behind the pack moves down by one."""
+        i = self._pack_step
+        if (not plan_common.FUSE_PACK or not getattr(self, 'nograd', False) or self.bf16 or i + 1 >= len(self.steps)
+                or self.steps[i].fn is not lib.gssd_pack_input_nhwc):
+            return
+        st, x16_ptr = self.steps[i + 1], self.steps[i].args[1]
+        d = st.keep
+        if (st.fn is not lib.gssd_conv2d_nhwc_f32 or not isinstance(d, _lib.ConvDesc) or d.in_ != x16_ptr or st.wait is not None
+                or lib.gssd_conv_thin_nchw3_takes(C.byref(d)) != 1):
+            return
+        d.flags |= _lib.CONV_IN_NCHW3
+        del self.steps[i]
+        self._reduce_steps = tuple(k - 1 for k in self._reduce_steps)
+        self._pack_step, self._in_desc = None, d
+
+    def _set_input(self, ptr):
+        """The address the step reads its NCHW batch from: the pack launch's source, or conv1_1's input (_fuse_input_pack)."""
+        d = self.__dict__.get('_in_desc')
+        if d is not None:
+            d.in_ = ptr
+        else:
+            self.steps[self._pack_step].args[0] = ptr
 
     def _build_bn_graph(self, x16):
         """models/...group.py:254-372, batch_norm=True (the driver's graph, train_lesion_multiphase_v2.py:77)."""
@@ -180,12 +207,18 @@ class PlanGraphMixin:
     def _after_conv4_3(self, x, H, Cc):
         """models/...group.py:261-298: [SA-base] -> [slice_and_cat] -> [DCN]* -> L2Norm -> [SA] -> fuse_11; pool4."""
         net, B = self.eng.net, self.B
-        attn_g = None
+        attn_g, cat_g = None, 0
         if net.use_self_attention_base:
-            x, attn_g = self._self_attn('self_attn_base_list', 0, x, H, Cc, need_out2=bool(net.dcn_cat_sab), want_map=self.want_maps)
+            # no backward, fp32: the block's o conv writes slice_and_cat's result itself where its kernel can (plan_ops._self_attn)
+            cat_g = (net.groups_vgg if (plan_common.FUSE_CAT and getattr(self, 'nograd', False) and not self.bf16 and net.use_dcn
+                                        and net.dcn_cat_sab) else 0)
+            x, attn_g = self._self_attn('self_attn_base_list', 0, x, H, Cc, need_out2=bool(net.dcn_cat_sab), want_map=self.want_maps,
+                                        cat_groups=cat_g)
         if net.use_dcn:
             xin, Cin = x, Cc
-            if net.dcn_cat_sab:
+            if net.dcn_cat_sab and cat_g and attn_g is None:
+                xin, Cin = x, 2 * Cc                 # x is the concatenation already
+            elif net.dcn_cat_sab:
                 xc = self._abuf(B, H, H, 2 * Cc)
                 esz = 2 if self.bf16 else 1          # a pure copy: bf16 pairs travel as one 4-byte word
                 self._add(lib.gssd_slice_and_cat_f32, (x.data_ptr(), attn_g.data_ptr(), xc.data_ptr(), B * H * H, Cc // esz, Cc // esz,

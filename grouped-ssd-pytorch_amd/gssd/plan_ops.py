@@ -221,11 +221,13 @@ class PlanOpsMixin:
         self.rec.append(('pool', dict(x_in=x, out=out, H=H, C=Cc, k=k, s=s, p=p, Hp=Hp)))
         return out, Hp
 
-    def _self_attn(self, lst_name, idx, x, H, Cc, need_out2, want_map=False):
+    def _self_attn(self, lst_name, idx, x, H, Cc, need_out2, want_map=False, cat_groups=0):
         """layers/self_attn.py:46-89 as three launches: ONE pass over x for the theta | phi | g projections (K9; g written
         transposed), the flash-style core theta^T phi -> softmax -> . g (K10, csrc/flash_attn.hip: the [N, N] map never exists),
         and the o conv with the sigma-gated residual epilogue.  ``want_map`` (visualize=True, op-level tests) additionally
-        materialises the attention map with two extra launches; the output path does not read it."""
+        materialises the attention map with two extra launches; the output path does not read it.  ``cat_groups`` > 0 (with need_out2): the
+        caller's only use of the two outputs is slice_and_cat over that many groups; when csrc/conv_x6.hip takes the o conv with the
+        grouped destination remap the block writes the concatenation itself and returns (xc [B,H,H,2C], None)."""
         eng, B = self.eng, self.B
         sa = getattr(eng.net, lst_name)[idx]
         a_tpg, a_o = self.sa_state[(lst_name, idx)]
@@ -292,6 +294,21 @@ class PlanOpsMixin:
             x6_o = eng._pack(name + f'.o.x6@{ops.x6_tile(Cc, 1, B * N)}', build_x6o)
         d5, _, _ = mk(ag, w_o, out, B=B, H=H, W=H, in_stride=C2, cin_g=C2, Cout=Cc, bias=sa.snconv1x1_attn.bias.detach(),
                       alpha=a_o, gate=sa.sigma.detach(), resid=x, out2=out2, wgt_x6=x6_o, flags=self.f16_ok)
+        xc = None
+        if cat_groups and need_out2 and x6_o is not None and Cc % cat_groups == 0:
+            ga = Cc // cat_groups
+            xc = self._abuf(B, H, H, 2 * Cc)
+            dc, _, _ = mk(ag, w_o, xc, B=B, H=H, W=H, in_stride=C2, cin_g=C2, Cout=Cc, bias=sa.snconv1x1_attn.bias.detach(),
+                          alpha=a_o, gate=sa.sigma.detach(), resid=x, out2=xc.view(-1)[ga:], wgt_x6=x6_o, out_stride=2 * Cc, split_n=ga,
+                          flags=self.f16_ok | _lib.CONV_OUT_GROUPCAT)
+            if lib.gssd_conv_x6_takes(C.byref(dc)) == 1:
+                d5 = dc
+                self.bufs[:] = [t for t in self.bufs if t is not out and t is not out2]      # the separate maps are never written
+                v = xc.view(B, H, H, cat_groups, 2, ga)       # the separate outputs, as views (records / debugging)
+                out, out2 = v[:, :, :, :, 0], v[:, :, :, :, 1]
+            else:
+                self.bufs[:] = [t for t in self.bufs if t is not xc]
+                xc = None
         fn = self.conv_fn
         if C4 % 64 == 0:
             self._add(fn, (C.byref(d1),), keep=(d1, w_tpg, b_tpg))
@@ -350,6 +367,8 @@ class PlanOpsMixin:
         self.attn_maps[(lst_name, idx)] = (S, Nk, Nkp)
         self.rec.append(('sa', dict(mod=sa, name=name, x_in=x, out=out, out2=out2, H=H, C=Cc, tp=tp, gT=gT, ag=ag, N=N, Np=Np,
                                     inv_sigma=(a_tpg, a_o), P=P, Nk=Nk, Nkp=Nkp, kp=kp, gTp=gTp, lse=lse)))
+        if xc is not None:
+            return xc, None
         return out, out2
 
     def _dcn(self, li, x, H, Cin):

@@ -203,6 +203,21 @@ int gssd_conv_x6_takes(const gssd_conv_desc* d);
  * mode (running statistics bound nothing) and never on a data-gradient launch (fp16 has no exponent range for gradients).  GSSD_X6_F16=0 (environment)
  * ignores it. */
 #define GSSD_CONV_F16_OK 32
+/* fp32 entry point, conv1_1 only (4 phase groups, 4 -> 16 channels per group, 3x3 / stride 1 / pad 1, plain input, batch sums allowed): `in` is
+ * the caller's NCHW image batch [B][4 * 3][H][W] instead of the packed NHWC map gssd_pack_input_nhwc makes of it -- group g reads planes 3g .. 3g + 2
+ * as its channels 0 .. 2 and zero as channel 3; cin_g / in_stride / K / the packed weights stay those of the padded form (4 / 16 / 36), `in` needs
+ * 4-byte alignment only.  The patch-staged kernel (csrc/conv_thin.hip) assembles the same LDS patch from the planes, so the output and the batch
+ * sums are those of pack + conv bit for bit, and the 184 MB (batch 32) packed copy is neither written nor re-read.  Only that kernel reads the
+ * layout: gssd_conv_thin_nchw3_takes() tells whether it runs a descriptor; any other descriptor with the flag returns GSSD_EINVAL. */
+#define GSSD_CONV_IN_NCHW3 64
+/* fp32 entry point, GSSD_OUT_NHWC, one conv group: the epilogue writes the per-group concatenation gssd_slice_and_cat_f32 would build of `out`
+ * and `out2` (models/ssd_multiphase_custom_group.py slice_and_cat behind Self_Attn-base 0).  split_n = channels per slab (Cout / the trunk's
+ * group count): output channel n is stored at column n + (n / split_n) * split_n of rows of out_stride (>= 2 * Cout) floats, in `out` and --
+ * with a gate -- in `out2`; the caller points `out` at the concatenated map and `out2` split_n floats behind it, so slab s of `out` fills
+ * [2 s split_n, (2 s + 1) split_n) and slab s of `out2` the split_n columns after it.  `resid` keeps its own dense rows of Cout floats.  Same
+ * values as the separate outputs, bit for bit.  Only csrc/conv_x6.hip has the epilogue (gssd_conv_x6_takes() tells); any other descriptor
+ * with the flag returns GSSD_EINVAL. */
+#define GSSD_CONV_OUT_GROUPCAT 128
 int gssd_conv2d_nhwc_bf16(const gssd_conv_desc* d, gssd_stream_t stream);
 /* OIHW fp32 -> packed bf16 rows [Cout][Kpad] (cin_g_pad, Kpad multiples of 8); fp32 -> bf16 array cast (round to nearest even) */
 int gssd_pack_conv_weight_bf16(const float* w_oihw, void* w_packed, int Cout, int cin_g, int KH, int KW, int cin_g_pad, int Kpad,
@@ -829,6 +844,8 @@ int gssd_conv_wino_x6_takes(const gssd_conv_desc* d);
  * models/ssd_multiphase_custom_group.py:434-460 -- plain or with the fused producer BatchNorm + ReLU / batch sums / GSSD_CONV_POOL2 epilogue
  * (no residual: their data gradients stay with the fp32 kernels).  GSSD_THIN_X6=0: never. */
 int gssd_conv_thin_x6_takes(const gssd_conv_desc* d);
+/* 1 when gssd_conv2d_nhwc_f32 runs the descriptor (with or without the flag set) in its GSSD_CONV_IN_NCHW3 form */
+int gssd_conv_thin_nchw3_takes(const gssd_conv_desc* d);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 
 usage: python3 scripts/critical_path.py <..._kernel_trace.csv> [label] [steps-from-the-end]
 
-A step = everything between two consecutive launches of the input pack kernel (the first launch of the plan; the steps before the
+A step = everything between two consecutive launches of the plan's first kernel -- the input pack kernel, or conv1_1 reading the NCHW
+batch itself (conv_thin_kernel<4,16,..,true>) in plans without a pack launch -- (the steps before the
 timed ones include captures and eager passes, so the LAST complete steps of the trace are used and averaged).  hipGraph replays map
 the plan's streams (trunk, six source branches, spectral norm) onto the device's hardware queues; the trace has no dependency
 edges, so the critical path is reconstructed the usual way: walk back from the kernel that ends last; the predecessor of a kernel is
@@ -40,7 +41,8 @@ def load(path):
 
 
 def steps_of(rows):
-    marks = [i for i, r in enumerate(rows) if 'pack_input' in r['name']]
+    first = re.compile(r'pack_input|conv_thin_kernel<4, ?16, ?true, ?false, ?true>')
+    marks = [i for i, r in enumerate(rows) if first.search(r['name'])]
     return [(rows[a:b]) for a, b in zip(marks[:-1], marks[1:])]
 
 
@@ -106,7 +108,7 @@ def main():
     rows = load(path)
     steps = steps_of(rows)
     if not steps:
-        print('no input-pack kernel in the trace')
+        print('no input-pack / NCHW conv1_1 kernel in the trace')
         return
     # the steady steps: the last `last_n` whose launch count equals the mode of the last 2 * last_n
     tail = steps[-2 * last_n:]

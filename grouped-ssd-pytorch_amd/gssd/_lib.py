@@ -60,7 +60,7 @@ class SnItem(C.Structure):
 
 OUT_NHWC, OUT_TRANSPOSED, OUT_HEADS, OUT_SPLIT_T = 0, 1, 2, 3
 CONV_OUT_F32, CONV_OUTB_BF16_PERM32, CONV_HEADS_SLICES, CONV_POOL2, CONV_RESID_F32, CONV_F16_OK = 1, 2, 4, 8, 16, 32
-CONV_IN_NCHW3, CONV_OUT_GROUPCAT = 64, 128
+CONV_IN_NCHW3, CONV_OUT_GROUPCAT, CONV_OUT_X6PLANES, CONV_RESID_XF = 64, 128, 256, 512
 
 # name -> (restype, argtypes); mirrors include/gssd_hip.h one to one
 SIGNATURES = {
@@ -147,6 +147,7 @@ SIGNATURES = {
     'gssd_self_attn_core_x6_supported': (c_i, [c_i, c_i]),
     'gssd_self_attn_core_x6_ws_bytes': (C.c_longlong, [c_i, c_i, c_i, c_i]),
     'gssd_self_attn_core_x6_f32': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
+    'gssd_self_attn_core_x6_planes_f32': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     'gssd_self_attn_core_bf16v': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     'gssd_softmax_rows_f32': (c_i, [c_fp, c_i64, c_i, c_i, c_fp]),
     'gssd_slice_and_cat_f32': (c_i, [c_fp, c_fp, c_fp, c_i64, c_i, c_i, c_i, c_fp]),

@@ -512,7 +512,7 @@ extern "C" int gssd_conv2d_nhwc_bf16(const gssd_conv_desc* dp, gssd_stream_t str
     GSSD_CHECK_ARG(dp != nullptr);
     const gssd_conv_desc& d = *dp;
     GSSD_CHECK_ARG(d.in && d.wgt && d.out);
-    GSSD_CHECK_ARG(!(d.flags & (GSSD_CONV_IN_NCHW3 | GSSD_CONV_OUT_GROUPCAT)));      // fp32 entry point only
+    GSSD_CHECK_ARG(!(d.flags & (GSSD_CONV_IN_NCHW3 | GSSD_CONV_OUT_GROUPCAT | GSSD_CONV_OUT_X6PLANES | GSSD_CONV_RESID_XF)));      // fp32 entry point only
     GSSD_CHECK_ARG(d.B > 0 && d.H > 0 && d.W > 0 && d.Ho > 0 && d.Wo > 0);
     GSSD_CHECK_ARG(d.groups > 0 && d.Cout > 0 && d.Cout % d.groups == 0);
     GSSD_CHECK_ARG(d.cin_g > 0 && d.cin_g % 8 == 0 && d.in_stride % 8 == 0 && d.in_ch_off % 8 == 0);

@@ -427,6 +427,18 @@ extern "C" int gssd_conv2d_nhwc_f32(const gssd_conv_desc* dp, gssd_stream_t stre
         gssd_set_error("GSSD_CONV_OUT_GROUPCAT: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)");
         return GSSD_EINVAL;
     }
+    if (d.flags & GSSD_CONV_RESID_XF) {                   // BatchNorm + ReLU of the residual on read: an epilogue of csrc/conv_x6.hip only
+        const int rc = d.wgt_x6 ? gssd_try_conv_x6(d, s) : 1;
+        if (rc != 1) return rc;
+        gssd_set_error("GSSD_CONV_RESID_XF: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)");
+        return GSSD_EINVAL;
+    }
+    if (d.flags & GSSD_CONV_OUT_X6PLANES) {               // the attention core's planes as the output: an epilogue of csrc/conv_x6.hip only
+        const int rc = d.wgt_x6 ? gssd_try_conv_x6(d, s) : 1;
+        if (rc != 1) return rc;
+        gssd_set_error("GSSD_CONV_OUT_X6PLANES: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)");
+        return GSSD_EINVAL;
+    }
     if (d.wgt_patch) {
         const int rc = gssd_try_conv_patch_x6(d, s);  // many input channels, <= 128 outputs, GSSD_CONV_F16_OK: patch-staged direct conv on fp16 planes (round 6)
         if (rc != 1) return rc;

@@ -375,7 +375,17 @@ __global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_c
                 }
             }
             if (p.resid) {
-                const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + ro), r1 = *reinterpret_cast<const f32x4*>(p.resid + ro + 4);
+                f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + ro), r1 = *reinterpret_cast<const f32x4*>(p.resid + ro + 4);
+                if (p.flags & GSSD_CONV_RESID_XF) {
+                    // the residual is its producer's raw map: BatchNorm + ReLU on read, finish_part's expression (bit-identical to the pass)
+                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(p.in_scale + n), s1 = *reinterpret_cast<const f32x4*>(p.in_scale + n + 4);
+                    const f32x4 h0 = *reinterpret_cast<const f32x4*>(p.in_shift + n), h1 = *reinterpret_cast<const f32x4*>(p.in_shift + n + 4);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        r0[c] = fmaxf(r0[c] * s0[c] + h0[c], 0.f);
+                        r1[c] = fmaxf(r1[c] * s1[c] + h1[c], 0.f);
+                    }
+                }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     v[c] += r0[c];
@@ -813,6 +823,83 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
     __syncthreads();
 #undef X6_LOADS_WAIT
 
+    if (p.flags & GSSD_CONV_OUT_X6PLANES) {
+        // ---- merged Self_Attn projection, GSSD_CONV_OUT_X6PLANES: the epilogue stores the three bf16 planes the attention core reads
+        //      (csrc/flash_attn_x6.hip) instead of the fp32 arrays its split pass would re-read.  `out`: theta | phi planes [3][M][split_n];
+        //      `out_b`: g^T planes [3][B][Cout - split_n][out_b_stride], keys permuted inside every 32-block of an image.  Same value
+        //      expression and the same split3 as the two-pass form: the planes are equal bit for bit. --------------------------------
+        constexpr int SLD = BM + 4;                                // fp32 staging rows of the g range: [BN channels][SLD pixels]
+        static_assert(BN * SLD * 4 <= K::LDS_BYTES, "the staging tile lives in the K loop's LDS");
+        float* const stg = reinterpret_cast<float*>(smem_h);
+        u16* const tpp = reinterpret_cast<u16*>(p.out);
+        u16* const gpl = reinterpret_cast<u16*>(p.out_b);
+        const long long tp_plane = (long long)M * p.split_n, g_plane = (long long)p.B * p.outb_batch_stride;
+        const bool g_range = n0g >= p.split_n;                     // workgroup-uniform: split_n is a multiple of the tile
+#pragma unroll
+        for (int u = 0; u < NT / 2; ++u) {
+            const int nl = wn * WTN + 32 * u + 8 * kq;            // channel inside the tile (whole tiles only: gssd_conv_x6_takes)
+            const int n = n0g + nl;
+            float bv[8], av[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                bv[c] = p.bias ? p.bias[n + c] : 0.f;
+                av[c] = p.alpha ? p.alpha[n + c] : 1.f;
+            }
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                const int ml = wm * WTM + i * 16 + r, m = m0 + ml;
+                float v[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] = acc[i][2 * u + (c >> 2)][c & 3] * av[c] + bv[c];
+                if (g_range) {
+                    // (rows beyond M hold the values of zero activations: staged, never stored)
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) stg[(nl + c) * SLD + ml] = v[c];
+                    continue;
+                }
+                if (m >= M) continue;
+                // theta | phi: the lane's 8 consecutive channels of one pixel are one 16-byte unit of every plane
+                bf16x8 h8, m8, l8;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    __bf16 h, mm, l;
+                    split3(v[c], h, mm, l);
+                    h8[c] = h;
+                    m8[c] = mm;
+                    l8[c] = l;
+                }
+                u16* dst = tpp + (size_t)m * p.split_n + n;
+                *reinterpret_cast<bf16x8*>(dst) = h8;
+                *reinterpret_cast<bf16x8*>(dst + tp_plane) = m8;
+                *reinterpret_cast<bf16x8*>(dst + 2 * tp_plane) = l8;
+            }
+        }
+        if (g_range) {
+            // g^T: channel rows of keys.  Slot 8 kq + e of a 32-block holds key 16 (e >> 2) + 4 kq + (e & 3): FOUR consecutive pixels are
+            // four consecutive slots (8 bytes per plane).  Images are a multiple of 4 pixels long and tiles start at a multiple of 4, so a
+            // group of four never straddles an image or the end of M -- ragged first / last 32-blocks of an image need no special case.
+            // A wave stores two channel rows of 32 groups = two 256-byte runs per plane.  The key columns [HoWo, out_b_stride) are never written.
+            __syncthreads();
+            for (int it = tid; it < BN * (BM / 4); it += 256) {
+                const int ch = it / (BM / 4), gr = it - ch * (BM / 4);
+                const int m = m0 + 4 * gr;
+                if (m >= M) continue;
+                const int bi = m / HoWo, ml = m - bi * HoWo;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(stg + ch * SLD + 4 * gr);
+                __bf16 h[4], mm[4], l[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) split3(v[e], h[e], mm[e], l[e]);
+                const int k = ml & 31;
+                u16* dst = gpl + (size_t)bi * p.outb_batch_stride + (size_t)(n0g - p.split_n + ch) * p.out_b_stride + (ml - k) +
+                           8 * ((k >> 2) & 3) + 4 * (k >> 4);
+                *reinterpret_cast<bf16x4*>(dst) = bf16x4{h[0], h[1], h[2], h[3]};
+                *reinterpret_cast<bf16x4*>(dst + g_plane) = bf16x4{mm[0], mm[1], mm[2], mm[3]};
+                *reinterpret_cast<bf16x4*>(dst + 2 * g_plane) = bf16x4{l[0], l[1], l[2], l[3]};
+            }
+        }
+        return;
+    }
+
     // ---- epilogue: + bias, batch sums of the pre-activation output, ReLU, 16-byte NHWC stores (lane: pixel r, 8 consecutive channels
     //      per tile pair) ------------------------------------------------------------------------------------------------------------
     float* red = reinterpret_cast<float*>(smem_h);          // [2 wm][BN][2]
@@ -867,7 +954,17 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
                 }
             }
             if (p.resid) {
-                const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + ro), r1 = *reinterpret_cast<const f32x4*>(p.resid + ro + 4);
+                f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + ro), r1 = *reinterpret_cast<const f32x4*>(p.resid + ro + 4);
+                if (p.flags & GSSD_CONV_RESID_XF) {
+                    // the residual is its producer's raw map: BatchNorm + ReLU on read, finish_part's expression (bit-identical to the pass)
+                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(p.in_scale + n), s1 = *reinterpret_cast<const f32x4*>(p.in_scale + n + 4);
+                    const f32x4 h0 = *reinterpret_cast<const f32x4*>(p.in_shift + n), h1 = *reinterpret_cast<const f32x4*>(p.in_shift + n + 4);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        r0[c] = fmaxf(r0[c] * s0[c] + h0[c], 0.f);
+                        r1[c] = fmaxf(r1[c] * s1[c] + h1[c], 0.f);
+                    }
+                }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     v[c] += r0[c];
@@ -950,7 +1047,7 @@ int launch(const gssd_conv_desc& d, int M, hipStream_t stream) {
     const int cout_g = d.Cout / d.groups;
     const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
     const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
-    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), Cfg<BN>::LDS_BYTES + (d.in_scale ? 8 * d.cin_g : 0), stream, d, M, ntn, mtiles, plane);
+    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), Cfg<BN>::LDS_BYTES + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), stream, d, M, ntn, mtiles, plane);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -965,7 +1062,7 @@ int launch2_impl(const gssd_conv_desc& d, int M, hipStream_t stream) {
     const int cout_g = d.Cout / d.groups;
     const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
     const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
-    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), lds + (d.in_scale ? 8 * d.cin_g : 0), stream, d, M, ntn, mtiles, plane);
+    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), lds + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), stream, d, M, ntn, mtiles, plane);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -976,6 +1073,9 @@ int launch2(const gssd_conv_desc& d, int M, hipStream_t stream) {
     return launch2_impl<BN, XF, false>(d, M, stream);
 }
 #endif
+
+// the fused INPUT transform (GSSD_CONV_RESID_XF: in_scale / in_shift belong to the residual, the input is read plain)
+inline bool x6_in_xf(const gssd_conv_desc& d) { return d.in_scale && !(d.flags & GSSD_CONV_RESID_XF); }
 
 bool shape_ok(int cin_g, int cout_g, int groups) {
     return cin_g > 0 && cin_g % BKC == 0 && cout_g >= 32 && cout_g % 8 == 0 && groups > 0;
@@ -1018,7 +1118,7 @@ extern "C" int gssd_conv_x6_takes(const gssd_conv_desc* dp) {
     const gssd_conv_desc& d = *dp;
     if (!d.wgt_x6 || d.groups <= 0 || d.Cout % d.groups != 0) return 0;
     if (!shape_ok(d.cin_g, d.Cout / d.groups, d.groups)) return 0;
-    if (d.split_k > 1 || (d.flags & ~(GSSD_CONV_OUT_F32 | GSSD_CONV_F16_OK | GSSD_CONV_OUT_GROUPCAT)) || (d.out2 && !d.gate)) return 0;
+    if (d.split_k > 1 || (d.flags & ~(GSSD_CONV_OUT_F32 | GSSD_CONV_F16_OK | GSSD_CONV_OUT_GROUPCAT | GSSD_CONV_OUT_X6PLANES | GSSD_CONV_RESID_XF)) || (d.out2 && !d.gate)) return 0;
     if (d.flags & GSSD_CONV_OUT_GROUPCAT) {
         // per-group concatenation written by the epilogue: one conv group, NHWC, whole slabs of 8-channel vectors, rows wide enough for both halves
         if (d.out_mode != GSSD_OUT_NHWC || d.groups != 1 || d.m_per_image || d.relu || d.stats || d.split_n <= 0 || d.split_n % 8 != 0 ||
@@ -1029,7 +1129,16 @@ extern "C" int gssd_conv_x6_takes(const gssd_conv_desc* dp) {
         // merged Self_Attn projection: columns [0, split_n) NHWC, the rest transposed per image; whole tiles on either side
         const int bn = gssd_conv_x6_tile(d.Cout / d.groups, d.groups, (long long)d.B * d.Ho * d.Wo);
         if (d.groups != 1 || !d.out_b || d.split_n <= 0 || d.split_n % bn != 0 || d.out_b_stride < d.Ho * d.Wo) return 0;
-    } else if (d.out_mode != GSSD_OUT_NHWC) {
+        if (d.flags & GSSD_CONV_OUT_X6PLANES) {
+            // the attention core's planes instead of the fp32 arrays: the v2 kernel's epilogue, whole tiles, dense theta | phi rows, key rows
+            // in whole 32-blocks, images of whole 4-pixel groups, no other epilogue work
+            if (!X6_V2 || bn > 128 || d.Cout % bn != 0 || d.out_stride != d.split_n || d.out_ch_off != 0 || d.out_b_stride % 32 != 0 ||
+                (d.Ho * d.Wo) % 4 != 0 || d.outb_batch_stride != (long long)(d.Cout - d.split_n) * d.out_b_stride || d.relu || d.stats ||
+                d.gate || d.resid || d.out2 || ((uintptr_t)d.out_b % 16))
+                return 0;
+            if (d.m_per_image && d.out_batch_stride != (long long)d.Ho * d.Wo * d.out_stride) return 0;
+        }
+    } else if (d.out_mode != GSSD_OUT_NHWC || (d.flags & GSSD_CONV_OUT_X6PLANES)) {
         return 0;
     }
     if (d.m_per_image) {
@@ -1039,10 +1148,16 @@ extern "C" int gssd_conv_x6_takes(const gssd_conv_desc* dp) {
             return 0;
     }
     if ((d.resid && ((uintptr_t)d.resid % 16)) || (d.out2 && ((uintptr_t)d.out2 % 16))) return 0;
+    if (d.flags & GSSD_CONV_RESID_XF) {
+        // BatchNorm + ReLU of the residual on read (in_scale / in_shift are the RESIDUAL's): NHWC epilogue, the residual's channel is the output's
+        if (!d.resid || !d.in_scale || !d.in_shift || d.out_mode != GSSD_OUT_NHWC || d.out_ch_off != 0 || ((uintptr_t)d.in_scale % 16) ||
+            ((uintptr_t)d.in_shift % 16))
+            return 0;
+    }
     if (d.in_stride % 4 || d.in_ch_off % 4 || d.out_stride % 4 || d.out_ch_off % 4) return 0;
     if (((uintptr_t)d.in % 16) || ((uintptr_t)d.out % 16) || ((uintptr_t)d.wgt_x6 % 16)) return 0;
     if ((long long)d.B * d.H * d.W * d.in_stride >= (1ll << 31)) return 0;
-    if (d.in_scale && d.cin_g > 512) return 0;               // the LDS table of the fused input transform
+    if (x6_in_xf(d) && d.cin_g > 512) return 0;              // the LDS table of the fused input transform
     return 1;
 }
 
@@ -1052,12 +1167,12 @@ int gssd_try_conv_x6(const gssd_conv_desc& d, hipStream_t stream) {
     const int M = (int)Mll;
     switch (gssd_conv_x6_tile(d.Cout / d.groups, d.groups, Mll)) {
 #if X6_V2
-        case 64: return d.in_scale ? launch2<64, true>(d, M, stream) : launch2<64, false>(d, M, stream);
-        case 128: return d.in_scale ? launch2<128, true>(d, M, stream) : launch2<128, false>(d, M, stream);
+        case 64: return x6_in_xf(d) ? launch2<64, true>(d, M, stream) : launch2<64, false>(d, M, stream);
+        case 128: return x6_in_xf(d) ? launch2<128, true>(d, M, stream) : launch2<128, false>(d, M, stream);
 #else
-        case 64: return d.in_scale ? launch<64, true>(d, M, stream) : launch<64, false>(d, M, stream);
-        case 128: return d.in_scale ? launch<128, true>(d, M, stream) : launch<128, false>(d, M, stream);
+        case 64: return x6_in_xf(d) ? launch<64, true>(d, M, stream) : launch<64, false>(d, M, stream);
+        case 128: return x6_in_xf(d) ? launch<128, true>(d, M, stream) : launch<128, false>(d, M, stream);
 #endif
-        default: return d.in_scale ? launch<256, true>(d, M, stream) : launch<256, false>(d, M, stream);
+        default: return x6_in_xf(d) ? launch<256, true>(d, M, stream) : launch<256, false>(d, M, stream);
     }
 }

@@ -354,3 +354,19 @@ extern "C" int gssd_self_attn_core_x6_f32(const float* tp, const float* gT, floa
     if (f16) return N > 1024 ? launch_x6<64, 256, 32, 12, true>(tpp, gp, out, B, N, Np32, lse, s) : launch_x6<64, 256, 32, 4, true>(tpp, gp, out, B, N, Np32, lse, s);
     return N > 1024 ? launch_x6<64, 256, 32, 12, false>(tpp, gp, out, B, N, Np32, lse, s) : launch_x6<64, 256, 32, 4, false>(tpp, gp, out, B, N, Np32, lse, s);
 }
+
+// pass 2 alone: the merged projection wrote the planes itself (csrc/conv_x6.hip, GSSD_CONV_OUT_X6PLANES)
+extern "C" int gssd_self_attn_core_x6_planes_f32(const void* ws, float* out, int B, int N, int D, int C2, float* lse, gssd_stream_t stream) {
+    GSSD_CHECK_ARG(ws && out && B > 0 && N > 0);
+    GSSD_CHECK_ARG(((uintptr_t)out % 16) == 0 && ((uintptr_t)ws % 16) == 0);
+    GSSD_CHECK_ARG((long long)B * ((N + 63) / 64) < (1ll << 31));
+    if (!gssd_self_attn_core_x6_supported(D, C2)) {
+        gssd_set_error("self-attention core (three-plane): unsupported (theta/phi channels %d, g channels %d); built: (64,256)", D, C2);
+        return GSSD_EINVAL;
+    }
+    hipStream_t s = as_stream(stream);
+    const int Np32 = (int)round32(N);
+    const u16* tpp = reinterpret_cast<const u16*>(ws);
+    const u16* gp = tpp + NP * ((long long)B * N * 2 * D);
+    return N > 1024 ? launch_x6<64, 256, 32, 12, false>(tpp, gp, out, B, N, Np32, lse, s) : launch_x6<64, 256, 32, 4, false>(tpp, gp, out, B, N, Np32, lse, s);
+}

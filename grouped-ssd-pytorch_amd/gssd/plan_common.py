@@ -35,6 +35,17 @@ FUSE_PACK = os.environ.get('GSSD_FUSE_PACK', '1') != '0'
 # the o conv of Self_Attn-base 0 in a no-backward fp32 plan writes its two outputs straight into the per-group concatenation the DCN reads
 # (csrc/conv_x6.hip, GSSD_CONV_OUT_GROUPCAT): no gssd_slice_and_cat_f32 launch; GSSD_FUSE_CAT=0 keeps the copy pass
 FUSE_CAT = os.environ.get('GSSD_FUSE_CAT', '1') != '0'
+# the merged theta | phi | g projection of a 38 x 38 Self_Attn block in a no-backward fp32 plan stores the attention core's bf16 planes itself
+# (csrc/conv_x6.hip, GSSD_CONV_OUT_X6PLANES) and the core runs its second pass only (gssd_self_attn_core_x6_planes_f32): no split_planes
+# launches, no fp32 theta | phi / g^T arrays; GSSD_FUSE_SPLIT=0 keeps the two-pass entry
+FUSE_SPLIT = os.environ.get('GSSD_FUSE_SPLIT', '1') != '0'
+# conv4_3's BatchNorm + ReLU pass of a no-backward fp32 plan with Self_Attn-base on: its two readers -- the block's projection (in_scale / in_shift)
+# and the residual read of the block's o conv (GSSD_CONV_RESID_XF, csrc/conv_x6.hip) -- apply it on read;
+# GSSD_FUSE_SA_BN=0 keeps the pass
+FUSE_SA_BN = os.environ.get('GSSD_FUSE_SA_BN', '1') != '0'
+# the BatchNorm + ReLU passes behind the fuse convs with <= 512 output channels of a no-backward fp32 plan: each one's only reader is its merged
+# loc | conf head conv, which applies it on read (in_scale / in_shift / in_pad); GSSD_FUSE_HEAD_BN=0 keeps the passes
+FUSE_HEAD_BN = os.environ.get('GSSD_FUSE_HEAD_BN', '1') != '0'
 SN_STREAM = 9               # stream id of the spectral-norm launch inside a captured graph
 ALL_STREAMS = -1            # _Step.wait value: join every forked stream before this step
 

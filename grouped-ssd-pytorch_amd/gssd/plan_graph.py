@@ -91,7 +91,7 @@ class PlanGraphMixin:
             # A conv whose only consumer is the next conv (no pool, not a multibox source) leaves its BatchNorm + ReLU to
             # that consumer, which applies scale/shift/ReLU on the fragments it reads: one HBM round trip less per layer
             # (737 MB for conv1_1).  Pooled layers and sources keep the separate BN + ReLU (+ pool) pass.
-            defer = (pool is None and not is_conv4_3)
+            defer = (pool is None and not is_conv4_3) or (is_conv4_3 and self._sa_base_reads_raw(H, conv.out_channels))
             cur, H, Cc, xf = self._conv_bn(f'vgg.{vi}', conv, bn, cur, H, Cc, g, relu=True, pool=pool, in_xf=xf,
                                            defer_bn=defer)
             vi += 3
@@ -101,7 +101,8 @@ class PlanGraphMixin:
             i += 1
             if is_conv4_3:
                 x43 = cur
-                cur, H, Cc, src0 = self._after_conv4_3(cur, H, Cc)
+                cur, H, Cc, src0 = self._after_conv4_3(cur, H, Cc, xf)
+                xf = None
         vi += 1   # pool5 module
         xf = None
         for li in range(2):                                 # conv6 (BN deferred into conv7), conv7
@@ -204,8 +205,18 @@ class PlanGraphMixin:
         self.steps[self._reduce_steps[0]].args[2] = loc.data_ptr()
         self.steps[self._reduce_steps[1]].args[2] = conf.data_ptr()
 
-    def _after_conv4_3(self, x, H, Cc):
-        """models/...group.py:261-298: [SA-base] -> [slice_and_cat] -> [DCN]* -> L2Norm -> [SA] -> fuse_11; pool4."""
+    def _sa_base_reads_raw(self, H, Cc):
+        """conv4_3 leaves its BatchNorm + ReLU to Self_Attn-base 0 (no backward, fp32): the activated map has two readers there, the block's
+        projection and the residual read of its o conv, and csrc/conv_x6.hip applies the transform on both reads -- when the engine hands it
+        both launches (plan_ops._sa_on_x6, the rule _self_attn itself uses; a descriptor the kernel then declines for another reason is an
+        error at plan build, never a silently untransformed read)."""
+        net = self.eng.net
+        return bool(plan_common.FUSE_SA_BN and getattr(self, 'nograd', False) and not self.bf16 and not self.want_maps
+                    and net.use_self_attention_base and Cc <= 512 and (Cc // 4) % 64 == 0 and all(self._sa_on_x6(H, Cc)))
+
+    def _after_conv4_3(self, x, H, Cc, xf=None):
+        """models/...group.py:261-298: [SA-base] -> [slice_and_cat] -> [DCN]* -> L2Norm -> [SA] -> fuse_11; pool4.  ``xf``: conv4_3's deferred
+        BatchNorm + ReLU (scale, shift, pad) when ``x`` is its raw map (_sa_base_reads_raw)."""
         net, B = self.eng.net, self.B
         attn_g, cat_g = None, 0
         if net.use_self_attention_base:
@@ -213,7 +224,7 @@ class PlanGraphMixin:
             cat_g = (net.groups_vgg if (plan_common.FUSE_CAT and getattr(self, 'nograd', False) and not self.bf16 and net.use_dcn
                                         and net.dcn_cat_sab) else 0)
             x, attn_g = self._self_attn('self_attn_base_list', 0, x, H, Cc, need_out2=bool(net.dcn_cat_sab), want_map=self.want_maps,
-                                        cat_groups=cat_g)
+                                        cat_groups=cat_g, in_xf=xf)
         if net.use_dcn:
             xin, Cin = x, Cc
             if net.dcn_cat_sab and cat_g and attn_g is None:
@@ -247,14 +258,21 @@ class PlanGraphMixin:
         downstream of the trunk reads a branch, so branch i is tagged with stream id i + 1: captured as a hipGraph the six branches
         run beside the trunk's continuation (on the small maps a kernel has 1..100 workgroups for 256 CUs)."""
         net = self.eng.net
+        xf = None
         prev, self._sid = getattr(self, '_sid', 0), sa_i + 1
         if net.use_self_attention:
             s, _ = self._self_attn('self_attn_list', sa_i, s, H, Cc, need_out2=False, want_map=self.want_maps)
         if net.use_fuseconv and net.batch_norm:
             conv, bn = getattr(net, f'fuse_{fuse}'), getattr(net, f'bn_fuse_{fuse}')
-            s, H, Cc, _ = self._conv_bn(f'fuse_{fuse}', conv, bn, s, H, Cc, 1, relu=True)
+            # no backward, fp32: the activated source has ONE reader, its head conv, which applies the BatchNorm + ReLU on read (zero padding
+            # through in_pad); self.sources then holds the RAW map.  fuse_21 (1024 channels: beyond the kernels' 512-entry tables) keeps its pass
+            defer = bool(plan_common.FUSE_HEAD_BN and getattr(self, 'nograd', False) and not self.bf16 and not self.want_maps
+                         and conv.out_channels <= 512)
+            s, H, Cc, xf = self._conv_bn(f'fuse_{fuse}', conv, bn, s, H, Cc, 1, relu=True, defer_bn=defer)
         elif net.use_fuseconv:
             s, H, Cc = self._conv_act(f'fuse_{fuse}', getattr(net, f'fuse_{fuse}'), s, H, Cc, 1)
-        self._head(sa_i, s, H, Cc)
+        self._head(sa_i, s, H, Cc, in_xf=xf)
         self._sid = prev
+        # (scale, shift, pad) where the source map is RAW (its BatchNorm + ReLU deferred to the head), else None: readers of plan.sources
+        self.__dict__.setdefault('sources_xf', {})[sa_i] = xf
         return (s, H, Cc)

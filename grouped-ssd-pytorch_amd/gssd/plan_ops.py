@@ -6,6 +6,7 @@ import os
 import torch
 from . import _lib, ops
 from ._lib import lib
+from . import plan_common
 from .plan_common import DCN_X6, HEAD_OFF, MBOX, SN_STREAM, USE_CONV_X6, USE_FLASH_X6, USE_HEADS_WINO, USE_PATCH_X6, USE_WINOGRAD
 
 
@@ -35,9 +36,10 @@ class PlanOpsMixin:
                                           stride=s, pad=p, dil=dl, groups=groups)))
         return out, Ho, Cout
 
-    def _head(self, i, s, Hs, Cs):
+    def _head(self, i, s, Hs, Cs, in_xf=None):
         """loc[i] / conf[i] (models/...group.py:375-380) as ONE merged 3x3 conv writing straight into the concatenated fp32
-        loc [B,8732,4] / conf [B,8732,C] at this source's prior offset."""
+        loc [B,8732,4] / conf [B,8732,C] at this source's prior offset.  ``in_xf`` = (scale, shift, pad) of the fuse conv's deferred
+        BatchNorm + ReLU when ``s`` is its raw map."""
         eng, net, B, dev, f32 = self.eng, self.eng.net, self.B, self.dev, torch.float32
         off = HEAD_OFF[i]
         A = MBOX[i]
@@ -76,6 +78,8 @@ class PlanOpsMixin:
                                      pad=1, bias=bp, out_mode=_lib.OUT_HEADS, out_b=None, split_n=nloc,
                                      out_batch_stride=self.P * 4, outb_batch_stride=self.P * self.nc,
                                      out_off=off * 4, outb_off=off * self.nc, split_k=split, wgt_wino=U,
+                                     in_scale=in_xf[0] if in_xf else None, in_shift=in_xf[1] if in_xf else None,
+                                     in_pad=in_xf[2] if in_xf else None,
                                      flags=_lib.CONV_OUT_F32 | (self.f16_ok if U is not None else 0))
         self.head_descs.append(d)
         self._add(self.conv_fn, (C.byref(d),), keep=d)
@@ -221,13 +225,23 @@ class PlanOpsMixin:
         self.rec.append(('pool', dict(x_in=x, out=out, H=H, C=Cc, k=k, s=s, p=p, Hp=Hp)))
         return out, Hp
 
-    def _self_attn(self, lst_name, idx, x, H, Cc, need_out2, want_map=False, cat_groups=0):
+    def _sa_on_x6(self, H, Cc):
+        """(projection, o conv): which of a Self_Attn block's two GEMMs the engine hands to csrc/conv_x6.hip -- the ONE statement of the shape rules,
+        read by _self_attn and by plan_graph._sa_base_reads_raw."""
+        M, C4, C2 = self.B * H * H, Cc // 4, Cc // 2
+        on = not self.bf16 and USE_CONV_X6
+        return (bool(on and ops.x6_wanted(1, Cc, C4 + C2, 1, M) and C4 % ops.x6_tile(C4 + C2, 1, M) == 0),
+                bool(on and ops.x6_wanted(1, C2, Cc, 1, M)))
+
+    def _self_attn(self, lst_name, idx, x, H, Cc, need_out2, want_map=False, cat_groups=0, in_xf=None):
         """layers/self_attn.py:46-89 as three launches: ONE pass over x for the theta | phi | g projections (K9; g written
         transposed), the flash-style core theta^T phi -> softmax -> . g (K10, csrc/flash_attn.hip: the [N, N] map never exists),
         and the o conv with the sigma-gated residual epilogue.  ``want_map`` (visualize=True, op-level tests) additionally
         materialises the attention map with two extra launches; the output path does not read it.  ``cat_groups`` > 0 (with need_out2): the
         caller's only use of the two outputs is slice_and_cat over that many groups; when csrc/conv_x6.hip takes the o conv with the
-        grouped destination remap the block writes the concatenation itself and returns (xc [B,H,H,2C], None)."""
+        grouped destination remap the block writes the concatenation itself and returns (xc [B,H,H,2C], None).  ``in_xf`` = (scale, shift,
+        pad): ``x`` is its producer's RAW map (conv4_3, plan_graph._sa_base_reads_raw) and both readers -- the projection and the o conv's
+        residual (GSSD_CONV_RESID_XF) -- apply the deferred BatchNorm + ReLU on read; csrc/conv_x6.hip must take both launches."""
         eng, B = self.eng, self.B
         sa = getattr(eng.net, lst_name)[idx]
         a_tpg, a_o = self.sa_state[(lst_name, idx)]
@@ -264,12 +278,8 @@ class PlanOpsMixin:
         b_tpg = eng._pack(name + '.tpg.b', build_b)
         # the o conv's weight is already K-major rows; bf16 mode keeps a rounded copy
         w_o = eng._pack(name + '.o.w', build_wo) if self.bf16 else sa.snconv1x1_attn.weight_orig.detach().view(Cc, C2)
-        tp = self._buf(B, N, C4)               # theta | phi stay fp32 in both modes: the logits and the softmax are fp32
         if self.bf16:                          # g^T bf16, rows in the key order of the bf16-value core (csrc/flash_attn.hip)
             Np = ops.round_up(N, 32)
-            gT = self._abuf(B, C2, Np)
-        else:
-            gT = self._buf(B, C2, Np)
         ag = self._abuf(B, N, C2)
         out = self._abuf(B, H, H, Cc)
         out2 = self._abuf(B, H, H, Cc) if need_out2 else None
@@ -277,30 +287,54 @@ class PlanOpsMixin:
         # fp32, N % 4 == 0 (38 x 38): all images as ONE M range -- 361 full row tiles instead of 12 per image with a ragged last one,
         # and the plain-GEMM dispatch (slot stream) instead of the per-image one
         flat = not self.bf16 and N % 4 == 0 and Np == N
+        xin = dict(in_scale=in_xf[0], in_shift=in_xf[1], in_pad=in_xf[2]) if in_xf else {}
+        rxf = _lib.CONV_RESID_XF if in_xf else 0       # the o conv: in_scale / in_shift are its RESIDUAL's (include/gssd_hip.h)
+        tpg_on_x6, o_on_x6 = self._sa_on_x6(H, Cc)
         x6_tpg = None
-        if (not self.bf16 and USE_CONV_X6 and ops.x6_wanted(1, Cc, C4 + C2, 1, B * N) and C4 % ops.x6_tile(C4 + C2, 1, B * N) == 0):
+        if tpg_on_x6:
             def build_x6p(out, key=name + '.tpg.w', bn=ops.x6_tile(C4 + C2, 1, B * N)):
                 return ops.x6_weight(eng._packed[key], 1, Cc, 1, bn, out)
             x6_tpg = eng._pack(name + f'.tpg.x6@{ops.x6_tile(C4 + C2, 1, B * N)}', build_x6p)
-            gT.zero_()                         # csrc/conv_x6.hip never writes the row tails [N, Np) of g^T (conv_igemm zero-fills them)
-        d1, _, _ = mk(x, w_tpg, tp, B=B, H=H, W=H, in_stride=Cc, cin_g=Cc, Cout=C4 + C2, bias=b_tpg, alpha=a_tpg, wgt_x6=x6_tpg,
-                      out_mode=_lib.OUT_SPLIT_T, out_b=gT, split_n=C4, out_stride=C4, out_b_stride=Np, m_per_image=not flat,
-                      in_batch_stride=N * Cc, out_batch_stride=N * C4, outb_batch_stride=C2 * Np,
-                      flags=_lib.CONV_OUT_F32 | (_lib.CONV_OUTB_BF16_PERM32 if self.bf16 else self.f16_ok))
+        # No backward, fp32, the three-plane core (38 x 38 blocks): the projection's epilogue writes the core's bf16 planes itself where
+        # csrc/conv_x6.hip takes the flagged descriptor (GSSD_CONV_OUT_X6PLANES) -- no split pass, and the fp32 theta | phi / g^T arrays do not
+        # exist (the record's tp / gT are None).  GSSD_FUSE_SPLIT=0, want_map (its logits GEMM reads the fp32 theta | phi), pooled keys and the
+        # opt-in fp16-plane core keep the two-pass entry.
+        d1 = ws_planes = tp = gT = None
+        if (plan_common.FUSE_SPLIT and getattr(self, 'nograd', False) and not want_map and x6_tpg is not None and flat and C4 % 64 == 0
+                and max(H // int(sa.max_pool_factor), 1) == H and USE_FLASH_X6 and N >= 1024 and C8 == 64
+                and lib.gssd_self_attn_core_x6_supported(C8, C2) and os.environ.get('GSSD_FLASH_X6_F16', '0') != '1'):
+            Np32 = ops.round_up(N, 32)
+            ws = torch.zeros(int(lib.gssd_self_attn_core_x6_ws_bytes(B, N, C8, C2)) // 2, device=dev, dtype=torch.int16)   # (the key columns [N, Np32) stay zero)
+            dp, _, _ = mk(x, w_tpg, ws, B=B, H=H, W=H, in_stride=Cc, cin_g=Cc, Cout=C4 + C2, bias=b_tpg, alpha=a_tpg, wgt_x6=x6_tpg,
+                          out_mode=_lib.OUT_SPLIT_T, out_b=ws[3 * B * N * C4:], split_n=C4, out_stride=C4, out_b_stride=Np32,
+                          in_batch_stride=N * Cc, out_batch_stride=N * C4, outb_batch_stride=C2 * Np32,
+                          flags=_lib.CONV_OUT_F32 | self.f16_ok | _lib.CONV_OUT_X6PLANES, **xin)
+            if lib.gssd_conv_x6_takes(C.byref(dp)) == 1:
+                d1, ws_planes = dp, ws
+                self.bufs.append(ws)
+        if d1 is None:
+            tp = self._buf(B, N, C4)           # theta | phi stay fp32 in both modes: the logits and the softmax are fp32
+            gT = self._abuf(B, C2, Np) if self.bf16 else self._buf(B, C2, Np)
+            if x6_tpg is not None:
+                gT.zero_()                     # csrc/conv_x6.hip never writes the row tails [N, Np) of g^T (conv_igemm zero-fills them)
+            d1, _, _ = mk(x, w_tpg, tp, B=B, H=H, W=H, in_stride=Cc, cin_g=Cc, Cout=C4 + C2, bias=b_tpg, alpha=a_tpg, wgt_x6=x6_tpg,
+                          out_mode=_lib.OUT_SPLIT_T, out_b=gT, split_n=C4, out_stride=C4, out_b_stride=Np, m_per_image=not flat,
+                          in_batch_stride=N * Cc, out_batch_stride=N * C4, outb_batch_stride=C2 * Np,
+                          flags=_lib.CONV_OUT_F32 | (_lib.CONV_OUTB_BF16_PERM32 if self.bf16 else self.f16_ok), **xin)
         x6_o = None
-        if not self.bf16 and USE_CONV_X6 and ops.x6_wanted(1, C2, Cc, 1, B * N):
+        if o_on_x6:
             def build_x6o(out, bn=ops.x6_tile(Cc, 1, B * N)):
                 return ops.x6_weight(sa.snconv1x1_attn.weight_orig.detach().view(Cc, C2), 1, C2, 1, bn, out)
             x6_o = eng._pack(name + f'.o.x6@{ops.x6_tile(Cc, 1, B * N)}', build_x6o)
         d5, _, _ = mk(ag, w_o, out, B=B, H=H, W=H, in_stride=C2, cin_g=C2, Cout=Cc, bias=sa.snconv1x1_attn.bias.detach(),
-                      alpha=a_o, gate=sa.sigma.detach(), resid=x, out2=out2, wgt_x6=x6_o, flags=self.f16_ok)
+                      alpha=a_o, gate=sa.sigma.detach(), resid=x, out2=out2, wgt_x6=x6_o, flags=self.f16_ok | rxf, **xin)
         xc = None
         if cat_groups and need_out2 and x6_o is not None and Cc % cat_groups == 0:
             ga = Cc // cat_groups
             xc = self._abuf(B, H, H, 2 * Cc)
             dc, _, _ = mk(ag, w_o, xc, B=B, H=H, W=H, in_stride=C2, cin_g=C2, Cout=Cc, bias=sa.snconv1x1_attn.bias.detach(),
                           alpha=a_o, gate=sa.sigma.detach(), resid=x, out2=xc.view(-1)[ga:], wgt_x6=x6_o, out_stride=2 * Cc, split_n=ga,
-                          flags=self.f16_ok | _lib.CONV_OUT_GROUPCAT)
+                          flags=self.f16_ok | _lib.CONV_OUT_GROUPCAT | rxf, **xin)
             if lib.gssd_conv_x6_takes(C.byref(dc)) == 1:
                 d5 = dc
                 self.bufs[:] = [t for t in self.bufs if t is not out and t is not out2]      # the separate maps are never written
@@ -310,6 +344,8 @@ class PlanOpsMixin:
                 self.bufs[:] = [t for t in self.bufs if t is not xc]
                 xc = None
         fn = self.conv_fn
+        if in_xf and (want_map or C4 % 64 != 0 or lib.gssd_conv_x6_takes(C.byref(d1)) != 1 or lib.gssd_conv_x6_takes(C.byref(d5)) != 1):
+            raise _lib.GssdError(f'{name}: the block was handed a raw input map, but csrc/conv_x6.hip does not take its projection and o conv')
         if C4 % 64 == 0:
             self._add(fn, (C.byref(d1),), keep=(d1, w_tpg, b_tpg))
         else:
@@ -342,6 +378,10 @@ class PlanOpsMixin:
             self._add(lib.gssd_self_attn_core_bf16v, (tp.data_ptr(), gT.data_ptr(), ag.data_ptr(), B, N, Np, C8, C2,
                                                       lse.data_ptr() if lse is not None else 0),
                       tag=(f'flash_attn_bf16v<{C8},{C2}>', 2.0 * B * N * N * (C8 + C2), B * (4.0 * N * C4 + 2.0 * C2 * Np + 2.0 * N * C2)))
+        elif ws_planes is not None:
+            self._add(lib.gssd_self_attn_core_x6_planes_f32, (ws_planes.data_ptr(), ag.data_ptr(), B, N, C8, C2,
+                                                              lse.data_ptr() if lse is not None else 0),
+                      tag=(f'flash_attn_x6<{C8},{C2}>', 2.0 * B * N * N * (C8 + C2), 2.0 * 3 * B * (N * C4 + C2 * Np) + 4.0 * B * N * C2))
         elif USE_FLASH_X6 and N >= 1024 and C8 == 64 and lib.gssd_self_attn_core_x6_supported(C8, C2):
             # both products of the core on the bf16 matrix cores over three-plane operands (csrc/flash_attn_x6.hip): fp32-equivalent results at
             # 6 / 16 of the fp32 instruction's matrix-pipe time; the planes of theta | phi and g^T live in a scratch buffer of the plan

@@ -218,6 +218,25 @@ int gssd_conv_x6_takes(const gssd_conv_desc* d);
  * values as the separate outputs, bit for bit.  Only csrc/conv_x6.hip has the epilogue (gssd_conv_x6_takes() tells); any other descriptor
  * with the flag returns GSSD_EINVAL. */
 #define GSSD_CONV_OUT_GROUPCAT 128
+/* fp32 entry point, GSSD_OUT_SPLIT_T (the merged Self_Attn projection), one conv group: the epilogue stores the three bf16 planes the
+ * three-plane attention core reads (csrc/flash_attn_x6.hip) instead of the fp32 arrays -- what the first pass of gssd_self_attn_core_x6_f32 would
+ * make of them, bit for bit (same value expression, same split).  `out` points to the theta | phi planes [3][B * Ho * Wo][split_n] (bf16;
+ * out_stride == split_n), `out_b` to the g^T planes [3][B][Cout - split_n][out_b_stride] (bf16; out_b_stride a multiple of 32 >= Ho * Wo;
+ * outb_batch_stride == (Cout - split_n) * out_b_stride) with the keys of every 32-block of an image in the order of the value product (slot
+ * 8 q + e holds key 16 (e >> 2) + 4 q + (e & 3)): a workspace of gssd_self_attn_core_x6_ws_bytes(B, Ho * Wo, split_n / 2, Cout - split_n) bytes is
+ * exactly `out` followed by `out_b`.  The key columns [Ho * Wo, out_b_stride) are NOT written: the caller zero-fills them once.  Ho * Wo must be a
+ * multiple of 4; no ReLU / batch sums / gate / residual.  gssd_self_attn_core_x6_planes_f32 then runs the core on the workspace.  Only
+ * csrc/conv_x6.hip has the epilogue (gssd_conv_x6_takes() tells); any other descriptor with the flag returns GSSD_EINVAL. */
+#define GSSD_CONV_OUT_X6PLANES 256
+/* fp32 entry point, GSSD_OUT_NHWC with a residual: in_scale / in_shift (and in_pad, which is not read) describe the deferred BatchNorm + ReLU of the
+ * RESIDUAL's producer, not of `in` -- `resid` is that producer's RAW map and is read as max(r*in_scale[c] + in_shift[c], 0), c = the output channel;
+ * `in` is read plain.  Self_Attn-base 0 behind conv4_3 in a plan no backward reads: the block's projection applies the same transform to its input
+ * the usual way, the o conv -- whose own input, the attention output, never has a deferred BatchNorm -- applies it to the residual, and the
+ * stand-alone BatchNorm + ReLU pass over conv4_3's output disappears.  The expression is the one the fused input transform and
+ * gssd_bn_relu_pool_f32 use: the transformed residual equals the activated map bit for bit.  Works with GSSD_CONV_OUT_GROUPCAT.  out_ch_off == 0.
+ * Only csrc/conv_x6.hip has the epilogue (gssd_conv_x6_takes() tells); any other descriptor with the flag returns GSSD_EINVAL.
+ * (A flag rather than new descriptor fields: the struct's layout is part of the ABI.) */
+#define GSSD_CONV_RESID_XF 512
 int gssd_conv2d_nhwc_bf16(const gssd_conv_desc* d, gssd_stream_t stream);
 /* OIHW fp32 -> packed bf16 rows [Cout][Kpad] (cin_g_pad, Kpad multiples of 8); fp32 -> bf16 array cast (round to nearest even) */
 int gssd_pack_conv_weight_bf16(const float* w_oihw, void* w_packed, int Cout, int cin_g, int KH, int KW, int cin_g_pad, int Kpad,
@@ -807,6 +826,9 @@ int gssd_self_attn_core_x6_supported(int D, int C2);
 long long gssd_self_attn_core_x6_ws_bytes(int B, int N, int D, int C2);
 int gssd_self_attn_core_x6_f32(const float* tp, const float* gT, float* out, int B, int N, int Np, int D, int C2, void* ws, float* lse,
                                gssd_stream_t stream);
+/* The second pass alone: `ws` already holds the planes (written by the projection's GSSD_CONV_OUT_X6PLANES epilogue, the key columns
+ * [N, round_up(N, 32)) of the g^T planes zero).  Three bf16 planes only (GSSD_FLASH_X6_F16 does not apply). */
+int gssd_self_attn_core_x6_planes_f32(const void* ws, float* out, int B, int N, int D, int C2, float* lse, gssd_stream_t stream);
 
 /* ---- launch-plan runner (csrc/plan_run.hip) ----------------------------------------------------------------------------------------------
  * The host side of the reference enqueues one kernel per Python call (nn.Module.__call__ -> ATen, train_lesion_multiphase_v2.py:242-253);

@@ -41,4 +41,7 @@ for kind, r in plan.rec:
         print('l2norm', rel(nchw(r['out']), taps['l2norm']))
 print('sab0.out', rel(nchw([r for k, r in plan.rec if k == 'sa'][0]['out']), taps['sab0.out']))
 for i, (s, H, C) in enumerate(plan.sources):
+    xf = getattr(plan, 'sources_xf', {}).get(i)      # no-backward fp32 plans keep RAW fuse maps (BatchNorm + ReLU applied by the head conv)
+    if xf is not None:
+        s = torch.relu(s * xf[0] + xf[1])
     print('source', i, rel(nchw(s), taps[f'source{i}']))

@@ -134,6 +134,7 @@ SIGNATURES = {
     'gssd_conv_flat_bf16_takes': (c_i, [c_fp]),
     'gssd_conv_flat_bf16_tile': (c_i, [c_i]),
     'gssd_heads_reduce_f32': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
+    'gssd_heads_reduce2_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     'gssd_interp_add_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp]),
     'gssd_pixellink_final_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp]),
     'gssd_pixellink_loss_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp]),
@@ -205,6 +206,9 @@ SIGNATURES = {
     'gssd_reduce_max_f32': (c_i, [c_fp, c_i64, c_fp, c_i, c_fp]),
     'gssd_hnm_loss': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
     'gssd_loss_finalize': (c_i, [c_fp, c_i, c_fp, c_fp, c_fp]),
+    'gssd_multibox_loss_workspace_bytes': (C.c_longlong, [c_i]),
+    'gssd_multibox_loss_forward_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_fp, c_fp, c_fp, c_fp,
+                                             c_fp, c_fp, c_fp, c_fp, C.c_longlong, c_fp]),
     'gssd_loss_finalize_global': (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp]),
     'gssd_loss_backward': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     'gssd_detect': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),

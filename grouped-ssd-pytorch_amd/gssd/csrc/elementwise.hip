@@ -429,6 +429,50 @@ __global__ __launch_bounds__(256) void heads_reduce_kernel(const float* __restri
     }
 }
 
+// Both heads in one grid: workgroups [0, blocks_loc) reduce loc (4 floats per prior), the rest conf (C per prior).  One thread per
+// (image, prior) row, the row read as one vector per slice when C is 4 or 2; every element is summed as heads_reduce_kernel sums it
+// (a = ws[0]; a += ws[k], k ascending), so the bits are the same.
+template <int CV>
+__device__ __forceinline__ void heads_reduce_rows(const float* __restrict__ ws, const signed char* __restrict__ splits,
+                                                  float* __restrict__ out, int rows, int P, int C, int block, int nblocks) {
+    const size_t total = (size_t)rows * C;
+    for (int r = block * 256 + threadIdx.x; r < rows; r += nblocks * 256) {
+        const int n = splits[r % P];
+        if constexpr (CV == 4) {
+            float4 a = reinterpret_cast<const float4*>(ws)[r];
+            for (int k = 1; k < n; ++k) {
+                const float4 t = reinterpret_cast<const float4*>(ws + (size_t)k * total)[r];
+                a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
+            }
+            reinterpret_cast<float4*>(out)[r] = a;
+        } else if constexpr (CV == 2) {
+            float2 a = reinterpret_cast<const float2*>(ws)[r];
+            for (int k = 1; k < n; ++k) {
+                const float2 t = reinterpret_cast<const float2*>(ws + (size_t)k * total)[r];
+                a.x += t.x; a.y += t.y;
+            }
+            reinterpret_cast<float2*>(out)[r] = a;
+        } else {
+            for (int c = 0; c < C; ++c) {
+                const size_t i = (size_t)r * C + c;
+                float a = ws[i];
+                for (int k = 1; k < n; ++k) a += ws[(size_t)k * total + i];
+                out[i] = a;
+            }
+        }
+    }
+}
+
+template <int CV>   // CV: the conf rows' vector width (4, 2, or 0 = scalar); loc rows are float4
+__global__ __launch_bounds__(256) void heads_reduce2_kernel(const float* __restrict__ ws_loc, const float* __restrict__ ws_conf,
+                                                           const signed char* __restrict__ splits, float* __restrict__ loc,
+                                                           float* __restrict__ conf, int rows, int P, int C, int blocks_loc) {
+    if ((int)blockIdx.x < blocks_loc)
+        heads_reduce_rows<4>(ws_loc, splits, loc, rows, P, 4, blockIdx.x, blocks_loc);
+    else
+        heads_reduce_rows<CV>(ws_conf, splits, conf, rows, P, C, blockIdx.x - blocks_loc, gridDim.x - blocks_loc);
+}
+
 }  // namespace
 
 extern "C" int gssd_pack_input_nhwc(const float* x, float* y, int B, int C, int H, int W, int groups, int cpg_out,
@@ -556,6 +600,27 @@ extern "C" int gssd_heads_reduce_f32(const float* ws, const signed char* splits,
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(heads_reduce_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), ws, splits, out, total, P, C);
+    GSSD_CHECK_LAUNCH();
+    return GSSD_OK;
+}
+
+extern "C" int gssd_heads_reduce2_f32(const float* ws_loc, const float* ws_conf, const signed char* splits, float* loc, float* conf, int B,
+                                      int P, int C, gssd_stream_t stream) {
+    GSSD_CHECK_ARG(ws_loc && ws_conf && splits && loc && conf && B > 0 && P > 0 && C > 0);
+    GSSD_CHECK_ARG((long long)B * P < (1ll << 30));
+    GSSD_CHECK_ARG(((uintptr_t)ws_loc % 16) == 0 && ((uintptr_t)loc % 16) == 0);
+    const int rows = B * P;
+    int blocks = (rows + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    // the conf rows travel as vectors where every slice of them is aligned for it (slices are B * P * C floats apart)
+    const uintptr_t ca = (uintptr_t)ws_conf | (uintptr_t)conf | (uintptr_t)((size_t)rows * C * sizeof(float));
+    const dim3 grid(2 * blocks), block(256);
+    if (C == 4 && ca % 16 == 0)
+        hipLaunchKernelGGL(heads_reduce2_kernel<4>, grid, block, 0, as_stream(stream), ws_loc, ws_conf, splits, loc, conf, rows, P, C, blocks);
+    else if (C == 2 && ca % 8 == 0)
+        hipLaunchKernelGGL(heads_reduce2_kernel<2>, grid, block, 0, as_stream(stream), ws_loc, ws_conf, splits, loc, conf, rows, P, C, blocks);
+    else
+        hipLaunchKernelGGL(heads_reduce2_kernel<0>, grid, block, 0, as_stream(stream), ws_loc, ws_conf, splits, loc, conf, rows, P, C, blocks);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }

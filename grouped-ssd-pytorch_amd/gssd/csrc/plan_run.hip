@@ -147,6 +147,7 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_reduce_max_f32),
     GSSD_PLAN_FN(gssd_hnm_loss),
     GSSD_PLAN_FN(gssd_loss_finalize),
+    GSSD_PLAN_FN(gssd_multibox_loss_forward_f32),
     GSSD_PLAN_FN(gssd_loss_finalize_global),
     GSSD_PLAN_FN(gssd_loss_backward),
     GSSD_PLAN_FN(gssd_detect),
@@ -154,6 +155,7 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_eval_match),
     GSSD_PLAN_FN(gssd_eval_ap),
     GSSD_PLAN_FN(gssd_heads_reduce_f32),
+    GSSD_PLAN_FN(gssd_heads_reduce2_f32),
     GSSD_PLAN_FN(gssd_interp_add_f32),
     GSSD_PLAN_FN(gssd_pixellink_final_f32),
     GSSD_PLAN_FN(gssd_pixellink_loss_f32),

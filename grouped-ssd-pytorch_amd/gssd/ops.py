@@ -483,29 +483,57 @@ def match_batch(tg, gt_off, priors, threshold=0.5, variance=(0.1, 0.2)):
     return loc_t, conf_t
 
 
+# GSSD_FUSE_LOSS=0: MultiBoxLoss's forward as the four launches match / reduce_max / hnm_loss / loss_finalize instead of the two of
+# gssd_multibox_loss_forward_f32 (the same bits: A-B in the same build)
+FUSE_LOSS = os.environ.get('GSSD_FUSE_LOSS', '1') != '0'
+_loss_ws = {}        # (device, stream) -> the fused entry's workspace: zeroed once, its ticket is left zero by every call
+
+
+def _loss_workspace(dev, B):
+    """One workspace per (device, stream): calls on one stream run one after the other, which is what its ticket needs."""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), _stream())
+    need = int(lib.gssd_multibox_loss_workspace_bytes(B))
+    if torch.cuda.is_current_stream_capturing():       # a captured call owns its workspace: the zeroing is a node of that graph
+        return torch.zeros(max(need, 4096), device=dev, dtype=torch.uint8)
+    ws = _loss_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _loss_ws[key] = torch.zeros(max(need, 4096), device=dev, dtype=torch.uint8)
+    return ws
+
+
 def multibox_loss_forward(loc, conf, priors, tg, n_gt, threshold=0.5, negpos_ratio=3, variance=(0.1, 0.2),
-                          want_scores=False, global_n=False):
+                          want_scores=False, global_n=False, fused=None):
     """Returns dict(losses[2], loc_t, conf_t, sel, n_total, loss_c_all?).  ``global_n``: the normaliser N of multibox_loss.py:117 over every
-    rank's images (one all-reduce of one double) instead of this rank's -- SURVEY.md 8e's exact equivalence to the single big batch."""
+    rank's images (one all-reduce of one double) instead of this rank's -- SURVEY.md 8e's exact equivalence to the single big batch.
+    ``fused``: True = the two launches of gssd_multibox_loss_forward_f32, False = the four separate ones, None = GSSD_FUSE_LOSS."""
     _need_cuda(loc, conf, priors)
     loc = loc.contiguous()
     conf = conf.contiguous()
     B, P, _ = loc.shape
     Cc = conf.shape[-1]
     priors = priors[:P].contiguous()
-    loc_t, conf_t = match_batch(tg, n_gt, priors, threshold, variance)
     dev = loc.device
-    NX = 128
-    xmax = torch.empty(NX, device=dev, dtype=torch.float32)
-    check(lib.gssd_reduce_max_f32(_p(conf), conf.numel(), _p(xmax), NX, _stream()))
     sel = torch.empty(B, P, device=dev, dtype=torch.uint8)
     partial = torch.empty(B, 4, device=dev, dtype=torch.float64)
     lca = torch.empty(B, P, device=dev, dtype=torch.float32) if want_scores else None
-    check(lib.gssd_hnm_loss(_p(loc), _p(conf), _p(loc_t), _p(conf_t), _p(xmax), NX, B, P, Cc, int(negpos_ratio), _p(sel),
-                            _p(partial), _p(lca), _stream()))
     losses = torch.empty(2, device=dev, dtype=torch.float32)
     n_total = torch.empty(1, device=dev, dtype=torch.float64)
-    check(lib.gssd_loss_finalize(_p(partial), B, _p(losses), _p(n_total), _stream()))
+    if FUSE_LOSS if fused is None else fused:
+        _need_cuda(tg, n_gt)
+        loc_t = torch.empty(B, P, 4, device=dev, dtype=torch.float32)
+        conf_t = torch.empty(B, P, device=dev, dtype=torch.int64)
+        ws = _loss_workspace(dev, B)
+        check(lib.gssd_multibox_loss_forward_f32(_p(loc), _p(conf), _p(priors), _p(tg), _p(n_gt), B, P, Cc, threshold, variance[0],
+                                                 variance[1], int(negpos_ratio), _p(loc_t), _p(conf_t), _p(sel), _p(partial),
+                                                 _p(losses), _p(n_total), _p(lca), _p(ws), ws.numel(), _stream()))
+    else:
+        loc_t, conf_t = match_batch(tg, n_gt, priors, threshold, variance)
+        NX = 128
+        xmax = torch.empty(NX, device=dev, dtype=torch.float32)
+        check(lib.gssd_reduce_max_f32(_p(conf), conf.numel(), _p(xmax), NX, _stream()))
+        check(lib.gssd_hnm_loss(_p(loc), _p(conf), _p(loc_t), _p(conf_t), _p(xmax), NX, B, P, Cc, int(negpos_ratio), _p(sel),
+                                _p(partial), _p(lca), _stream()))
+        check(lib.gssd_loss_finalize(_p(partial), B, _p(losses), _p(n_total), _stream()))
     if global_n:
         import torch.distributed as dist
         if dist.is_initialized() and dist.get_world_size() > 1:

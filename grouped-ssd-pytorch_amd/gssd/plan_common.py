@@ -46,6 +46,9 @@ FUSE_SA_BN = os.environ.get('GSSD_FUSE_SA_BN', '1') != '0'
 # the BatchNorm + ReLU passes behind the fuse convs with <= 512 output channels of a no-backward fp32 plan: each one's only reader is its merged
 # loc | conf head conv, which applies it on read (in_scale / in_shift / in_pad); GSSD_FUSE_HEAD_BN=0 keeps the passes
 FUSE_HEAD_BN = os.environ.get('GSSD_FUSE_HEAD_BN', '1') != '0'
+# the split-K slices of the loc and the conf heads are added by ONE launch (csrc/elementwise.hip, gssd_heads_reduce2_f32: the same sums in the
+# same order); GSSD_FUSE_HEADS_REDUCE=0 keeps one gssd_heads_reduce_f32 launch per head
+FUSE_HEADS_REDUCE = os.environ.get('GSSD_FUSE_HEADS_REDUCE', '1') != '0'
 SN_STREAM = 9               # stream id of the spectral-norm launch inside a captured graph
 ALL_STREAMS = -1            # _Step.wait value: join every forked stream before this step
 

@@ -176,7 +176,7 @@ class PlanGraphMixin:
 
     def _finish_heads(self):
         """Deterministic split-K for the heads: every reduction slice of a head conv writes its partial sums to its own copy of the
-        outputs (GSSD_CONV_HEADS_SLICES); two launches then add the slices of every prior in order into loc / conf.  (With fp32
+        outputs (GSSD_CONV_HEADS_SLICES); one launch (two with GSSD_FUSE_HEADS_REDUCE=0) then adds the slices of every prior in order into loc / conf.  (With fp32
         atomics loc / conf -- and with them Detect's index output -- differed in their last bits from run to run.)"""
         B, dev = self.B, self.dev
         smax = max(d.split_k for d in self.head_descs)
@@ -196,12 +196,20 @@ class PlanGraphMixin:
             d.flags |= _lib.CONV_HEADS_SLICES
         prev, self._sid = getattr(self, '_sid', 0), 0
         self._pending_wait = ALL_STREAMS                      # the heads run on the branch streams: join them all first
-        self._reduce_steps = (len(self.steps), len(self.steps) + 1)
-        self._add(lib.gssd_heads_reduce_f32, [self._ws_loc.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, 4])
-        self._add(lib.gssd_heads_reduce_f32, [self._ws_conf.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, self.nc])
+        if plan_common.FUSE_HEADS_REDUCE:                     # one launch for both heads (GSSD_FUSE_HEADS_REDUCE=0: one each)
+            self._reduce_steps = (len(self.steps),)
+            self._add(lib.gssd_heads_reduce2_f32, [self._ws_loc.data_ptr(), self._ws_conf.data_ptr(), self._head_splits.data_ptr(), 0, 0,
+                                                   B, self.P, self.nc])
+        else:
+            self._reduce_steps = (len(self.steps), len(self.steps) + 1)
+            self._add(lib.gssd_heads_reduce_f32, [self._ws_loc.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, 4])
+            self._add(lib.gssd_heads_reduce_f32, [self._ws_conf.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, self.nc])
         self._sid = prev
 
     def _set_outputs(self, loc, conf):
+        if len(self._reduce_steps) == 1:
+            self.steps[self._reduce_steps[0]].args[3:5] = [loc.data_ptr(), conf.data_ptr()]
+            return
         self.steps[self._reduce_steps[0]].args[2] = loc.data_ptr()
         self.steps[self._reduce_steps[1]].args[2] = conf.data_ptr()
 

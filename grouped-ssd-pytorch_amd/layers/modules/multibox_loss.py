@@ -5,8 +5,10 @@ tuple ``(loc [B,P,4], conf [B,P,C], priors [>=P,4])``, ``targets`` a python list
 returns ``(loss_l, loss_c)`` 0-dim tensors with gradients to ``loc`` / ``conf``.
 
 The reference's per-image Python matching loop with a D2H copy per image (:67-75) and the two full
-sorts of [B, 8732] (:101-102) become three HIP launches for the whole batch (gssd_match_batch,
-gssd_hnm_loss, gssd_loss_finalize); nothing synchronises with the host."""
+sorts of [B, 8732] (:101-102) become two HIP launches for the whole batch
+(gssd_multibox_loss_forward_f32; ``fused = False`` or GSSD_FUSE_LOSS=0: the four separate launches
+gssd_match_batch, gssd_reduce_max_f32, gssd_hnm_loss, gssd_loss_finalize, same bits); nothing
+synchronises with the host."""
 import torch
 import torch.nn as nn
 
@@ -16,9 +18,9 @@ from data.config import v2 as cfg
 
 class _MultiBoxLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loc, conf, priors, tg, n_gt, threshold, negpos_ratio, variance, global_n=False):
+    def forward(ctx, loc, conf, priors, tg, n_gt, threshold, negpos_ratio, variance, global_n=False, fused=None):
         st = ops.multibox_loss_forward(loc.detach(), conf.detach(), priors, tg, n_gt, threshold, negpos_ratio,
-                                       variance, global_n=global_n)
+                                       variance, global_n=global_n, fused=fused)
         ctx.st = st
         losses = st['losses']
         return losses[0], losses[1]
@@ -26,7 +28,7 @@ class _MultiBoxLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_l, g_c):
         dloc, dconf = ops.multibox_loss_backward(ctx.st, g_l, g_c)
-        return dloc, dconf, None, None, None, None, None, None, None
+        return dloc, dconf, None, None, None, None, None, None, None, None
 
 
 class MultiBoxLoss(nn.Module):
@@ -46,8 +48,10 @@ class MultiBoxLoss(nn.Module):
         # extension (not in the reference): one process per GPU keeps the reference's per-replica normaliser N by default; True
         # all-reduces N over the ranks so that the data-parallel mean of the losses / gradients equals the single (world x B)-image batch
         self.global_normalizer = False
+        # None: the forward's launch sequence follows GSSD_FUSE_LOSS (default: the fused two launches); True / False choose it here
+        self.fused = None
 
-    def forward(self, predictions, targets):
+    def forward(self, predictions, targets, fused=None):
         loc_data, conf_data, priors = predictions
         P = loc_data.size(1)
         priors = priors[:P, :]                       # DataParallel concatenates priors (:60)
@@ -56,4 +60,4 @@ class MultiBoxLoss(nn.Module):
         tg, n_gt = ops.pack_targets(targets, loc_data.device)
         return _MultiBoxLossFn.apply(loc_data, conf_data, priors.detach().contiguous(), tg, n_gt, float(self.threshold),
                                      int(self.negpos_ratio), (float(self.variance[0]), float(self.variance[1])),
-                                     bool(self.global_normalizer))
+                                     bool(self.global_normalizer), self.fused if fused is None else fused)

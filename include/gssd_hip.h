@@ -698,6 +698,18 @@ int gssd_loss_finalize(const double* partial, int B, float* losses, double* n_to
  * losses, and of the gradients gssd_loss_backward forms with this n_total, equals the single (world x B)-image batch. */
 int gssd_loss_finalize_global(const double* partial, int B, const double* n_global, int world, float* losses, double* n_total,
                               gssd_stream_t stream);
+/* The forward of MultiBoxLoss in two launches: what gssd_match_batch, gssd_reduce_max_f32, gssd_hnm_loss and gssd_loss_finalize compute in
+ * four, bit for bit (same arithmetic, same order of every sum).  Launch 1 (B x GSSD_MULTIBOX_SLICES workgroups) matches a slice of the
+ * priors and takes the maximum of that slice of conf; launch 2 (one workgroup per image) mines, sums, and its last workgroup to finish adds
+ * the rows of partial in image order into losses [2] and *n_total (optional).  loss_c_all is optional.
+ * workspace: at least gssd_multibox_loss_workspace_bytes(B) bytes, 16-byte aligned, ZEROED once by its owner and then used by one stream
+ * at a time; every call leaves its first 16 bytes (the ticket of launch 2) zero again. */
+#define GSSD_MULTIBOX_SLICES 8
+long long gssd_multibox_loss_workspace_bytes(int B);
+int gssd_multibox_loss_forward_f32(const float* loc, const float* conf, const float* priors, const float* targets, const int* gt_off,
+                                   int B, int P, int C, float threshold, float var0, float var1, int negpos_ratio, float* loc_t,
+                                   int64_t* conf_t, uint8_t* sel, double* partial, float* losses, double* n_total, float* loss_c_all,
+                                   void* workspace, long long workspace_bytes, gssd_stream_t stream);
 /* d(loss_l + loss_c)/d(loc, conf) scaled by grad_l, grad_c (device scalars) / N. */
 int gssd_loss_backward(const float* loc, const float* conf, const float* loc_t, const int64_t* conf_t,
                        const uint8_t* sel, const double* n_total, const float* grad_l, const float* grad_c, int B,
@@ -744,6 +756,10 @@ int gssd_eval_ap(const float* conf, const uint8_t* flags, int M, int n_metrics, 
 /* out[b][p][c] = sum_{k < splits[p]} ws[k][b][p][c] (ws slices B*P*C floats apart), in slice order: the deterministic reduction of
  * the multibox heads' split-K slices (GSSD_CONV_HEADS_SLICES).  splits: int8 [P], the slice count of the head that owns prior p. */
 int gssd_heads_reduce_f32(const float* ws, const signed char* splits, float* out, int B, int P, int C, gssd_stream_t stream);
+/* Both heads in one launch: loc [B][P][4] from ws_loc and conf [B][P][C] from ws_conf, each element summed exactly as
+ * gssd_heads_reduce_f32 sums it (same slices, same order: identical bits). */
+int gssd_heads_reduce2_f32(const float* ws_loc, const float* ws_conf, const signed char* splits, float* loc, float* conf, int B, int P,
+                           int C, gssd_stream_t stream);
 
 /* ---- PixelLink++ tail (ssd_liverdet/pixel_link) ------------------------------------------------------------
  * The trunk / Self_Attn / DCN / fuse / score-head launches are gssd_conv2d_nhwc_f32 & co; these four are the rest. */

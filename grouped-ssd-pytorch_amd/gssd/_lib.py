@@ -77,6 +77,7 @@ SIGNATURES = {
     'gssd_pack_conv_weight': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp]),
     'gssd_conv2d_nhwc_f32': (c_i, [C.POINTER(ConvDesc), c_fp]),
     'gssd_conv2d_nhwc_bf16': (c_i, [C.POINTER(ConvDesc), c_fp]),
+    'gssd_conv2d_kernel_name': (c_i, [C.POINTER(ConvDesc), c_i, C.c_char_p, c_i]),
     'gssd_conv_x6_tile': (c_i, [c_i, c_i, c_i64]),
     'gssd_conv_x6_weight_elems': (c_i64, [c_i, c_i, c_i, c_i, c_i]),
     'gssd_conv_x6_pack_weight': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp]),

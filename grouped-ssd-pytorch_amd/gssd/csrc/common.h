@@ -98,31 +98,75 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
+// What the conv dispatchers hand down their gssd_try_* / launch chain: the stream to launch on, or (name != nullptr) the buffer
+// gssd_conv2d_kernel_name wants the chosen kernel instance's name in.  A launch site names its instance FIRST -- before any HIP call
+// or claimed resource -- so the query runs the dispatch's own control flow and touches no device.
+struct gssd_conv_ctx {
+    hipStream_t stream = nullptr;
+    char* name = nullptr;
+    int cap = 0;
+    int tile_m = 0;                 // out, when naming: pixels per workgroup of a conv_flat_bf16 instance (gssd_conv_flat_bf16_takes)
+};
+// writes the name (printf-style) into c.name: GSSD_OK, or GSSD_EINVAL when it does not fit c.cap (runtime.hip)
+int gssd_name_kernel(const gssd_conv_ctx& c, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// The implicit-GEMM tile of a launch the specialised kernels left to conv_igemm.hip / conv_bf16.hip (the two share their tilings).
+enum gssd_igemm_tile { GSSD_TILE_32x64, GSSD_TILE_64x64, GSSD_TILE_128x128, GSSD_TILE_128x64, GSSD_TILE_128x32, GSSD_TILE_128x16 };
+static inline gssd_igemm_tile gssd_pick_igemm_tile(const gssd_conv_desc& d, int M, int images) {
+    const int cout_g = d.Cout / d.groups;
+    // small maps (<= 10 x 10 at batch 32; per-image GEMMs of <= 100 tokens): 32- / 64-row tiles, three-stage K loop
+    static const bool no_small = getenv("GSSD_NO_SMALL_TILES") != nullptr;       // ablation switch
+    if (!no_small && cout_g > 32 && d.split_k == 1 && !(d.out_mode == GSSD_OUT_SPLIT_T && d.split_n % 64 != 0)) {
+        // (per-image GEMMs count all their images: the 19 x 19 projections -- 361 tokens x 32 images -- keep the 128-row tiles)
+        const long long mtot = (long long)M * images;
+        if (mtot <= 512 || (d.m_per_image && mtot <= 4096 && M <= 128)) return GSSD_TILE_32x64;
+        if (mtot <= 4096) return GSSD_TILE_64x64;
+    }
+    if (cout_g > 64) {
+        // 128x128 tiles run 2 workgroups per CU (LDS), 128x64 tiles 3: pick the one whose last round of workgroups is
+        // fuller (wave quantisation decides small 19x19 / 38x38 layers); the wide tile wins ties (less B re-read).
+        const long long mt = (M + 127) / 128, z = d.m_per_image ? images : d.split_k;
+        const long long b128 = mt * d.groups * ((cout_g + 127) / 128) * z, b64 = mt * d.groups * ((cout_g + 63) / 64) * z;
+        const double e128 = (double)b128 / (double)(((b128 + 511) / 512) * 512);
+        const double e64 = 0.94 * (double)b64 / (double)(((b64 + 767) / 768) * 768);
+        // short reductions (K <= 256: the attention output conv) are prologue / epilogue bound: three resident 128x64
+        // workgroups per CU overlap those phases better than two 128x128 ones
+        // (the three-stage K loop of the small tiles on these 128-row tiles: bf16 fwd + loss 3.87 -> 4.11 ms, measured round 4)
+        if (e64 > e128 || d.K <= 256 || (d.out_mode == GSSD_OUT_SPLIT_T && d.split_n % 128 != 0)) return GSSD_TILE_128x64;
+        return GSSD_TILE_128x128;
+    }
+    return cout_g > 32 ? GSSD_TILE_128x64 : cout_g > 16 ? GSSD_TILE_128x32 : GSSD_TILE_128x16;
+}
+
+// conv_igemm.hip / conv_bf16.hip: the two conv entry points' validation + dispatch (launches on c.stream, or names into c.name)
+int gssd_conv_dispatch_f32(const gssd_conv_desc* d, gssd_conv_ctx& c);
+int gssd_conv_dispatch_bf16(const gssd_conv_desc* d, gssd_conv_ctx& c);
+// The gssd_try_* below: 1 = not this kernel's descriptor (the dispatcher goes on), else the GSSD_* code of the launch (or of naming it).
 // conv_thin.hip: returns 1 when the descriptor is not one of the thin grouped 3x3 shapes, else a GSSD_* code
-int gssd_try_conv_thin(const gssd_conv_desc& d, hipStream_t stream);
+int gssd_try_conv_thin(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // conv_wino.hip: returns 1 when the descriptor is not a Winograd shape / has no transformed weights
-int gssd_try_conv_wino(const gssd_conv_desc& d, hipStream_t stream);
-int gssd_try_conv_x6(const gssd_conv_desc& d, hipStream_t stream);      // csrc/conv_x6.hip: 1 = not taken
+int gssd_try_conv_wino(const gssd_conv_desc& d, gssd_conv_ctx& c);
+int gssd_try_conv_x6(const gssd_conv_desc& d, gssd_conv_ctx& c);      // csrc/conv_x6.hip: 1 = not taken
 // conv_wino_x6.hip: Winograd with three-plane bf16 operands; its U planes are stored behind the fp32 U of gssd_winograd_weight_f32
 long long gssd_wino_x6_plane_elems(int cout_g, int groups, int cin_g);  // bf16 elements (0: not a shape it takes)
 int gssd_wino_x6_pack(const float* w_packed, void* Ux, int Cout, int groups, int cin_g, int row_stride, hipStream_t stream);
 bool gssd_wino_x6_enabled();                                             // GSSD_WINO_X6=0 switches it off
 bool gssd_wino_x6_wanted(const gssd_conv_desc& d);                        // the shapes it takes by default (GSSD_WINO_X6=2: all it can)
-int gssd_launch_conv_wino_x6(const gssd_conv_desc& d, const void* Ux, hipStream_t stream);
+int gssd_launch_conv_wino_x6(const gssd_conv_desc& d, const void* Ux, gssd_conv_ctx& c);
 // conv_patch_x6.hip: dense 3x3 convs with many input channels and <= 128 outputs, fp16 planes (GSSD_CONV_F16_OK launches with wgt_patch); else 1
-int gssd_try_conv_patch_x6(const gssd_conv_desc& d, hipStream_t stream);
+int gssd_try_conv_patch_x6(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // conv_thin_x6.hip: conv1_2 / conv2_1 / conv2_2 shape classes on the bf16 matrix cores with three-plane operands; else returns 1
-int gssd_try_conv_thin_x6(const gssd_conv_desc& d, hipStream_t stream);
+int gssd_try_conv_thin_x6(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // conv_thin_wino.hip: conv1_2's shape class (4 x 16 -> 16 channels, large map) with Winograd weights; else returns 1
-int gssd_try_conv_thin_wino(const gssd_conv_desc& d, hipStream_t stream);
+int gssd_try_conv_thin_wino(const gssd_conv_desc& d, gssd_conv_ctx& c);
 int gssd_try_conv_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream);
 // conv_patch_wgrad.hip: conv2_1 .. conv3_3 shapes (patch-staged, one phase group per workgroup); else returns 1
 int gssd_try_conv_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream);
 // gemm_slot.hip: large plain 1x1 convs / GEMMs as a slot-scheduled 128 x 256 MFMA stream; returns 1 for every other shape
-int gssd_try_gemm_slot(const gssd_conv_desc& d, hipStream_t stream);
+int gssd_try_gemm_slot(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // wgrad_slot.hip: weight gradient of large plain 1x1 convs (and the DCN contraction) as a slot-scheduled TN GEMM; else returns 1
 int gssd_try_wgrad_slot(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream);
 // conv_thin_bf16.hip: bf16 thin trunk layers (conv1_1 .. conv2_2); returns 1 when the descriptor is not one of them
-int gssd_try_conv_thin_bf16(const gssd_conv_desc& d, hipStream_t stream);
+int gssd_try_conv_thin_bf16(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // conv_flat_bf16.hip: bf16 grouped 3x3 trunk layers with 32 .. 128 channels per group (conv3_1 .. conv6); returns 1 when not one of them
-int gssd_try_conv_flat_bf16(const gssd_conv_desc& d, hipStream_t stream);
+int gssd_try_conv_flat_bf16(const gssd_conv_desc& d, gssd_conv_ctx& c);

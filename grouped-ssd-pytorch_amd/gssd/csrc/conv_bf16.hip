@@ -391,7 +391,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_bf16_kernel(const gssd_conv
 }
 
 template <int BM, int BN, int WM, int WN, int NSTG = 2>
-int launch_cfg(const gssd_conv_desc& d, int M, int images, hipStream_t stream) {
+int launch_cfg(const gssd_conv_desc& d, int M, int images, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_bf16<%dx%d>", BM, BN);
     static unsigned attr_mask = 0;
     constexpr size_t smem_base = NSTG * (size_t)(BM + BN) * BK * sizeof(u16);
     const size_t smem = smem_base + (d.in_scale ? 2 * (size_t)d.cin_g * sizeof(float) : 0);
@@ -401,7 +402,7 @@ int launch_cfg(const gssd_conv_desc& d, int M, int images, hipStream_t stream) {
     const int tiles = (cout_g + BN - 1) / BN;
     const int mtiles = (M + BM - 1) / BM;
     dim3 grid = d.m_per_image ? dim3(mtiles, d.groups * tiles, images) : dim3((mtiles + 7) / 8 * 8 * d.groups * tiles, 1, d.split_k);
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, stream, d, M, tiles);
+    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, c.stream, d, M, tiles);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -508,7 +509,8 @@ extern "C" int gssd_cast_f32_bf16(const float* x, void* y, int64_t n, gssd_strea
     return GSSD_OK;
 }
 
-extern "C" int gssd_conv2d_nhwc_bf16(const gssd_conv_desc* dp, gssd_stream_t stream) {
+// gssd_conv2d_nhwc_bf16 and, with a name sink in `c`, gssd_conv2d_kernel_name (csrc/conv_igemm.hip)
+int gssd_conv_dispatch_bf16(const gssd_conv_desc* dp, gssd_conv_ctx& c) {
     GSSD_CHECK_ARG(dp != nullptr);
     const gssd_conv_desc& d = *dp;
     GSSD_CHECK_ARG(d.in && d.wgt && d.out);
@@ -547,53 +549,39 @@ extern "C" int gssd_conv2d_nhwc_bf16(const gssd_conv_desc* dp, gssd_stream_t str
     GSSD_CHECK_ARG((long long)(d.Cout / d.groups + 256) * d.wgt_row_stride < (1ll << 31));
     const int M = (int)Mll;
     const int cout_g = d.Cout / d.groups;
-    hipStream_t s = as_stream(stream);
-    {
-        const int rc = gssd_try_conv_thin_bf16(d, s);      // conv1_1 .. conv2_2: patch-staged HBM-stream kernel
-        if (rc != 1) return rc;
-    }
+    if (const int rc = gssd_try_conv_thin_bf16(d, c); rc != 1) return rc;      // conv1_1 .. conv2_2: patch-staged HBM-stream kernel
     if (d.flags & GSSD_CONV_POOL2) {
         gssd_set_error("GSSD_CONV_POOL2: no bf16 kernel with a pooled epilogue takes this descriptor (thin trunk shapes only)");
         return GSSD_EINVAL;
     }
-    {
-        const int rc = gssd_try_conv_flat_bf16(d, s);      // conv3_1 .. conv6: flat-window kernel (csrc/conv_flat_bf16.hip)
-        if (rc != 1) return rc;
-    }
+    if (const int rc = gssd_try_conv_flat_bf16(d, c); rc != 1) return rc;      // conv3_1 .. conv6: flat-window kernel (csrc/conv_flat_bf16.hip)
     if (d.in_scale) GSSD_CHECK_ARG(d.cin_g <= 1024 && !d.m_per_image);
-    // small maps (<= 10 x 10 at batch 32; per-image GEMMs of <= 100 tokens): 32- / 64-row tiles, three-stage K loop (csrc/conv_igemm.hip)
-    static const bool no_small = getenv("GSSD_NO_SMALL_TILES") != nullptr;
-    if (!no_small && cout_g > 32 && d.split_k == 1 && !(d.out_mode == GSSD_OUT_SPLIT_T && d.split_n % 64 != 0)) {
-        // (per-image GEMMs count all their images: the 19 x 19 projections -- 361 tokens x 32 images -- keep the 128-row tiles)
-        const long long mtot = (long long)M * images;
-        if (mtot <= 512 || (d.m_per_image && mtot <= 4096 && M <= 128)) return launch_cfg<32, 64, 1, 4, 3>(d, M, images, s);
-        if (mtot <= 4096) return launch_cfg<64, 64, 2, 2, 3>(d, M, images, s);
-    }
     // Measured and rejected (round 5), kept behind GSSD_BF16_BIG_TILES=1: 256 x 128 tiles on eight waves for the large GEMM-shaped launches (the
     // 38 x 38 / 19 x 19 Self_Attn projections and output convs, the fuse convs).  The idea: 128 x 64 tiles re-read the activation tile once per
     // output tile (566 MB of L2 -> LDS traffic per fuse_11 launch for 94 MB of operands).  Result: 7 launches 74.5 us at 197 TFLOP/s against
     // 58.9 us at 287 -- with K = 256 .. 1024 a tile runs 4 .. 16 K steps, so the launch is bound by the tiles' prologue / epilogue, not by the
-    // traffic of the main loop, and the larger tile only costs occupancy.
+    // traffic of the main loop, and the larger tile only costs occupancy.  (M >= 8192: never a launch of the small-map tiles below.)
     static const int big = [] { const char* e = getenv("GSSD_BF16_BIG_TILES"); return e ? atoi(e) : 0; }();
     if (big && !d.m_per_image && d.split_k == 1 && M >= 8192 && cout_g % 128 == 0 && d.K % BK == 0 && d.K >= 256 &&
         (d.out_mode == GSSD_OUT_NHWC || (d.out_mode == GSSD_OUT_SPLIT_T && d.split_n % 128 == 0))) {
-        if (big == 2) return launch_cfg<256, 128, 4, 2, 3>(d, M, images, s);     // round 6 sweep: the same tile behind a three-stage ring (144 KB)
-        if (big == 3) return launch_cfg<192, 128, 4, 2, 3>(d, M, images, s);     // 192 rows: 46 208 pixels = 241 row tiles -> 723 / 964 tiles = 2.8 / 3.8 rounds
-        if (big == 4) return launch_cfg<128, 128, 2, 2, 4>(d, M, images, s);     // four stages of 32 KB, four 64 x 64 waves
-        if (big == 5) return launch_cfg<128, 128, 2, 2, 3>(d, M, images, s);
-        if (big == 6) return launch_cfg<128, 128, 4, 2, 4>(d, M, images, s);     // eight 32 x 64 waves
-        return launch_cfg<256, 128, 4, 2>(d, M, images, s);      // (256 x 256 on eight waves: 256 registers and 672 bytes of scratch per lane)
+        if (big == 2) return launch_cfg<256, 128, 4, 2, 3>(d, M, images, c);     // round 6 sweep: the same tile behind a three-stage ring (144 KB)
+        if (big == 3) return launch_cfg<192, 128, 4, 2, 3>(d, M, images, c);     // 192 rows: 46 208 pixels = 241 row tiles -> 723 / 964 tiles = 2.8 / 3.8 rounds
+        if (big == 4) return launch_cfg<128, 128, 2, 2, 4>(d, M, images, c);     // four stages of 32 KB, four 64 x 64 waves
+        if (big == 5) return launch_cfg<128, 128, 2, 2, 3>(d, M, images, c);
+        if (big == 6) return launch_cfg<128, 128, 4, 2, 4>(d, M, images, c);     // eight 32 x 64 waves
+        return launch_cfg<256, 128, 4, 2>(d, M, images, c);      // (256 x 256 on eight waves: 256 registers and 672 bytes of scratch per lane)
     }
-    if (cout_g > 64) {
-        const long long mt = (M + 127) / 128, z = d.m_per_image ? images : d.split_k;
-        const long long b128 = mt * d.groups * ((cout_g + 127) / 128) * z, b64 = mt * d.groups * ((cout_g + 63) / 64) * z;
-        const double e128 = (double)b128 / (double)(((b128 + 511) / 512) * 512);
-        const double e64 = 0.94 * (double)b64 / (double)(((b64 + 767) / 768) * 768);
-        // (the three-stage K loop of the small tiles on these 128-row tiles: bf16 fwd + loss 3.87 -> 4.11 ms, measured round 4)
-        if (e64 > e128 || d.K <= 256 || (d.out_mode == GSSD_OUT_SPLIT_T && d.split_n % 128 != 0)) return launch_cfg<128, 64, 2, 2>(d, M, images, s);
-        return launch_cfg<128, 128, 2, 2>(d, M, images, s);
+    switch (gssd_pick_igemm_tile(d, M, images)) {             // the fp32 kernel's tilings (common.h)
+        case GSSD_TILE_32x64: return launch_cfg<32, 64, 1, 4, 3>(d, M, images, c);
+        case GSSD_TILE_64x64: return launch_cfg<64, 64, 2, 2, 3>(d, M, images, c);
+        case GSSD_TILE_128x128: return launch_cfg<128, 128, 2, 2>(d, M, images, c);
+        case GSSD_TILE_128x64: return launch_cfg<128, 64, 2, 2>(d, M, images, c);
+        case GSSD_TILE_128x32: return launch_cfg<128, 32, 4, 1>(d, M, images, c);
+        default: return launch_cfg<128, 16, 4, 1>(d, M, images, c);
     }
-    if (cout_g > 32) return launch_cfg<128, 64, 2, 2>(d, M, images, s);
-    if (cout_g > 16) return launch_cfg<128, 32, 4, 1>(d, M, images, s);
-    return launch_cfg<128, 16, 4, 1>(d, M, images, s);
+}
+
+extern "C" int gssd_conv2d_nhwc_bf16(const gssd_conv_desc* dp, gssd_stream_t stream) {
+    gssd_conv_ctx c{as_stream(stream)};
+    return gssd_conv_dispatch_bf16(dp, c);
 }

@@ -352,14 +352,12 @@ __global__ __launch_bounds__(WMW * WNW * 64, WMW * WNW == 4 ? 2 : 1) void conv_f
 }
 
 int g_force_bm = getenv("GSSD_FLAT_BM") ? atoi(getenv("GSSD_FLAT_BM")) : 0;     // 0 = choose per shape; 128 / 256 = force (ablation, tests)
-thread_local bool g_dry = false;   // gssd_conv_flat_bf16_takes: run the dispatch logic without launching
-thread_local int g_dry_bm = 0;
 
 template <int CIN_G, int COUT_T, bool XF, int NSTG, int WMW, int WNW>
-int launch_flat_n(const gssd_conv_desc& d, const FlatParams& p, size_t smem, hipStream_t stream) {
-    if (g_dry) {
-        g_dry_bm = 64 * WMW;
-        return GSSD_OK;
+int launch_flat_n(const gssd_conv_desc& d, const FlatParams& p, size_t smem, gssd_conv_ctx& c) {
+    if (c.name) {
+        c.tile_m = 64 * WMW;
+        return gssd_name_kernel(c, "conv_flat_bf16<%d,%d,%d>", CIN_G, COUT_T, 64 * WMW);
     }
     auto kern = conv_flat_bf16_kernel<CIN_G, COUT_T, XF, NSTG, WMW, WNW>;
     static unsigned attr_mask = 0;
@@ -370,13 +368,13 @@ int launch_flat_n(const gssd_conv_desc& d, const FlatParams& p, size_t smem, hip
     int grid = (p.total + 1) / 2 * 8;
     const int slots = WMW * WNW == 4 ? 512 : 256;
     if (persist && grid > slots) grid = slots;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WMW * WNW * 64), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WMW * WNW * 64), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 template <int CIN_G, int COUT_T, bool XF>
-int launch_flat(const gssd_conv_desc& d, hipStream_t stream) {
+int launch_flat(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     constexpr int CP = CIN_G < 64 ? CIN_G : 64, PPI = 64 / (CP / 8), RPP = 64 / (CP / 8);
     constexpr int NSTG_DEF = CP == 64 ? 3 : 4;       // ring stages: 2 slices in flight at 64 k, 3 at 32 k
     FlatParams p;
@@ -414,18 +412,18 @@ int launch_flat(const gssd_conv_desc& d, hipStream_t stream) {
     if constexpr (COUT_T == 64) {
         if ((force_bm == 256 || (force_bm == 0 && fill256)) && NSTG_DEF * stage + window(256) <= 80 * 1024) {
             geometry(256);
-            return launch_flat_n<CIN_G, COUT_T, XF, NSTG_DEF, 4, 1>(d, p, NSTG_DEF * stage + window(256), stream);
+            return launch_flat_n<CIN_G, COUT_T, XF, NSTG_DEF, 4, 1>(d, p, NSTG_DEF * stage + window(256), c);
         }
     } else if constexpr (COUT_T / RPP / 8 >= 1) {
         if (force_bm == 256 && NSTG_DEF * stage + window(256) <= 160 * 1024) {
             geometry(256);
-            return launch_flat_n<CIN_G, COUT_T, XF, NSTG_DEF, 4, 2>(d, p, NSTG_DEF * stage + window(256), stream);
+            return launch_flat_n<CIN_G, COUT_T, XF, NSTG_DEF, 4, 2>(d, p, NSTG_DEF * stage + window(256), c);
         }
     }
     geometry(128);
     // two workgroups per CU or not at all (the generic kernel takes what does not fit): wide windows (dilated conv6) run a 2-stage ring
-    if (NSTG_DEF * stage + window(128) <= 80 * 1024) return launch_flat_n<CIN_G, COUT_T, XF, NSTG_DEF, 2, 2>(d, p, NSTG_DEF * stage + window(128), stream);
-    if (2 * stage + window(128) <= 80 * 1024) return launch_flat_n<CIN_G, COUT_T, XF, 2, 2, 2>(d, p, 2 * stage + window(128), stream);
+    if (NSTG_DEF * stage + window(128) <= 80 * 1024) return launch_flat_n<CIN_G, COUT_T, XF, NSTG_DEF, 2, 2>(d, p, NSTG_DEF * stage + window(128), c);
+    if (2 * stage + window(128) <= 80 * 1024) return launch_flat_n<CIN_G, COUT_T, XF, 2, 2, 2>(d, p, 2 * stage + window(128), c);
     return 1;
 }
 
@@ -439,15 +437,13 @@ extern "C" int gssd_conv_flat_bf16_tile(int bm) {
 
 extern "C" int gssd_conv_flat_bf16_takes(const gssd_conv_desc* d) {
     if (!d) return 0;
-    g_dry = true;
-    g_dry_bm = 0;
-    const int rc = gssd_try_conv_flat_bf16(*d, nullptr);
-    g_dry = false;
-    return rc == GSSD_OK ? g_dry_bm : 0;
+    char name[64];
+    gssd_conv_ctx c{nullptr, name, (int)sizeof(name)};
+    return gssd_try_conv_flat_bf16(*d, c) == GSSD_OK ? c.tile_m : 0;
 }
 
 // Eligibility + dispatch; called from gssd_conv2d_nhwc_bf16 (conv_bf16.hip).  Returns 1 if not eligible.
-int gssd_try_conv_flat_bf16(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_conv_flat_bf16(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     static const bool off = getenv("GSSD_NO_CONV_FLAT") != nullptr && atoi(getenv("GSSD_NO_CONV_FLAT")) != 0;   // ablation
     if (off) return 1;
     const int cout_g = d.Cout / d.groups;
@@ -460,8 +456,8 @@ int gssd_try_conv_flat_bf16(const gssd_conv_desc& d, hipStream_t stream) {
 #define FLAT_CASE(CI)                                                                                                     \
     if (d.cin_g == CI) {                                                                                                  \
         if (cout_g % 128 == 0)                                                                                            \
-            return d.in_scale ? launch_flat<CI, 128, true>(d, stream) : launch_flat<CI, 128, false>(d, stream);           \
-        return d.in_scale ? launch_flat<CI, 64, true>(d, stream) : launch_flat<CI, 64, false>(d, stream);                 \
+            return d.in_scale ? launch_flat<CI, 128, true>(d, c) : launch_flat<CI, 128, false>(d, c);           \
+        return d.in_scale ? launch_flat<CI, 64, true>(d, c) : launch_flat<CI, 64, false>(d, c);                 \
     }
     FLAT_CASE(32)
     FLAT_CASE(64)

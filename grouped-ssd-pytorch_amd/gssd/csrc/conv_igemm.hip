@@ -357,7 +357,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const gssd_con
 }
 
 template <int BM, int BN, int WM, int WN, int NSTG = 2>
-int launch_cfg(const gssd_conv_desc& d, int M, int images, hipStream_t stream) {
+int launch_cfg(const gssd_conv_desc& d, int M, int images, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_igemm<%dx%d>", BM, BN);
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
     constexpr size_t smem_base = NSTG * (size_t)(BM + BN) * BK * sizeof(float);
     const size_t smem = smem_base + (d.in_scale ? 2 * (size_t)d.cin_g * sizeof(float) : 0);
@@ -368,14 +369,15 @@ int launch_cfg(const gssd_conv_desc& d, int M, int images, hipStream_t stream) {
     const int mtiles = (M + BM - 1) / BM;
     dim3 grid = d.m_per_image ? dim3(mtiles, d.groups * tiles, images) : dim3((mtiles + 7) / 8 * 8 * d.groups * tiles, 1, d.split_k);
     static_assert(BM % (8 * WM * WN) == 0, "A rows must split evenly over the waves");
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, stream, d, M, tiles);
+    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, c.stream, d, M, tiles);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 }  // namespace
 
-extern "C" int gssd_conv2d_nhwc_f32(const gssd_conv_desc* dp, gssd_stream_t stream) {
+// gssd_conv2d_nhwc_f32 and, with a name sink in `c`, gssd_conv2d_kernel_name: one walk through validation and dispatch for both
+int gssd_conv_dispatch_f32(const gssd_conv_desc* dp, gssd_conv_ctx& c) {
     GSSD_CHECK_ARG(dp != nullptr);
     const gssd_conv_desc& d = *dp;
     GSSD_CHECK_ARG(d.in && d.wgt && d.out);
@@ -413,87 +415,56 @@ extern "C" int gssd_conv2d_nhwc_f32(const gssd_conv_desc* dp, gssd_stream_t stre
     GSSD_CHECK_ARG((long long)(d.m_per_image ? 1 : d.B) * d.H * d.W * d.in_stride < (1ll << 31));
     GSSD_CHECK_ARG((long long)(d.Cout / d.groups + 256) * d.wgt_row_stride < (1ll << 31));
     const int M = (int)Mll;
-    const int cout_g = d.Cout / d.groups;
-    hipStream_t s = as_stream(stream);
     if (d.flags & GSSD_CONV_IN_NCHW3) {                   // `in` is the NCHW image batch: only the patch-staged thin kernel reads that
-        const int rc = gssd_try_conv_thin(d, s);
-        if (rc != 1) return rc;
+        if (const int rc = gssd_try_conv_thin(d, c); rc != 1) return rc;
         gssd_set_error("GSSD_CONV_IN_NCHW3: not conv1_1's shape (see gssd_conv_thin_nchw3_takes)");
         return GSSD_EINVAL;
     }
-    if (d.flags & GSSD_CONV_OUT_GROUPCAT) {               // grouped destination remap: an epilogue of csrc/conv_x6.hip only
-        const int rc = d.wgt_x6 ? gssd_try_conv_x6(d, s) : 1;
-        if (rc != 1) return rc;
-        gssd_set_error("GSSD_CONV_OUT_GROUPCAT: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)");
+    // the grouped destination remap, BatchNorm + ReLU of the residual on read, the attention core's planes as the output: epilogues of
+    // csrc/conv_x6.hip only
+    if (d.flags & (GSSD_CONV_OUT_GROUPCAT | GSSD_CONV_RESID_XF | GSSD_CONV_OUT_X6PLANES)) {
+        if (const int rc = gssd_try_conv_x6(d, c); rc != 1) return rc;
+        gssd_set_error("%s: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)",
+                       (d.flags & GSSD_CONV_OUT_GROUPCAT) ? "GSSD_CONV_OUT_GROUPCAT" : (d.flags & GSSD_CONV_RESID_XF) ? "GSSD_CONV_RESID_XF" : "GSSD_CONV_OUT_X6PLANES");
         return GSSD_EINVAL;
     }
-    if (d.flags & GSSD_CONV_RESID_XF) {                   // BatchNorm + ReLU of the residual on read: an epilogue of csrc/conv_x6.hip only
-        const int rc = d.wgt_x6 ? gssd_try_conv_x6(d, s) : 1;
-        if (rc != 1) return rc;
-        gssd_set_error("GSSD_CONV_RESID_XF: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)");
-        return GSSD_EINVAL;
-    }
-    if (d.flags & GSSD_CONV_OUT_X6PLANES) {               // the attention core's planes as the output: an epilogue of csrc/conv_x6.hip only
-        const int rc = d.wgt_x6 ? gssd_try_conv_x6(d, s) : 1;
-        if (rc != 1) return rc;
-        gssd_set_error("GSSD_CONV_OUT_X6PLANES: csrc/conv_x6.hip does not take this descriptor (see gssd_conv_x6_takes)");
-        return GSSD_EINVAL;
-    }
-    if (d.wgt_patch) {
-        const int rc = gssd_try_conv_patch_x6(d, s);  // many input channels, <= 128 outputs, GSSD_CONV_F16_OK: patch-staged direct conv on fp16 planes (round 6)
-        if (rc != 1) return rc;
-    }
-    if (d.wgt_x6) {
-        const int rc = gssd_try_conv_x6(d, s);        // fp32-equivalent products on the bf16 matrix cores (caller packed wgt_x6)
-        if (rc != 1) return rc;
-    }
-    {
-        const int rc = gssd_try_conv_thin_x6(d, s);   // conv1_2 / conv2_1 / conv2_2: patch-staged direct conv, three-plane bf16 operands (round 6)
-        if (rc != 1) return rc;
-    }
-    {
-        const int rc = gssd_try_conv_thin_wino(d, s); // conv1_2 (and its dgrad): patch-staged Winograd
-        if (rc != 1) return rc;
-    }
-    {
-        const int rc = gssd_try_conv_thin(d, s);      // conv1_1 / conv2_1 (conv1_2 without Winograd weights): patch-staged kernel
-        if (rc != 1) return rc;
-    }
-    {
-        const int rc = gssd_try_conv_wino(d, s);      // compute-bound 3x3 trunk layers: Winograd F(2x2,3x3)
-        if (rc != 1) return rc;
-    }
+    // the specialised kernels in dispatch order: the first that does not answer 1 ("not mine") has launched, named itself or failed
+    static constexpr int (*chain[])(const gssd_conv_desc&, gssd_conv_ctx&) = {
+        gssd_try_conv_patch_x6,   // wgt_patch: many input channels, <= 128 outputs, GSSD_CONV_F16_OK: patch-staged direct conv on fp16 planes (round 6)
+        gssd_try_conv_x6,         // wgt_x6: fp32-equivalent products on the bf16 matrix cores
+        gssd_try_conv_thin_x6,    // conv1_2 / conv2_1 / conv2_2: patch-staged direct conv, three-plane bf16 operands (round 6)
+        gssd_try_conv_thin_wino,  // conv1_2 (and its dgrad): patch-staged Winograd
+        gssd_try_conv_thin,       // conv1_1 / conv2_1 (conv1_2 without Winograd weights): patch-staged kernel
+        gssd_try_conv_wino,       // compute-bound 3x3 trunk layers: Winograd F(2x2,3x3)
+    };
+    for (auto try_kernel : chain)
+        if (const int rc = try_kernel(d, c); rc != 1) return rc;
     if (d.flags & GSSD_CONV_POOL2) {
         gssd_set_error("GSSD_CONV_POOL2: no fp32 kernel with a pooled epilogue takes this descriptor (Winograd trunk shapes only)");
         return GSSD_EINVAL;
     }
     if (d.in_scale) GSSD_CHECK_ARG(d.cin_g <= 512 && !d.m_per_image);
-    {
-        static const bool no_slot = getenv("GSSD_NO_GEMM_SLOT") != nullptr;      // ablation switch (scripts/layer_times.py)
-        const int rc = no_slot ? 1 : gssd_try_gemm_slot(d, s);                   // large plain 1x1 convs / GEMMs: 128 x 256 slot stream
-        if (rc != 1) return rc;
+    static const bool no_slot = getenv("GSSD_NO_GEMM_SLOT") != nullptr;      // ablation switch (scripts/layer_times.py)
+    if (!no_slot)                                                            // large plain 1x1 convs / GEMMs: 128 x 256 slot stream
+        if (const int rc = gssd_try_gemm_slot(d, c); rc != 1) return rc;
+    switch (gssd_pick_igemm_tile(d, M, images)) {
+        case GSSD_TILE_32x64: return launch_cfg<32, 64, 1, 4, 3>(d, M, images, c);
+        case GSSD_TILE_64x64: return launch_cfg<64, 64, 2, 2, 3>(d, M, images, c);
+        case GSSD_TILE_128x128: return launch_cfg<128, 128, 2, 2>(d, M, images, c);
+        case GSSD_TILE_128x64: return launch_cfg<128, 64, 2, 2>(d, M, images, c);
+        case GSSD_TILE_128x32: return launch_cfg<128, 32, 4, 1>(d, M, images, c);
+        default: return launch_cfg<128, 16, 4, 1>(d, M, images, c);
     }
-    // small maps (<= 10 x 10 at batch 32; per-image GEMMs of <= 100 tokens): 32- / 64-row tiles, three-stage K loop
-    static const bool no_small = getenv("GSSD_NO_SMALL_TILES") != nullptr;       // ablation switch
-    if (!no_small && cout_g > 32 && d.split_k == 1 && !(d.out_mode == GSSD_OUT_SPLIT_T && d.split_n % 64 != 0)) {
-        // (per-image GEMMs count all their images: the 19 x 19 projections -- 361 tokens x 32 images -- keep the 128-row tiles)
-        const long long mtot = (long long)M * images;
-        if (mtot <= 512 || (d.m_per_image && mtot <= 4096 && M <= 128)) return launch_cfg<32, 64, 1, 4, 3>(d, M, images, s);
-        if (mtot <= 4096) return launch_cfg<64, 64, 2, 2, 3>(d, M, images, s);
-    }
-    if (cout_g > 64) {
-        // 128x128 tiles run 2 workgroups per CU (LDS), 128x64 tiles 3: pick the one whose last round of workgroups is
-        // fuller (wave quantisation decides small 19x19 / 38x38 layers); the wide tile wins ties (less B re-read).
-        const long long mt = (M + 127) / 128, z = d.m_per_image ? images : d.split_k;
-        const long long b128 = mt * d.groups * ((cout_g + 127) / 128) * z, b64 = mt * d.groups * ((cout_g + 63) / 64) * z;
-        const double e128 = (double)b128 / (double)(((b128 + 511) / 512) * 512);
-        const double e64 = 0.94 * (double)b64 / (double)(((b64 + 767) / 768) * 768);
-        // short reductions (K <= 256: the attention output conv) are prologue / epilogue bound: three resident 128x64
-        // workgroups per CU overlap those phases better than two 128x128 ones
-        if (e64 > e128 || d.K <= 256 || (d.out_mode == GSSD_OUT_SPLIT_T && d.split_n % 128 != 0)) return launch_cfg<128, 64, 2, 2>(d, M, images, s);
-        return launch_cfg<128, 128, 2, 2>(d, M, images, s);
-    }
-    if (cout_g > 32) return launch_cfg<128, 64, 2, 2>(d, M, images, s);
-    if (cout_g > 16) return launch_cfg<128, 32, 4, 1>(d, M, images, s);
-    return launch_cfg<128, 16, 4, 1>(d, M, images, s);
+}
+
+extern "C" int gssd_conv2d_nhwc_f32(const gssd_conv_desc* dp, gssd_stream_t stream) {
+    gssd_conv_ctx c{as_stream(stream)};
+    return gssd_conv_dispatch_f32(dp, c);
+}
+
+extern "C" int gssd_conv2d_kernel_name(const gssd_conv_desc* dp, int bf16, char* buf, int cap) {
+    GSSD_CHECK_ARG(buf != nullptr && cap > 0);
+    buf[0] = 0;
+    gssd_conv_ctx c{nullptr, buf, cap};
+    return bf16 ? gssd_conv_dispatch_bf16(dp, c) : gssd_conv_dispatch_f32(dp, c);
 }

@@ -221,8 +221,9 @@ extern "C" int gssd_conv_patch_x6_takes(const gssd_conv_desc* dp) {
     return 1;
 }
 
-int gssd_try_conv_patch_x6(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_conv_patch_x6(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     if (!gssd_conv_patch_x6_takes(&d)) return 1;
+    if (c.name) return gssd_name_kernel(c, "conv_patch_x6<%d>", BN);
     PatchX6Params p;
     p.in = d.in + d.in_ch_off;
     p.wp = reinterpret_cast<const u16*>(d.wgt_patch);
@@ -244,7 +245,7 @@ int gssd_try_conv_patch_x6(const gssd_conv_desc& d, hipStream_t stream) {
     if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, LDS_BYTES)) return rc;
     const int ntiles = p.B * p.tiles_y * p.tiles_x;
     const int per = (ntiles + 7) / 8;
-    hipLaunchKernelGGL(kern, dim3(per * 8), dim3(NTHR), LDS_BYTES, stream, p);
+    hipLaunchKernelGGL(kern, dim3(per * 8), dim3(NTHR), LDS_BYTES, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }

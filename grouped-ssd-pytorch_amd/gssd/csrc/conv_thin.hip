@@ -309,7 +309,8 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_kernel(c
 }
 
 template <int CIN_G, int COUT_G, bool FIXED, bool XF, bool NCHW3 = false>
-int launch_thin_impl(const gssd_conv_desc& d, hipStream_t stream) {
+int launch_thin_impl(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_thin<%d,%d>", CIN_G, COUT_G);
     constexpr int CIN = 4 * CIN_G, COUT = 4 * COUT_G;
     ThinParams p;
     p.in = d.in;
@@ -350,17 +351,17 @@ int launch_thin_impl(const gssd_conv_desc& d, hipStream_t stream) {
     const int per_cu = smem > 60 * 1024 ? 2 : 3;
     int grid = 256 * per_cu;
     if (ntiles < grid) grid = (int)ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 template <int CIN_G, int COUT_G>
-int launch_thin(const gssd_conv_desc& d, hipStream_t stream) {
+int launch_thin(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     // compile-time 8 x 16 tile (97.4 % of 300 x 300); a runtime 5 x 25 tile that divides 150 and 75 exactly spilled registers
     // and lost (round 1), so only the FIXED instantiations are built
-    return d.in_scale ? launch_thin_impl<CIN_G, COUT_G, true, true>(d, stream)
-                      : launch_thin_impl<CIN_G, COUT_G, true, false>(d, stream);
+    return d.in_scale ? launch_thin_impl<CIN_G, COUT_G, true, true>(d, c)
+                      : launch_thin_impl<CIN_G, COUT_G, true, false>(d, c);
 }
 
 bool thin_shape_ok(const gssd_conv_desc& d) {
@@ -382,15 +383,15 @@ bool thin_nchw3_ok(const gssd_conv_desc& d) {
 extern "C" int gssd_conv_thin_nchw3_takes(const gssd_conv_desc* d) { return (d && thin_nchw3_ok(*d)) ? 1 : 0; }
 
 // Eligibility + dispatch; called from gssd_conv2d_nhwc_f32 (conv_igemm.hip).  Returns 1 if not eligible.
-int gssd_try_conv_thin(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_conv_thin(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     const int cout_g = d.Cout / d.groups;
-    if (d.flags & GSSD_CONV_IN_NCHW3) return thin_nchw3_ok(d) ? launch_thin_impl<4, 16, true, false, true>(d, stream) : 1;
+    if (d.flags & GSSD_CONV_IN_NCHW3) return thin_nchw3_ok(d) ? launch_thin_impl<4, 16, true, false, true>(d, c) : 1;
     if (!thin_shape_ok(d)) return 1;                             // (no pooled epilogue here: conv1_2 takes the Winograd thin kernel)
-    if (d.cin_g == 4 && cout_g == 16) return launch_thin<4, 16>(d, stream);
-    if (d.cin_g == 16 && cout_g == 16) return launch_thin<16, 16>(d, stream);
+    if (d.cin_g == 4 && cout_g == 16) return launch_thin<4, 16>(d, c);
+    if (d.cin_g == 16 && cout_g == 16) return launch_thin<16, 16>(d, c);
     // conv2_1 with Winograd weights goes to conv_wino<32> (round 4: this direct kernel is pipe-bound -- fp32 MFMA + VALU 93 % busy -- at
     // 2.25 x the MACs of the Winograd form: 300 -> 262 us at B = 32); GSSD_CONV21_WINO=0 keeps it here
     static const bool c21_wino = !gssd_env_off("GSSD_CONV21_WINO");
-    if (d.cin_g == 16 && cout_g == 32) return (c21_wino && d.wgt_wino) ? 1 : launch_thin<16, 32>(d, stream);
+    if (d.cin_g == 16 && cout_g == 32) return (c21_wino && d.wgt_wino) ? 1 : launch_thin<16, 32>(d, c);
     return 1;
 }

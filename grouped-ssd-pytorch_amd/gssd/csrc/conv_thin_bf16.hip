@@ -494,7 +494,8 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
 }
 
 template <int CIN_G, int COUT_G, bool XF, bool POOL>
-int launch_thin_bf16(const gssd_conv_desc& d, hipStream_t stream) {
+int launch_thin_bf16(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_thin_bf16<%d,%d>%s", CIN_G, COUT_G, POOL ? "/pool2" : "");
     constexpr int CIN = 4 * CIN_G;
     constexpr int TH = CIN <= 64 ? 16 : 8;
     constexpr int NPATCH = (TH + 2) * PW;
@@ -519,7 +520,7 @@ int launch_thin_bf16(const gssd_conv_desc& d, hipStream_t stream) {
     int grid = 256 * (COUT_G > 16 ? 2 : 3);      // workgroups per CU = the kernel's launch bound (three for conv2_1, whose 166 registers
     //                                              would allow it: 90 us against 80 with two -- round 4)
     if (ntiles < grid) grid = (int)ntiles;
-    hipLaunchKernelGGL((conv_thin_bf16_kernel<CIN_G, COUT_G, XF, TH, POOL>), dim3(grid), dim3(256), smem, stream, p);
+    hipLaunchKernelGGL((conv_thin_bf16_kernel<CIN_G, COUT_G, XF, TH, POOL>), dim3(grid), dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -527,7 +528,7 @@ int launch_thin_bf16(const gssd_conv_desc& d, hipStream_t stream) {
 }  // namespace
 
 // Eligibility + dispatch; called from gssd_conv2d_nhwc_bf16 (conv_bf16.hip).  Returns 1 if not eligible.
-int gssd_try_conv_thin_bf16(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_conv_thin_bf16(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     const int cout_g = d.Cout / d.groups;
     const bool shape_ok = d.groups == 4 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.dil == 1 &&
                           d.in_stride == 4 * d.cin_g && d.in_ch_off == 0 && d.out_mode == GSSD_OUT_NHWC && d.out_stride == d.Cout &&
@@ -537,8 +538,8 @@ int gssd_try_conv_thin_bf16(const gssd_conv_desc& d, hipStream_t stream) {
     const bool pool = (d.flags & GSSD_CONV_POOL2) != 0;
 #define THIN_CASE(CI, CO)                                                                                                          \
     if (d.cin_g == CI && cout_g == CO)                                                                                             \
-        return d.in_scale ? (pool ? launch_thin_bf16<CI, CO, true, true>(d, stream) : launch_thin_bf16<CI, CO, true, false>(d, stream)) \
-                          : (pool ? launch_thin_bf16<CI, CO, false, true>(d, stream) : launch_thin_bf16<CI, CO, false, false>(d, stream));
+        return d.in_scale ? (pool ? launch_thin_bf16<CI, CO, true, true>(d, c) : launch_thin_bf16<CI, CO, true, false>(d, c)) \
+                          : (pool ? launch_thin_bf16<CI, CO, false, true>(d, c) : launch_thin_bf16<CI, CO, false, false>(d, c));
     THIN_CASE(8, 16)
     THIN_CASE(16, 16)
     THIN_CASE(16, 32)

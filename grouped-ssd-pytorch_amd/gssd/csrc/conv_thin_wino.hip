@@ -244,7 +244,8 @@ __global__ __launch_bounds__(256, 2) void conv_thin_wino_kernel(const ThinWinoPa
 }
 
 template <bool XF>
-int launch_thin_wino(const gssd_conv_desc& d, hipStream_t stream) {
+int launch_thin_wino(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_thin_wino<16,16>");
     ThinWinoParams p;
     p.in = d.in;
     p.U = d.wgt_wino;
@@ -268,7 +269,7 @@ int launch_thin_wino(const gssd_conv_desc& d, hipStream_t stream) {
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     int grid = 512;                                       // two resident workgroups per CU (80 KB of LDS, <= 256 VGPRs each)
     if (ntiles < grid) grid = (int)ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -276,7 +277,7 @@ int launch_thin_wino(const gssd_conv_desc& d, hipStream_t stream) {
 }  // namespace
 
 // returns 1 when the descriptor is not the conv1_2 shape class (4 groups x 16 -> 16 channels, large map) with Winograd weights
-int gssd_try_conv_thin_wino(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_conv_thin_wino(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     if (!d.wgt_wino) return 1;
     const bool ok = d.groups == 4 && d.Cout == 64 && d.cin_g == 16 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 &&
                     d.dil == 1 && d.in_stride == 64 && d.in_ch_off == 0 && d.out_mode == GSSD_OUT_NHWC && d.out_stride == 64 &&
@@ -284,5 +285,5 @@ int gssd_try_conv_thin_wino(const gssd_conv_desc& d, hipStream_t stream) {
                     d.H * d.W >= 75 * 75 && ((uintptr_t)d.out % 16) == 0 && ((uintptr_t)d.in % 16) == 0 &&
                     (long long)d.B * d.H * d.W * 64 < (1ll << 31);
     if (!ok) return 1;
-    return d.in_scale ? launch_thin_wino<true>(d, stream) : launch_thin_wino<false>(d, stream);
+    return d.in_scale ? launch_thin_wino<true>(d, c) : launch_thin_wino<false>(d, c);
 }

@@ -518,7 +518,9 @@ int* tx6_counters(hipStream_t stream) {
 }
 
 template <int CIN_G, int COUT_G, bool XF, bool POOL, bool F16>
-int launch_thin_x6_impl(const gssd_conv_desc& d, hipStream_t stream) {
+int launch_thin_x6_impl(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    // (one name per kernel symbol as rocprofv3 --stats groups them; the plane format is not part of it)
+    if (c.name) return gssd_name_kernel(c, "conv_thin_x6<%d,%d>%s%s", CIN_G, COUT_G, XF ? "" : "/plain", POOL ? "/pool2" : "");
     constexpr int NPL = F16 ? 2 : 3;
     ThinX6Params p;
     p.in = d.in;
@@ -546,17 +548,17 @@ int launch_thin_x6_impl(const gssd_conv_desc& d, hipStream_t stream) {
     long long grid = 512;                                 // two workgroups per CU
     if (ntiles * NGI < grid) grid = ntiles * NGI;
     if (NGI > 1 && grid % NGI) grid += NGI - grid % NGI;  // every slab needs its workgroups
-    p.ctr = tx6_counters(stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT_), smem, stream, p);
+    p.ctr = tx6_counters(c.stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT_), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 // the two-plane fp16 form for launches the caller flags GSSD_CONV_F16_OK (operands inside fp16's range; never inferred from the descriptor); GSSD_X6_F16=0: bf16 planes everywhere
 template <int CIN_G, int COUT_G, bool XF, bool POOL>
-int launch_thin_x6(const gssd_conv_desc& d, hipStream_t stream) {
-    if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) return launch_thin_x6_impl<CIN_G, COUT_G, XF, POOL, true>(d, stream);
-    return launch_thin_x6_impl<CIN_G, COUT_G, XF, POOL, false>(d, stream);
+int launch_thin_x6(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) return launch_thin_x6_impl<CIN_G, COUT_G, XF, POOL, true>(d, c);
+    return launch_thin_x6_impl<CIN_G, COUT_G, XF, POOL, false>(d, c);
 }
 
 }  // namespace
@@ -587,14 +589,14 @@ static bool thin_x6_shape(const gssd_conv_desc& d) {
 extern "C" int gssd_conv_thin_x6_takes(const gssd_conv_desc* d) { return d && thin_x6_enabled() && thin_x6_shape(*d) ? 1 : 0; }
 
 // Eligibility + dispatch; called from gssd_conv2d_nhwc_f32 (conv_igemm.hip).  Returns 1 if not eligible.
-int gssd_try_conv_thin_x6(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_conv_thin_x6(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     if (!thin_x6_enabled() || !thin_x6_shape(d)) return 1;
     const int cout_g = d.Cout / d.groups;
     const bool pool = (d.flags & GSSD_CONV_POOL2) != 0;
 #define TX6_CASE(CI, CO)                                                                                                              \
     if (d.cin_g == CI && cout_g == CO)                                                                                                \
-        return d.in_scale ? (pool ? launch_thin_x6<CI, CO, true, true>(d, stream) : launch_thin_x6<CI, CO, true, false>(d, stream))   \
-                          : (pool ? launch_thin_x6<CI, CO, false, true>(d, stream) : launch_thin_x6<CI, CO, false, false>(d, stream));
+        return d.in_scale ? (pool ? launch_thin_x6<CI, CO, true, true>(d, c) : launch_thin_x6<CI, CO, true, false>(d, c))   \
+                          : (pool ? launch_thin_x6<CI, CO, false, true>(d, c) : launch_thin_x6<CI, CO, false, false>(d, c));
     TX6_CASE(16, 16)
     TX6_CASE(16, 32)
     TX6_CASE(32, 32)

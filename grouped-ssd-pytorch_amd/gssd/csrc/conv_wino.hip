@@ -479,7 +479,9 @@ inline int wino_u_rows(int cout_g, int groups) {
 }
 
 template <int NB, bool XF, bool PERSIST, int EPI>
-int launch_wino(const gssd_conv_desc& d, hipStream_t stream) {
+int launch_wino(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    // (one name per kernel symbol as rocprofv3 --stats groups them: tile, fused input transform, pooled epilogue)
+    if (c.name) return gssd_name_kernel(c, "conv_wino<%d>%s%s", NB, XF ? "" : "/plain", EPI == 2 ? "/pool2" : "");
     WinoParams p;
     p.in = d.in;
     p.U = d.wgt_wino;
@@ -530,39 +532,45 @@ int launch_wino(const gssd_conv_desc& d, hipStream_t stream) {
     if (gx > nitems || !PERSIST) gx = nitems;
     const dim3 grid = PERSIST ? dim3(gx, p.cout_pad / NB, d.groups)
                               : dim3(((nitems + 7) / 8) * 8 * (p.cout_pad / NB) * d.groups, 1, 1);
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(kern, grid, dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
+}
+
+// the Winograd kernels' one eligibility rule (gssd_try_conv_wino, gssd_conv_wino_x6_takes); on_x6: csrc/conv_wino_x6.hip takes and wants it
+bool wino_takes(const gssd_conv_desc& d, bool* on_x6) {
+    if (!d.wgt_wino || d.groups <= 0) return false;
+    const int cout_g = d.Cout / d.groups;
+    // the same transforms with the 16 GEMMs on the bf16 matrix cores (three-plane operands, conv_wino_x6.hip): its U planes lie behind the fp32 U
+    *on_x6 = gssd_wino_x6_plane_elems(cout_g, d.groups, d.cin_g) > 0 && gssd_wino_x6_wanted(d);
+    // (GSSD_OUT_HEADS: only the form conv_wino_x6.hip takes -- one reduction slice, no batch sums / residual / pooling, both sides of split_n whole quads)
+    const bool heads = d.out_mode == GSSD_OUT_HEADS && d.out_b && d.split_k <= 1 && !d.stats && !d.resid && !(d.flags & GSSD_CONV_POOL2) &&
+                       d.split_n % 4 == 0 && (d.Cout - d.split_n) % 4 == 0 && *on_x6;
+    const bool ok = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.dil == 1 && d.cin_g % 16 == 0 && wino_nb(cout_g, d.groups) != 0 &&
+                    (d.out_mode == GSSD_OUT_NHWC || heads) && !d.alpha && !d.gate && !d.out2 && !d.relu && d.split_k <= 1 && !d.m_per_image &&
+                    d.in_stride % 4 == 0 && d.in_ch_off % 4 == 0 && ((uintptr_t)d.wgt_wino % 16) == 0 &&
+                    (long long)d.B * d.H * d.W * d.in_stride < (1ll << 30);     // 32-bit BYTE offsets into the input
+    return ok && !((d.flags & GSSD_CONV_POOL2) && (d.resid || !d.pool_sign));
 }
 
 }  // namespace
 
 // returns 1 when the descriptor is not a Winograd shape (or carries no transformed weights)
-int gssd_try_conv_wino(const gssd_conv_desc& d, hipStream_t stream) {
-    if (!d.wgt_wino) return 1;
+int gssd_try_conv_wino(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    bool on_x6 = false;
+    if (!wino_takes(d, &on_x6)) return 1;
     const int cout_g = d.Cout / d.groups;
-    // (GSSD_OUT_HEADS: only the form conv_wino_x6.hip takes -- one reduction slice, no batch sums / residual / pooling, both sides of split_n whole quads)
-    const bool heads = d.out_mode == GSSD_OUT_HEADS && d.out_b && d.split_k <= 1 && !d.stats && !d.resid && !(d.flags & GSSD_CONV_POOL2) &&
-                       d.split_n % 4 == 0 && (d.Cout - d.split_n) % 4 == 0 && gssd_wino_x6_plane_elems(cout_g, d.groups, d.cin_g) > 0 && gssd_wino_x6_wanted(d);
-    const bool ok = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.dil == 1 && d.cin_g % 16 == 0 && wino_nb(cout_g, d.groups) != 0 &&
-                    (d.out_mode == GSSD_OUT_NHWC || heads) && !d.alpha && !d.gate && !d.out2 && !d.relu && d.split_k <= 1 && !d.m_per_image &&
-                    d.in_stride % 4 == 0 && d.in_ch_off % 4 == 0 && ((uintptr_t)d.wgt_wino % 16) == 0 &&
-                    (long long)d.B * d.H * d.W * d.in_stride < (1ll << 30);     // 32-bit BYTE offsets into the input
-    if (!ok) return 1;
-    if ((d.flags & GSSD_CONV_POOL2) && (d.resid || !d.pool_sign)) return 1;
-    // the same transforms with the 16 GEMMs on the bf16 matrix cores (three-plane operands, conv_wino_x6.hip): its U planes lie behind the fp32 U
-    if (gssd_wino_x6_plane_elems(cout_g, d.groups, d.cin_g) > 0 && gssd_wino_x6_wanted(d))
-        return gssd_launch_conv_wino_x6(d, d.wgt_wino + 16ll * d.groups * wino_u_rows(cout_g, d.groups) * d.cin_g, stream);
+    if (on_x6) return gssd_launch_conv_wino_x6(d, d.wgt_wino + 16ll * d.groups * wino_u_rows(cout_g, d.groups) * d.cin_g, c);
     // NB = 64 holds 256 accumulators per lane and has no registers left for a prefetched patch across the epilogue: one item
     // per workgroup there; the NB = 32 variant (conv2_2: two chunks per item) runs persistent.  (Round 2: the persistent NB = 32
     // variant forced onto the 64 / 128-channel layers measures 15-30 % slower -- conv3_2 489 vs 415 us, conv4_2 436 vs 336 us: it
     // transforms every input tile once per 32-channel block.)
     const int epi = (d.flags & GSSD_CONV_POOL2) ? 2 : d.resid ? 1 : 0;
 #define WINO_GO(NB_, P_)                                                                                              \
-    (d.in_scale ? (epi == 2 ? launch_wino<NB_, true, P_, 2>(d, stream)                                               \
-                            : epi == 1 ? launch_wino<NB_, true, P_, 1>(d, stream) : launch_wino<NB_, true, P_, 0>(d, stream))   \
-                : (epi == 2 ? launch_wino<NB_, false, P_, 2>(d, stream)                                              \
-                            : epi == 1 ? launch_wino<NB_, false, P_, 1>(d, stream) : launch_wino<NB_, false, P_, 0>(d, stream)))
+    (d.in_scale ? (epi == 2 ? launch_wino<NB_, true, P_, 2>(d, c)                                               \
+                            : epi == 1 ? launch_wino<NB_, true, P_, 1>(d, c) : launch_wino<NB_, true, P_, 0>(d, c))   \
+                : (epi == 2 ? launch_wino<NB_, false, P_, 2>(d, c)                                              \
+                            : epi == 1 ? launch_wino<NB_, false, P_, 1>(d, c) : launch_wino<NB_, false, P_, 0>(d, c)))
     if (wino_nb(cout_g, d.groups) == 64) return WINO_GO(64, false);
     return WINO_GO(32, true);
 #undef WINO_GO
@@ -577,16 +585,8 @@ extern "C" long long gssd_winograd_weight_elems(int Cout, int groups, int cin_g)
 }
 
 extern "C" int gssd_conv_wino_x6_takes(const gssd_conv_desc* d) {
-    if (!d || !d->wgt_wino || !gssd_wino_x6_enabled()) return 0;
-    const int cout_g = d->Cout / d->groups;
-    const bool heads = d->out_mode == GSSD_OUT_HEADS && d->split_k <= 1      // (out / out_b may still be unset when a plan names its kernels)
-                       && !d->stats && !d->resid && !(d->flags & GSSD_CONV_POOL2) &&
-                       d->split_n % 4 == 0 && (d->Cout - d->split_n) % 4 == 0;
-    const bool ok = d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dil == 1 && d->cin_g % 16 == 0 && wino_nb(cout_g, d->groups) != 0 &&
-                    (d->out_mode == GSSD_OUT_NHWC || heads) && !d->alpha && !d->gate && !d->out2 && !d->relu && d->split_k <= 1 && !d->m_per_image &&
-                    d->in_stride % 4 == 0 && d->in_ch_off % 4 == 0 && (long long)d->B * d->H * d->W * d->in_stride < (1ll << 30);
-    if (!ok || ((d->flags & GSSD_CONV_POOL2) && (d->resid || !d->pool_sign))) return 0;
-    return gssd_wino_x6_plane_elems(cout_g, d->groups, d->cin_g) > 0 && gssd_wino_x6_wanted(*d);
+    bool on_x6 = false;
+    return d && wino_takes(*d, &on_x6) && on_x6;
 }
 
 extern "C" int gssd_winograd_weight_f32(const float* w_packed, float* U, int Cout, int groups, int cin_g, int row_stride,

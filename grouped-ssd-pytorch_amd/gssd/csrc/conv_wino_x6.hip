@@ -642,8 +642,10 @@ __global__ void wino_x6_weight_kernel(const float* __restrict__ w, u16* __restri
 }
 
 template <int NBT, bool XF, int EPI, bool PSEL, bool F16>
-int launch_wino_x6_impl(const gssd_conv_desc& d, const u16* Ux, hipStream_t stream) {
+int launch_wino_x6_impl(const gssd_conv_desc& d, const u16* Ux, gssd_conv_ctx& c) {
     constexpr int NB = 16 * NBT, NPX = F16 ? 2 : 3;
+    // (one name per tile, fused input transform and pooled epilogue; the plane format and the padding form are not part of it)
+    if (c.name) return gssd_name_kernel(c, "conv_wino_x6<%d>%s%s", NB, XF ? "" : "/plain", EPI == 2 ? "/pool2" : "");
     WinoX6Params p;
     p.in = d.in;
     p.Ux = Ux;
@@ -691,28 +693,28 @@ int launch_wino_x6_impl(const gssd_conv_desc& d, const u16* Ux, hipStream_t stre
     if (gx < 1) gx = 1;
     if (gx > nitems) gx = nitems;
     p.gx = gx;
-    hipLaunchKernelGGL(kern, dim3(gx * p.npairs), dim3(512), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(gx * p.npairs), dim3(512), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 // the two-plane fp16 form: launches marked GSSD_CONV_F16_OK by the caller (operands inside fp16's range; never inferred); never a data gradient (EPI 1)
 template <int NBT, bool XF, int EPI, bool PSEL>
-int launch_wino_x6_sel(const gssd_conv_desc& d, const u16* Ux, hipStream_t stream) {
+int launch_wino_x6_sel(const gssd_conv_desc& d, const u16* Ux, gssd_conv_ctx& c) {
     if constexpr (EPI != 1) {
         if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) {
             const int cout_g = d.Cout / d.groups;
             const long long nb = cout_g > 32 ? 64 : 32, ncb = (cout_g + nb - 1) / nb, nchunks = (d.cin_g + 31) / 32;
-            return launch_wino_x6_impl<NBT, XF, EPI, PSEL, true>(d, Ux + (long long)d.groups * ncb * nchunks * 16 * NP * nb * 32, stream);
+            return launch_wino_x6_impl<NBT, XF, EPI, PSEL, true>(d, Ux + (long long)d.groups * ncb * nchunks * 16 * NP * nb * 32, c);
         }
     }
-    return launch_wino_x6_impl<NBT, XF, EPI, PSEL, false>(d, Ux, stream);
+    return launch_wino_x6_impl<NBT, XF, EPI, PSEL, false>(d, Ux, c);
 }
 
 template <int NBT, bool XF, int EPI>
-int launch_wino_x6(const gssd_conv_desc& d, const u16* Ux, hipStream_t stream) {
-    if (XF && wx6_pad_off(d)) return launch_wino_x6_sel<NBT, XF, EPI, false>(d, Ux, stream);
-    return launch_wino_x6_sel<NBT, XF, EPI, true>(d, Ux, stream);
+int launch_wino_x6(const gssd_conv_desc& d, const u16* Ux, gssd_conv_ctx& c) {
+    if (XF && wx6_pad_off(d)) return launch_wino_x6_sel<NBT, XF, EPI, false>(d, Ux, c);
+    return launch_wino_x6_sel<NBT, XF, EPI, true>(d, Ux, c);
 }
 
 }  // namespace
@@ -742,6 +744,7 @@ int gssd_wino_x6_mode() {
     }();
     return mode;
 }
+
 bool gssd_wino_x6_enabled() { return gssd_wino_x6_mode() != 0; }
 
 // the shapes it is used for by default: where it beat conv_wino.hip in a same-box A/B at batch 32 (scripts/wino_x6_ab.sh, round 5: conv3_1 176 vs
@@ -764,15 +767,15 @@ bool gssd_wino_x6_wanted(const gssd_conv_desc& d) {
 }
 
 // called by gssd_try_conv_wino() once the descriptor is known to be a Winograd shape: `Ux` = the three-plane U behind the fp32 U
-int gssd_launch_conv_wino_x6(const gssd_conv_desc& d, const void* Ux, hipStream_t stream) {
+int gssd_launch_conv_wino_x6(const gssd_conv_desc& d, const void* Ux, gssd_conv_ctx& c) {
     const u16* ux = reinterpret_cast<const u16*>(Ux);
     const int epi = (d.flags & GSSD_CONV_POOL2) ? 2 : d.resid ? 1 : 0;
     const bool wide = wx6_nb(d.Cout / d.groups) == 64;
 #define WX6_GO(NBT_)                                                                                                                        \
-    (d.in_scale ? (epi == 2 ? launch_wino_x6<NBT_, true, 2>(d, ux, stream) : epi == 1 ? launch_wino_x6<NBT_, true, 1>(d, ux, stream)       \
-                                                                                       : launch_wino_x6<NBT_, true, 0>(d, ux, stream))      \
-                : (epi == 2 ? launch_wino_x6<NBT_, false, 2>(d, ux, stream) : epi == 1 ? launch_wino_x6<NBT_, false, 1>(d, ux, stream)     \
-                                                                                        : launch_wino_x6<NBT_, false, 0>(d, ux, stream)))
+    (d.in_scale ? (epi == 2 ? launch_wino_x6<NBT_, true, 2>(d, ux, c) : epi == 1 ? launch_wino_x6<NBT_, true, 1>(d, ux, c)       \
+                                                                                       : launch_wino_x6<NBT_, true, 0>(d, ux, c))      \
+                : (epi == 2 ? launch_wino_x6<NBT_, false, 2>(d, ux, c) : epi == 1 ? launch_wino_x6<NBT_, false, 1>(d, ux, c)     \
+                                                                                        : launch_wino_x6<NBT_, false, 0>(d, ux, c)))
     return wide ? WX6_GO(4) : WX6_GO(2);
 #undef WX6_GO
 }

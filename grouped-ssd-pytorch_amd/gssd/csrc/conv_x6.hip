@@ -1040,21 +1040,23 @@ __global__ void conv_x6_pack_kernel(const float* __restrict__ w, u16* __restrict
 }
 
 template <int BN, bool XF>
-int launch(const gssd_conv_desc& d, int M, hipStream_t stream) {
+int launch(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_x6<%d>", BN);
     static unsigned attr_mask = 0;
     auto kern = conv_x6_kernel<BN, XF>;
     if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, Cfg<BN>::LDS_BYTES + 4096)) return rc;
     const int cout_g = d.Cout / d.groups;
     const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
     const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
-    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), Cfg<BN>::LDS_BYTES + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), stream, d, M, ntn, mtiles, plane);
+    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), Cfg<BN>::LDS_BYTES + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), c.stream, d, M, ntn, mtiles, plane);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 #if X6_V2
 template <int BN, bool XF, bool F16>
-int launch2_impl(const gssd_conv_desc& d, int M, hipStream_t stream) {
+int launch2_impl(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_x6<%d>", BN);
     static unsigned attr_mask = 0;
     auto kern = conv_x6_v2_kernel<BN, XF, F16>;
     constexpr int lds = Cfg2<BN>::LDS_BYTES;
@@ -1062,15 +1064,15 @@ int launch2_impl(const gssd_conv_desc& d, int M, hipStream_t stream) {
     const int cout_g = d.Cout / d.groups;
     const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
     const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
-    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), lds + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), stream, d, M, ntn, mtiles, plane);
+    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), lds + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), c.stream, d, M, ntn, mtiles, plane);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 // the three-MFMA fp16 form: only launches the CALLER flags GSSD_CONV_F16_OK (operands inside fp16's range: include/gssd_hip.h) -- never inferred
 template <int BN, bool XF>
-int launch2(const gssd_conv_desc& d, int M, hipStream_t stream) {
-    if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) return launch2_impl<BN, XF, true>(d, M, stream);
-    return launch2_impl<BN, XF, false>(d, M, stream);
+int launch2(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
+    if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) return launch2_impl<BN, XF, true>(d, M, c);
+    return launch2_impl<BN, XF, false>(d, M, c);
 }
 #endif
 
@@ -1161,18 +1163,18 @@ extern "C" int gssd_conv_x6_takes(const gssd_conv_desc* dp) {
     return 1;
 }
 
-int gssd_try_conv_x6(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_conv_x6(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     if (!gssd_conv_x6_takes(&d)) return 1;
     const long long Mll = (long long)d.B * d.Ho * d.Wo;
     const int M = (int)Mll;
     switch (gssd_conv_x6_tile(d.Cout / d.groups, d.groups, Mll)) {
 #if X6_V2
-        case 64: return x6_in_xf(d) ? launch2<64, true>(d, M, stream) : launch2<64, false>(d, M, stream);
-        case 128: return x6_in_xf(d) ? launch2<128, true>(d, M, stream) : launch2<128, false>(d, M, stream);
+        case 64: return x6_in_xf(d) ? launch2<64, true>(d, M, c) : launch2<64, false>(d, M, c);
+        case 128: return x6_in_xf(d) ? launch2<128, true>(d, M, c) : launch2<128, false>(d, M, c);
 #else
-        case 64: return x6_in_xf(d) ? launch<64, true>(d, M, stream) : launch<64, false>(d, M, stream);
-        case 128: return x6_in_xf(d) ? launch<128, true>(d, M, stream) : launch<128, false>(d, M, stream);
+        case 64: return x6_in_xf(d) ? launch<64, true>(d, M, c) : launch<64, false>(d, M, c);
+        case 128: return x6_in_xf(d) ? launch<128, true>(d, M, c) : launch<128, false>(d, M, c);
 #endif
-        default: return x6_in_xf(d) ? launch<256, true>(d, M, stream) : launch<256, false>(d, M, stream);
+        default: return x6_in_xf(d) ? launch<256, true>(d, M, c) : launch<256, false>(d, M, c);
     }
 }

@@ -417,7 +417,8 @@ static int slot_shape(const gssd_conv_desc& d) {
 extern "C" int gssd_gemm_slot_takes(const gssd_conv_desc* d) { return d && slot_shape(*d) ? 1 : 0; }
 
 template <int BN, bool SWAP>
-static int launch_slot(const gssd_conv_desc& d, hipStream_t stream) {
+static int launch_slot(const gssd_conv_desc& d, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "gemm_slot<128x%d>", BN);
     const long long M = (long long)(d.m_per_image ? 1 : d.B) * d.Ho * d.Wo;
     const int images = d.m_per_image ? d.B : 1;
     const int ntn = (d.Cout + BN - 1) / BN, mtiles = (int)((M + BM - 1) / BM);
@@ -431,13 +432,13 @@ static int launch_slot(const gssd_conv_desc& d, hipStream_t stream) {
     } else {
         blocks = ((mtiles * ntn + 7) / 8) * 8;
     }
-    hipLaunchKernelGGL((gemm_slot_kernel<BN, SWAP>), dim3(blocks, 1, images), dim3(256), smem, stream, d, (int)M, ntn, mtiles);
+    hipLaunchKernelGGL((gemm_slot_kernel<BN, SWAP>), dim3(blocks, 1, images), dim3(256), smem, c.stream, d, (int)M, ntn, mtiles);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 // returns 1 when the descriptor is not a plain 1x1 / GEMM shape worth a slot stream (the caller falls through to conv_igemm)
-int gssd_try_gemm_slot(const gssd_conv_desc& d, hipStream_t stream) {
+int gssd_try_gemm_slot(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     const int cls = slot_shape(d);
     // channel-major accumulators (16-byte epilogue accesses) for NHWC outputs with 16-byte aligned channel vectors; GSSD_GEMM_SLOT_SWAP=0
     // keeps the pixel-major form everywhere (ablation)
@@ -447,7 +448,7 @@ int gssd_try_gemm_slot(const gssd_conv_desc& d, hipStream_t stream) {
     const bool swap = !no_swap && d.out_mode == GSSD_OUT_NHWC && (d.gate || d.resid) && d.Cout % 4 == 0 && d.out_stride % 4 == 0 && d.out_ch_off % 4 == 0 &&
                       ((uintptr_t)d.out % 16) == 0 && (!d.resid || ((uintptr_t)d.resid % 16) == 0) && (!d.out2 || ((uintptr_t)d.out2 % 16) == 0) &&
                       (!d.bias || ((uintptr_t)d.bias % 16) == 0) && (!d.alpha || ((uintptr_t)d.alpha % 16) == 0) && d.out_batch_stride % 4 == 0;
-    if (cls == 256) return swap ? launch_slot<256, true>(d, stream) : launch_slot<256, false>(d, stream);
-    if (cls == 128) return swap ? launch_slot<128, true>(d, stream) : launch_slot<128, false>(d, stream);
+    if (cls == 256) return swap ? launch_slot<256, true>(d, c) : launch_slot<256, false>(d, c);
+    if (cls == 128) return swap ? launch_slot<128, true>(d, c) : launch_slot<128, false>(d, c);
     return 1;
 }

@@ -12,6 +12,18 @@ void gssd_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+// gssd_conv2d_kernel_name's sink (common.h): the whole name or an error, never a truncated one
+int gssd_name_kernel(const gssd_conv_ctx& c, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    const int n = vsnprintf(c.name, c.cap > 0 ? (size_t)c.cap : 0, fmt, ap);
+    va_end(ap);
+    if (n >= 0 && n < c.cap) return GSSD_OK;
+    if (c.cap > 0) c.name[0] = 0;
+    gssd_set_error("gssd_conv2d_kernel_name: the name needs %d bytes, the buffer holds %d", n + 1, c.cap);
+    return GSSD_EINVAL;
+}
+
 // the library's one read of GSSD_X6_F16 (common.h)
 bool gssd_x6_f16_enabled() {
     static const bool on = !gssd_env_off("GSSD_X6_F16");

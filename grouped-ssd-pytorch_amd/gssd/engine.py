@@ -299,19 +299,29 @@ class _Plan(_PlanBase, PlanGraphMixin, PlanOpsMixin, PlanExecMixin):
         self._place_sn_step()
         self._place_branch0()
         self._fuse_input_pack()
+        self._name_convs()
 
     # ------------------------------------------------------------------------------------------------
     def _add(self, fn, args, keep=None, tag=None):
         d = None
         if tag is None and fn in (lib.gssd_conv2d_nhwc_f32, lib.gssd_conv2d_nhwc_bf16):
             d = keep[0] if isinstance(keep, tuple) else keep
-            tag = conv_tag(d, 3 if (d.cin_g in (4, 8) and d.groups == 4 and d.H == 300) else None,
-                           bf16=fn is lib.gssd_conv2d_nhwc_bf16)
+            tag = (None, 0.0, 0.0)                   # a conv: named by _name_convs() once the plan's descriptors are final
         if tag is not None:
             tag = Tag(tag)
             tag.layer = getattr(self, '_layer', None)
             tag.desc = d
         self.steps.append(_Step(fn, args, keep, tag, getattr(self, '_sid', 0), self.__dict__.pop('_pending_wait', None)))
+
+    def _name_convs(self):
+        """Last step of a plan build: every conv step gets its (kernel instance, FLOPs, bytes) from the library's dispatcher
+        (plan_common.conv_tag), now that the heads have their outputs and conv1_1 its final input form.  A descriptor the
+        entry point would refuse raises GssdError here, not at the first launch."""
+        for st in self.steps:
+            if st.tag is not None and st.tag[0] is None:
+                tag = Tag(conv_tag(st.tag.desc, bf16=st.fn is lib.gssd_conv2d_nhwc_bf16))
+                tag.layer, tag.desc = st.tag.layer, st.tag.desc
+                st.tag = tag
 
     def _abuf(self, *shape):
         """Activation buffer in the plan's storage type (fp32, or bf16 in configs[4] mode)."""
@@ -417,6 +427,7 @@ class _PlanVanilla(_Plan):
             off += Hs * Hs * A
         assert off == self.P, off
         self._finish_heads()
+        self._name_convs()
 
     def _conv_relu(self, name, conv, x, H, Cin):
         B = self.B
@@ -456,6 +467,7 @@ class SelfAttnOp(_Plan):
         self.x = self._buf(B, H, H, Cc)
         self._setup_spectral_norm([('self_attn_list', holder.self_attn_list)])
         self.out, self.out2 = self._self_attn('self_attn_list', 0, self.x, H, Cc, need_out2=True, want_map=True)
+        self._name_convs()
 
     def run(self, x_nhwc):
         self.generation += 1

@@ -125,6 +125,7 @@ class _PlanPixelLink(_Plan):
         self._final_out = nptr + 5                              # argument index of out1 (out2 follows)
         self._add(fn, [f.data_ptr() for f in feats] + [0] * (nptr - len(feats)) + wargs, keep=(w1, b1, w2, b2, feats))
         self.rec.append(('plfinal', dict(feats=feats, H=Ho, final_1=net.final_1, final_2=net.final_2)))
+        self._name_convs()
 
     # ------------------------------------------------------------------------------------------------
     def _identity_relu(self, Cc):

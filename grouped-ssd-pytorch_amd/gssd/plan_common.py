@@ -2,8 +2,7 @@
 plan_exec): the layer tables of models/ssd_multiphase_custom_group.py:434-490, the GSSD_* environment switches, the step / tag records."""
 import ctypes as C
 import os
-import torch
-from . import _lib, ops
+from . import _lib
 from ._lib import lib
 
 VGG_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'C', 512, 512, 512, 'M', 512, 512, 512]
@@ -66,72 +65,25 @@ class _Step:
         self.fn, self.args, self.keep, self.tag, self.sid, self.wait = fn, args, keep, tag, sid, wait
 
 
-def conv_tag(d, real_cin_g=None, bf16=False):
-    """(kernel instance, algorithmic FLOPs, algorithmic bytes) of one gssd_conv2d launch; the instance name
-    mirrors the tile selection in csrc/conv_igemm.hip so it can be matched against rocprofv3's kernel names."""
-    cout_g = d.Cout // d.groups
-    inst = '128x128' if cout_g > 64 else '128x64' if cout_g > 32 else '128x32' if cout_g > 16 else '128x16'
-    if cout_g > 64:       # same wave-quantisation rule as gssd_conv2d_nhwc_f32
-        mt = -(-(d.Ho * d.Wo * (1 if d.m_per_image else d.B)) // 128)
-        z = d.B if d.m_per_image else d.split_k
-        b128 = mt * d.groups * (-(-cout_g // 128)) * z
-        b64 = mt * d.groups * (-(-cout_g // 64)) * z
-        e128 = b128 / (-(-b128 // 512) * 512)
-        e64 = 0.94 * b64 / (-(-b64 // 768) * 768)
-        if e64 > e128 or d.K <= 256:
-            inst = '128x64'
-    # small maps: 32- / 64-row tiles with a three-stage K loop (csrc/conv_igemm.hip, csrc/conv_bf16.hip: the same host rule)
-    Ms, Mtot = d.Ho * d.Wo * (1 if d.m_per_image else d.B), d.Ho * d.Wo * d.B
-    if (cout_g > 32 and d.split_k == 1 and Mtot <= 4096 and os.environ.get('GSSD_NO_SMALL_TILES') is None
-            and not (d.out_mode == _lib.OUT_SPLIT_T and d.split_n % 64 != 0)):
-        inst = '32x64' if (Mtot <= 512 or (d.m_per_image and Ms <= 128)) else '64x64'
-    if (bf16 and os.environ.get('GSSD_BF16_BIG_TILES', '0') == '1' and not d.m_per_image and d.split_k == 1 and d.B * d.Ho * d.Wo >= 8192
-            and cout_g % 128 == 0 and d.K % 64 == 0 and d.K >= 256
-            and (d.out_mode == _lib.OUT_NHWC or (d.out_mode == _lib.OUT_SPLIT_T and d.split_n % 128 == 0))):
-        inst = '256x128'                                 # csrc/conv_bf16.hip: opt-in experiment (measured slower, round 5)
-    name = ('conv_bf16<' if bf16 else 'conv_igemm<') + inst + '>'
-    if not bf16 and d.wgt_patch and lib.gssd_conv_patch_x6_takes(C.byref(d)) == 1:      # first in gssd_conv2d_nhwc_f32's dispatch order
-        M6 = d.B * d.Ho * d.Wo
-        return ('conv_patch_x6<128>', 2.0 * M6 * d.Cout * 9 * d.cin_g, 4.0 * (d.B * d.H * d.W * d.cin_g + M6 * d.Cout + d.Cout * 9 * d.cin_g))
-    if not bf16 and d.wgt_x6 and lib.gssd_conv_x6_takes(C.byref(d)) == 1:
-        M6 = d.B * d.Ho * d.Wo
-        flops = 2.0 * M6 * d.Cout * d.KH * d.KW * d.cin_g
-        return (f'conv_x6<{ops.x6_tile(cout_g, d.groups, M6)}>', flops, 4.0 * (d.B * d.H * d.W * d.cin_g * d.groups + M6 * d.Cout + d.Cout * d.KH * d.KW * d.cin_g))
-    if bf16:
-        if (d.groups == 4 and d.KH == 3 and d.stride == 1 and d.pad == 1 and d.dil == 1 and d.H * d.W >= 75 * 75
-                and (d.cin_g, cout_g) in ((8, 16), (16, 16), (16, 32), (32, 32)) and not d.m_per_image and d.split_k == 1
-                and d.flags in (0, _lib.CONV_POOL2)):
-            name = f'conv_thin_bf16<{d.cin_g},{cout_g}>' + ('/pool2' if d.flags & _lib.CONV_POOL2 else '')   # gssd_try_conv_thin_bf16
-    elif (d.groups == 4 and d.KH == 3 and d.stride == 1 and d.pad == 1 and d.dil == 1 and d.H * d.W >= 75 * 75
-            and (d.cin_g, cout_g) in ((4, 16), (16, 16), (16, 32)) and not d.m_per_image and d.split_k == 1):
-        name = f'conv_thin<{d.cin_g},{cout_g}>'          # gssd_try_conv_thin (csrc/conv_thin.hip)
-        if d.wgt_wino and (d.cin_g, cout_g) == (16, 32) and os.environ.get('GSSD_CONV21_WINO', '1') != '0':
-            name = 'conv_wino<32>'                       # conv2_1 with Winograd weights: handed on to gssd_try_conv_wino
-        if d.wgt_wino and (d.cin_g, cout_g) == (16, 16) and not d.resid:
-            name = 'conv_thin_wino<16,16>'               # gssd_try_conv_thin_wino (csrc/conv_thin_wino.hip)
-    elif (d.wgt_wino and ops.winograd_eligible(d.KH, d.stride, d.pad, d.dil, d.cin_g, cout_g, d.groups) and not d.m_per_image
-          and d.split_k <= 1 and not d.relu):
-        name = f'conv_wino<{64 if (cout_g % 64 == 0 or (cout_g % 32 != 0 and cout_g > 32)) else 32}>'   # gssd_try_conv_wino
-    igemm_name = ('conv_bf16<' if bf16 else 'conv_igemm<') + inst + '>'
-    if name.startswith('conv_wino<') and lib.gssd_conv_wino_x6_takes(C.byref(d)) == 1:
-        name = f'conv_wino_x6<{64 if cout_g > 32 else 32}>'      # csrc/conv_wino_x6.hip: the library's own host rule
-    elif name.startswith('conv_wino<') and d.out_mode == _lib.OUT_HEADS:
-        name = igemm_name                                        # (the fp32 Winograd kernel has no heads epilogue: gssd_try_conv_wino hands it on)
-    if not bf16 and lib.gssd_conv_thin_x6_takes(C.byref(d)) == 1:
-        name = f'conv_thin_x6<{d.cin_g},{cout_g}>'               # csrc/conv_thin_x6.hip: first in gssd_conv2d_nhwc_f32's dispatch order
-    if name.startswith(('conv_wino<', 'conv_wino_x6<', 'conv_thin_x6<')):
-        # one name per kernel SYMBOL, as rocprofv3 --stats groups them (template <tile, fused input transform, ..., pooled epilogue>)
-        name += ('' if d.in_scale else '/plain') + ('/pool2' if d.flags & _lib.CONV_POOL2 else '')
-    if bf16 and name.startswith('conv_bf16'):
-        bm = lib.gssd_conv_flat_bf16_takes(C.byref(d))      # csrc/conv_flat_bf16.hip: the library's own host rule
-        if bm:
-            name = f'conv_flat_bf16<{d.cin_g},{min(cout_g, 128) if cout_g % 128 == 0 else 64},{bm}>'
-    if not bf16 and name.startswith('conv_igemm') and lib.gssd_gemm_slot_takes(C.byref(d)) == 1:
-        name = 'gemm_slot<128x128>'                      # gssd_try_gemm_slot (csrc/gemm_slot.hip): the library's own host rule
+def conv_cost(name, d):
+    """(algorithmic FLOPs, algorithmic bytes) of the conv launch ``name`` runs for descriptor ``d``."""
     M = d.B * d.Ho * d.Wo
-    cin_g = real_cin_g if real_cin_g is not None else d.cin_g
-    flops = 2.0 * M * d.Cout * d.KH * d.KW * cin_g
-    esz = 2.0 if bf16 else 4.0
-    out_elems = M * d.Cout // 4 if (d.flags & _lib.CONV_POOL2) else M * d.Cout       # pooled raw output: a quarter of the map
-    byts = esz * (d.B * d.H * d.W * cin_g * d.groups + out_elems + d.Cout * d.KH * d.KW * cin_g)
-    return (name, flops, byts)
+    if name.startswith('conv_patch_x6<'):
+        return 2.0 * M * d.Cout * 9 * d.cin_g, 4.0 * (d.B * d.H * d.W * d.cin_g + M * d.Cout + d.Cout * 9 * d.cin_g)
+    if name.startswith('conv_x6<'):
+        return (2.0 * M * d.Cout * d.KH * d.KW * d.cin_g,
+                4.0 * (d.B * d.H * d.W * d.cin_g * d.groups + M * d.Cout + d.Cout * d.KH * d.KW * d.cin_g))
+    cin_g = 3 if (d.cin_g in (4, 8) and d.groups == 4 and d.H == 300) else d.cin_g       # conv1_1: 3 real channels per group in 4 / 8 stored
+    esz = 2.0 if '_bf16<' in name else 4.0                                               # (every kernel of the bf16 entry point is named so)
+    out_elems = M * d.Cout // 4 if (d.flags & _lib.CONV_POOL2) else M * d.Cout           # pooled raw output: a quarter of the map
+    return 2.0 * M * d.Cout * d.KH * d.KW * cin_g, esz * (d.B * d.H * d.W * cin_g * d.groups + out_elems + d.Cout * d.KH * d.KW * cin_g)
+
+
+def conv_tag(d, bf16=False):
+    """(kernel instance, algorithmic FLOPs, algorithmic bytes) of one gssd_conv2d launch.  The name is the dispatcher's own statement
+    (gssd_conv2d_kernel_name walks the launch path and names the template instance it arrives at; rocprofv3's kernel symbols carry the same
+    arguments); a descriptor the entry point would refuse raises GssdError."""
+    buf = C.create_string_buffer(64)
+    _lib.check(lib.gssd_conv2d_kernel_name(C.byref(d), int(bf16), buf, len(buf)))
+    name = buf.value.decode()
+    return (name,) + conv_cost(name, d)

@@ -238,6 +238,15 @@ int gssd_conv_x6_takes(const gssd_conv_desc* d);
  * (A flag rather than new descriptor fields: the struct's layout is part of the ABI.) */
 #define GSSD_CONV_RESID_XF 512
 int gssd_conv2d_nhwc_bf16(const gssd_conv_desc* d, gssd_stream_t stream);
+/* Name of the kernel instance gssd_conv2d_nhwc_f32 (bf16 == 0) or gssd_conv2d_nhwc_bf16 (bf16 != 0) would launch for *d, as a
+ * NUL-terminated string in buf[cap].  Makes no HIP runtime call and touches no device state.  Returns what the launch would return
+ * for an invalid descriptor (GSSD_EINVAL, gssd_last_error set), GSSD_OK otherwise; a name that does not fit cap is GSSD_EINVAL too,
+ * never a truncated name.  The name comes from the launch path itself -- the entry point's validation, its chain of kernels in
+ * order, the environment switches they read -- which names the template instance it arrives at instead of launching it:
+ * conv_igemm<BMxBN>, conv_bf16<BMxBN>, gemm_slot<128x128>, conv_x6<BN>, conv_patch_x6<128>, conv_thin<ci,co>, conv_thin_wino<16,16>,
+ * conv_thin_bf16<ci,co>[/pool2], conv_flat_bf16<cin_g,cout tile,pixels>, and conv_wino<NB>, conv_wino_x6<NB>, conv_thin_x6<ci,co> with
+ * "/plain" (no fused input transform) and "/pool2" (GSSD_CONV_POOL2). */
+int gssd_conv2d_kernel_name(const gssd_conv_desc* d, int bf16, char* buf, int cap);
 /* OIHW fp32 -> packed bf16 rows [Cout][Kpad] (cin_g_pad, Kpad multiples of 8); fp32 -> bf16 array cast (round to nearest even) */
 int gssd_pack_conv_weight_bf16(const float* w_oihw, void* w_packed, int Cout, int cin_g, int KH, int KW, int cin_g_pad, int Kpad,
                                gssd_stream_t stream);
@@ -879,7 +888,8 @@ int gssd_plan_run(const gssd_plan_op* ops, int n_ops, const gssd_stream_t* strea
 int gssd_conv_wino_x6_takes(const gssd_conv_desc* d);
 /* 1 when gssd_conv2d_nhwc_f32 runs the descriptor on the patch-staged three-plane direct conv (csrc/conv_thin_x6.hip, round 6): the grouped 3x3
  * trunk layers with 16 -> 16, 16 -> 32 and 32 -> 32 channels per group on maps of >= 75 x 75 pixels -- conv1_2, conv2_1, conv2_2 of
- * models/ssd_multiphase_custom_group.py:434-460 -- plain or with the fused producer BatchNorm + ReLU / batch sums / GSSD_CONV_POOL2 epilogue
+ * models/ssd_multiphase_custom_group.py:434-460 -- and, for launches flagged GSSD_CONV_F16_OK only, 32 -> 64 (conv3_1; GSSD_THIN_X6_CONV31=0
+ * or GSSD_X6_F16=0: not that one) -- plain or with the fused producer BatchNorm + ReLU / batch sums / GSSD_CONV_POOL2 epilogue
  * (no residual: their data gradients stay with the fp32 kernels).  GSSD_THIN_X6=0: never. */
 int gssd_conv_thin_x6_takes(const gssd_conv_desc* d);
 /* 1 when gssd_conv2d_nhwc_f32 runs the descriptor (with or without the flag set) in its GSSD_CONV_IN_NCHW3 form */

@@ -114,6 +114,177 @@ def test_conv_x6_host_rules():
     assert desc(m_per_image=True, **dict(sp, in_batch_stride=400 * 256)) == 0
 
 
+def _kernel_name(bf16=False, cap=64, **kw):
+    """(code, name) of gssd_conv2d_kernel_name for an ops.make_conv_desc(**kw) descriptor over 16-byte aligned host addresses (nothing
+    dereferences them); P in a keyword's value stands for such an address."""
+    from gssd import _lib, ops
+    kw = {k: (_ADDR if v is P else v) for k, v in kw.items()}
+    d, _, _ = ops.make_conv_desc(_ADDR, _ADDR, _ADDR, **kw)
+    buf = ctypes.create_string_buffer(b'?' * (max(cap, 1) - 1), max(cap, 1))
+    return _lib.lib.gssd_conv2d_kernel_name(ctypes.byref(d), int(bf16), buf, cap), buf.value.decode()
+
+
+P = object()
+_ADDR = torch.zeros(64, dtype=torch.float32)
+_POOL2, _F16, _F32OUT, _NCHW3, _GCAT, _PLANES, _RXF = 8, 32, 1, 64, 128, 256, 512          # GSSD_CONV_* flags (include/gssd_hip.h)
+_XF = dict(in_scale=P, in_shift=P, in_pad=P)
+# grouped 3x3 trunk layers (4 groups), dense 3x3 / 1x1 convs, the merged multibox head, the merged Self_Attn projection
+_G4 = lambda ci, co, H, B=2, **kw: dict(dict(B=B, H=H, W=H, groups=4, cin_g=ci, in_stride=4 * ci, Cout=4 * co, k=3, pad=1), **kw)
+_D3 = lambda ci, co, H, W, B=1, **kw: dict(dict(B=B, H=H, W=W, cin_g=ci, in_stride=ci, Cout=co, k=3, pad=1), **kw)
+_D1 = lambda ci, co, H, W, B=1, **kw: dict(dict(B=B, H=H, W=W, cin_g=ci, in_stride=ci, Cout=co), **kw)
+_HEAD = lambda B, **kw: _D3(512, 24, 38, 38, B, out_mode=2, out_b=P, split_n=16, out_batch_stride=8732 * 4, outb_batch_stride=8732 * 2, **kw)
+_SPLIT = lambda sn, **kw: _D1(512, 384, 64, 64, 16, out_mode=3, out_b=P, split_n=sn, out_stride=sn, out_b_stride=4096,
+                              outb_batch_stride=(384 - sn) * 4096, **kw)
+_PLANES_D = lambda obs: _D1(256, 384, 20, 20, 2, wgt_x6=P, out_mode=3, out_b=P, split_n=128, out_stride=128, out_b_stride=obs,
+                            outb_batch_stride=256 * obs, flags=_PLANES)
+_BIG = dict(B=16, H=64, W=64)                # M = 65 536 rows = 512 row tiles: one full round of 128 x 128 workgroups
+
+KERNEL_NAME_ROWS = [
+    # ---- gssd_conv2d_nhwc_f32, in dispatch order: the flags only one kernel serves ----
+    ('nchw3', False, _G4(4, 16, 300, flags=_NCHW3), 'conv_thin<4,16>'),
+    ('nchw3 declined', False, _G4(4, 32, 300, flags=_NCHW3), "EINVAL GSSD_CONV_IN_NCHW3: not conv1_1's shape"),
+    ('groupcat', False, _D1(256, 512, 19, 19, 2, wgt_x6=P, flags=_GCAT, split_n=128, out_stride=1024), 'conv_x6<128>'),
+    ('groupcat declined', False, _D1(256, 512, 19, 19, 2, flags=_GCAT, split_n=128, out_stride=1024),
+     'EINVAL GSSD_CONV_OUT_GROUPCAT: csrc/conv_x6.hip does not take this descriptor'),
+    ('resid_xf', False, _D1(256, 512, 19, 19, 2, wgt_x6=P, flags=_RXF, resid=P, **_XF), 'conv_x6<128>'),
+    ('resid_xf declined', False, _D1(256, 512, 19, 19, 2, wgt_x6=P, flags=_RXF, **_XF),
+     'EINVAL GSSD_CONV_RESID_XF: csrc/conv_x6.hip does not take this descriptor'),
+    ('x6planes', False, _PLANES_D(416), 'conv_x6<128>'),
+    ('x6planes declined', False, _PLANES_D(400), 'EINVAL GSSD_CONV_OUT_X6PLANES: csrc/conv_x6.hip does not take this descriptor'),
+    # ---- wgt_patch / wgt_x6 present and absent ----
+    ('patch', False, _D3(512, 108, 38, 38, 2, wgt_patch=P, flags=_F16), 'conv_patch_x6<128>'),
+    ('patch absent', False, _D3(512, 108, 38, 38, 2, flags=_F16), 'conv_igemm<64x64>'),
+    ('x6', False, _D1(256, 512, 19, 19, 2, wgt_x6=P), 'conv_x6<128>'),
+    ('x6 64 columns', False, _D1(256, 64, 19, 19, 2, wgt_x6=P), 'conv_x6<64>'),
+    ('x6 absent', False, _D1(256, 512, 19, 19, 2), 'conv_igemm<64x64>'),
+    # ---- the thin grouped layers: 75 x 75 against 74 x 74, fused input transform, pooled epilogue ----
+    ('thin_x6', False, _G4(16, 16, 75), 'conv_thin_x6<16,16>/plain'),
+    ('thin_x6 74', False, _G4(16, 16, 74), 'conv_igemm<128x16>'),
+    ('thin_x6 xf', False, _G4(16, 16, 75, **_XF), 'conv_thin_x6<16,16>'),
+    ('thin_x6 16,32', False, _G4(16, 32, 150), 'conv_thin_x6<16,32>/plain'),
+    ('thin_x6 pool2', False, _G4(16, 16, 150, flags=_POOL2, pool_sign=P), 'conv_thin_x6<16,16>/plain/pool2'),
+    ('thin_x6 xf pool2', False, _G4(32, 32, 150, flags=_POOL2, pool_sign=P, **_XF), 'conv_thin_x6<32,32>/pool2'),
+    ('pool2 without pool_sign', False, _G4(16, 16, 150, flags=_POOL2), 'EINVAL GSSD_CONV_POOL2: no fp32 kernel with a pooled epilogue'),
+    ('thin_x6 32,64 f16', False, _G4(32, 64, 75, flags=_F16), 'conv_thin_x6<32,64>/plain'),
+    ('32,64 not flagged', False, _G4(32, 64, 75), 'conv_igemm<128x64>'),
+    ('thin_wino', False, _G4(16, 16, 75, wgt_wino=P, wgt_row_stride=152), 'conv_thin_wino<16,16>'),       # (padded weight rows: not conv_thin_x6's)
+    ('thin_wino absent', False, _G4(16, 16, 75, wgt_row_stride=152), 'conv_igemm<128x16>'),
+    ('thin', False, _G4(4, 16, 300), 'conv_thin<4,16>'),
+    ('thin 74', False, _G4(4, 16, 74), 'conv_igemm<128x16>'),
+    # ---- Winograd: wgt_wino present and absent, the size gate of the three-plane form, the heads ----
+    ('wino 32', False, _G4(32, 32, 38, wgt_wino=P), 'conv_wino<32>/plain'),
+    ('wino absent', False, _G4(32, 32, 38), 'conv_igemm<128x32>'),
+    ('wino 32 xf pool2', False, _G4(32, 32, 38, wgt_wino=P, flags=_POOL2, pool_sign=P, **_XF), 'conv_wino<32>/pool2'),
+    ('wino pool2 without pool_sign', False, _G4(32, 32, 38, wgt_wino=P, flags=_POOL2), 'EINVAL GSSD_CONV_POOL2: no fp32 kernel with a pooled epilogue'),
+    ('wino 64 small batch', False, _G4(32, 64, 75, wgt_wino=P), 'conv_wino<64>/plain'),
+    ('wino_x6 64', False, _G4(32, 64, 75, B=8, wgt_wino=P), 'conv_wino_x6<64>/plain'),
+    ('wino_x6 64 xf pool2', False, _G4(64, 64, 75, B=8, wgt_wino=P, flags=_POOL2, pool_sign=P, **_XF), 'conv_wino_x6<64>/pool2'),
+    ('head on wino_x6', False, _HEAD(24, wgt_wino=P, flags=_F16), 'conv_wino_x6<32>/plain'),
+    ('head small batch', False, _HEAD(8, wgt_wino=P, flags=_F16), 'conv_igemm<128x32>'),
+    ('head not flagged', False, _HEAD(24, wgt_wino=P), 'conv_igemm<128x32>'),
+    # ---- the slot-scheduled GEMM and the implicit-GEMM tiles: B Ho Wo at 512 / 513 and 4096 / 4097, per-image M at 128 / 129 ----
+    ('gemm_slot', False, _D1(512, 512, 38, 38, 32), 'gemm_slot<128x128>'),
+    ('M 512', False, _D3(64, 128, 16, 32), 'conv_igemm<32x64>'),
+    ('M 513', False, _D3(64, 128, 27, 19), 'conv_igemm<64x64>'),
+    ('M 4096', False, _D3(64, 128, 64, 64), 'conv_igemm<64x64>'),
+    ('M 4097', False, _D3(64, 128, 17, 241), 'conv_igemm<128x64>'),
+    ('per image M 128', False, _D3(64, 128, 8, 16, 8, m_per_image=True), 'conv_igemm<32x64>'),
+    ('per image M 129', False, _D3(64, 128, 3, 43, 8, m_per_image=True), 'conv_igemm<64x64>'),
+    # cout_g at 16 / 17, 32 / 33, 64 / 65 (M = 65 536: 65 channels fill one round of 128 x 128 workgroups)
+    ('cout 16', False, _D3(64, 16, **_BIG), 'conv_igemm<128x16>'),
+    ('cout 17', False, _D3(64, 17, **_BIG), 'conv_igemm<128x32>'),
+    ('cout 32', False, _D3(64, 32, **_BIG), 'conv_igemm<128x32>'),
+    ('cout 33', False, _D3(64, 33, **_BIG), 'conv_igemm<128x64>'),
+    ('cout 64', False, _D3(64, 64, **_BIG), 'conv_igemm<128x64>'),
+    ('cout 65', False, _D3(64, 65, **_BIG), 'conv_igemm<128x128>'),
+    ('cout 128 wave quantisation', False, _D3(64, 128, 38, 38, 32), 'conv_igemm<128x64>'),       # 361 workgroups of 512 against 722 of 768
+    # K at 256 / 260 (K = taps x cin_g, cin_g a multiple of 4; a fused input transform keeps gemm_slot out)
+    ('K 256', False, _D1(256, 128, **_BIG, **_XF), 'conv_igemm<128x64>'),
+    ('K 260', False, _D1(260, 128, **_BIG, **_XF), 'conv_igemm<128x128>'),
+    # GSSD_OUT_SPLIT_T: split_n must be whole 128-column tiles for the wide tile (the Python restatement had no such term)
+    ('split_t 64', False, _SPLIT(64, **_XF), 'conv_igemm<128x64>'),
+    ('split_t 128', False, _SPLIT(128, **_XF), 'conv_igemm<128x128>'),
+    ('split_t 192', False, _SPLIT(192, **_XF), 'conv_igemm<128x64>'),
+    # conv_thin's own shape rule (the restatement tested the channel counts and the map only): a residual, padded weight rows
+    ('thin with residual', False, _G4(4, 16, 300, resid=P), 'conv_igemm<128x16>'),
+    ('thin padded rows', False, _G4(4, 16, 300, wgt_row_stride=44), 'conv_igemm<128x16>'),
+    # ---- gssd_conv2d_nhwc_bf16 ----
+    ('bf16 fp32-only flag', True, _G4(8, 16, 300, flags=_NCHW3), 'EINVAL invalid argument: !(d.flags & (GSSD_CONV_IN_NCHW3'),
+    ('thin_bf16', True, _G4(8, 16, 300), 'conv_thin_bf16<8,16>'),
+    ('thin_bf16 75', True, _G4(16, 16, 75), 'conv_thin_bf16<16,16>'),
+    ('thin_bf16 74', True, _G4(16, 16, 74), 'conv_bf16<128x16>'),
+    ('thin_bf16 pool2', True, _G4(32, 32, 150, flags=_POOL2, pool_sign=P, **_XF), 'conv_thin_bf16<32,32>/pool2'),
+    ('bf16 pool2 without pool_sign', True, _G4(32, 32, 150, flags=_POOL2), 'EINVAL GSSD_CONV_POOL2: no bf16 kernel with a pooled epilogue'),
+    ('thin_bf16 with gate', True, _G4(16, 16, 150, gate=P), 'conv_bf16<128x16>'),       # (the restatement left gssd_try_conv_thin_bf16's epilogue terms out)
+    ('flat 64 channels', True, _G4(64, 64, 75), 'conv_flat_bf16<64,64,128>'),
+    ('flat 64 channels, full tiles', True, _G4(64, 64, 75, B=32), 'conv_flat_bf16<64,64,256>'),
+    ('flat 128 channels', True, _G4(128, 128, 38), 'conv_flat_bf16<128,128,128>'),
+    ('flat dilated', True, _G4(128, 128, 19, B=32, pad=6, dil=6), 'conv_flat_bf16<128,128,128>'),
+    ('bf16 M 512', True, _D3(64, 128, 16, 32), 'conv_bf16<32x64>'),
+    ('bf16 M 513', True, _D3(64, 128, 27, 19), 'conv_bf16<64x64>'),
+    ('bf16 M 4097', True, _D3(64, 128, 17, 241), 'conv_bf16<128x64>'),
+    ('bf16 cout 16', True, _D3(64, 16, **_BIG), 'conv_bf16<128x16>'),
+    ('bf16 cout 17', True, _D3(64, 17, **_BIG, flags=_F32OUT), 'conv_bf16<128x32>'),
+    ('bf16 cout 33', True, _D3(64, 33, **_BIG, flags=_F32OUT), 'conv_bf16<128x64>'),
+    ('bf16 cout 65', True, _D3(64, 65, **_BIG, flags=_F32OUT), 'conv_bf16<128x128>'),
+    ('bf16 K 256', True, _D1(256, 128, **_BIG), 'conv_bf16<128x64>'),
+    ('bf16 K 264', True, _D1(264, 128, **_BIG), 'conv_bf16<128x128>'),
+    ('bf16 split_t 192', True, _SPLIT(192, m_per_image=True, flags=_F32OUT, in_batch_stride=4096 * 512, out_batch_stride=4096 * 192), 'conv_bf16<128x64>'),
+    ('bf16 split_t 128', True, _SPLIT(128, m_per_image=True, flags=_F32OUT, in_batch_stride=4096 * 512, out_batch_stride=4096 * 128), 'conv_bf16<128x128>'),
+]
+
+
+@pytest.mark.parametrize('row', KERNEL_NAME_ROWS, ids=lambda r: ('bf16 ' if r[1] and not r[0].startswith('bf16') else '') + r[0])
+def test_conv2d_kernel_name(row):
+    """gssd_conv2d_kernel_name: one row per leaf of the two conv dispatchers and per boundary where the leaf changes -- the name the
+    launch path itself arrives at, on a host without a GPU.  A descriptor the entry point refuses is GSSD_EINVAL with the launch's text."""
+    from gssd import _lib
+    _, bf16, kw, want = row
+    rc, name = _kernel_name(bf16, **kw)
+    if want.startswith('EINVAL '):
+        assert rc == -1 and name == '' and want[7:] in _lib.lib.gssd_last_error().decode(), (rc, name, _lib.lib.gssd_last_error())
+    else:
+        assert (rc, name) == (0, want), _lib.lib.gssd_last_error()
+
+
+def test_conv2d_kernel_name_buffer_and_takes():
+    """A buffer too short for the name is an error, never a truncated name; gssd_conv_flat_bf16_takes reports the pixel tile of the same walk."""
+    from gssd import _lib, ops
+    kw = _G4(64, 64, 75, B=32)
+    assert _kernel_name(True, cap=26, **kw) == (0, 'conv_flat_bf16<64,64,256>')             # 25 characters + NUL
+    for cap in (25, 8, 1):
+        rc, name = _kernel_name(True, cap=cap, **kw)
+        assert rc == -1 and name == '' and b'needs 26 bytes' in _lib.lib.gssd_last_error()
+    d, _, _ = ops.make_conv_desc(_ADDR, _ADDR, _ADDR, **kw)
+    assert _lib.lib.gssd_conv2d_kernel_name(ctypes.byref(d), 1, None, 64) == -1 and _lib.lib.gssd_conv2d_kernel_name(None, 0, ctypes.create_string_buffer(8), 8) == -1
+    assert _lib.lib.gssd_conv_flat_bf16_takes(ctypes.byref(d)) == 256
+    d.B = 2
+    assert _lib.lib.gssd_conv_flat_bf16_takes(ctypes.byref(d)) == 128
+    d.gate = d.out
+    assert _lib.lib.gssd_conv_flat_bf16_takes(ctypes.byref(d)) == 0
+
+
+@pytest.mark.parametrize('env,bf16,kw,want', [
+    # switches the Python restatement of the dispatch had lost or never had (they are read once per process: a child each)
+    ({'GSSD_NO_GEMM_SLOT': '1'}, False, "dict(B=32, H=38, W=38, cin_g=512, in_stride=512, Cout=512)", 'conv_igemm<128x128>'),
+    ({'GSSD_BF16_BIG_TILES': '1'}, True, "dict(B=32, H=38, W=38, cin_g=512, in_stride=512, Cout=512)", 'conv_bf16<256x128>'),
+    ({'GSSD_BF16_BIG_TILES': '3'}, True, "dict(B=32, H=38, W=38, cin_g=512, in_stride=512, Cout=512)", 'conv_bf16<192x128>'),
+    ({'GSSD_BF16_BIG_TILES': '5'}, True, "dict(B=32, H=38, W=38, cin_g=512, in_stride=512, Cout=256)", 'conv_bf16<128x128>'),
+    ({'GSSD_NO_SMALL_TILES': '1'}, False, "dict(B=1, H=16, W=32, cin_g=64, in_stride=64, Cout=128, k=3, pad=1)", 'conv_igemm<128x64>'),
+    ({'GSSD_CONV21_WINO': '0'}, False, "dict(B=2, H=150, W=150, groups=4, cin_g=16, in_stride=64, Cout=128, k=3, pad=1, wgt_wino=a, wgt_row_stride=144, relu=False, "
+                                       "flags=0, out2=a)", 'conv_thin<16,32>'),
+])
+def test_conv2d_kernel_name_follows_switches(env, bf16, kw, want):
+    import subprocess
+    import sys
+    src = ('import ctypes, torch\nfrom gssd import _lib, ops\na = torch.zeros(64)\n'
+           f'd, _, _ = ops.make_conv_desc(a, a, a, **{kw})\nbuf = ctypes.create_string_buffer(64)\n'
+           f'assert _lib.lib.gssd_conv2d_kernel_name(ctypes.byref(d), {int(bf16)}, buf, 64) == 0, _lib.lib.gssd_last_error()\nprint(buf.value.decode())\n')
+    r = subprocess.run([sys.executable, '-c', src], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, PYTHONPATH=os.pathsep.join(sys.path), **env))
+    assert r.returncode == 0 and r.stdout.strip() == want, (r.stdout, r.stderr[-2000:])
+
+
 def test_priorbox_bit_exact(golden):
     from layers.functions import PriorBox
     from data import v2, v2_512

@@ -37,6 +37,12 @@ class BackwardPlan(BackwardOpsMixin):
         self.grads = {}          # id(param) -> fp32 grad tensor
         self.zero_list = []      # tensors to zero before every run
         self.gbuf = {}           # data_ptr of a forward tensor -> gradient buffer w.r.t. it
+        self._g16, self._c16 = {}, {}        # data_ptr -> the bf16 form of a gradient map / the bf16 cast of a map (bwd_ops._dgrad, _cast16)
+        self._bn_outs_set = None             # bwd_ops._bn_outs16's answer
+        self._layer_no, self._nrun = 0, 0
+        self.single_stream = False           # True: run() ignores the branch / leaf stream ids (tests/test_gpu_training.py)
+        self._graphs, self._programs = {}, {}        # captured hipGraphs / recorded programs of the step ranges
+        self._segs = self._zero_groups = None
         # every parameter gradient is a 16-byte aligned slice of ONE flat fp32 tensor: the autograd glue hands these views out
         # as ``param.grad`` without copying, and data-parallel training all-reduces ``self.flat`` in a single call
         offs, n = [], 0
@@ -96,7 +102,7 @@ class BackwardPlan(BackwardOpsMixin):
         self.param_order = [p for p in net.parameters()]
 
     def _one(self, kind, r):
-        self._layer_no = getattr(self, '_layer_no', 0) + 1      # (the leaf launches of one layer stay on one leaf stream, in order)
+        self._layer_no += 1      # (the leaf launches of one layer stay on one leaf stream, in order)
         first_in = self.first_in
         if kind == 'head':
             self._head(r)
@@ -155,7 +161,7 @@ class BackwardPlan(BackwardOpsMixin):
         return g
 
     def _grad_of(self, t):
-        if t.data_ptr() in self.__dict__.get('_g16', {}):
+        if t.data_ptr() in self._g16:
             raise _lib.GssdError('this gradient map exists in bf16 only (a thin trunk layer): its one reader is the BatchNorm backward')
         return self.gbuf.get(t.data_ptr())
 
@@ -195,7 +201,7 @@ class BackwardPlan(BackwardOpsMixin):
         hook = self.segment_hook
         fire = {}
         if hook is not None:
-            if getattr(self, '_segs', None) is None:
+            if self._segs is None:
                 self._segs = self.segments()
             for k, (lo, hi, ready) in enumerate(self._segs):
                 fire.setdefault(max(ready, 0), []).append(k)
@@ -204,15 +210,15 @@ class BackwardPlan(BackwardOpsMixin):
         for c in cuts:                                       # [lo, hi] inclusive step ranges, a hook point (or the end) behind each
             ranges.append((lo, c))
             lo = c + 1
-        self._nrun = getattr(self, '_nrun', 0) + 1
-        use_graph = USE_BWD_GRAPH and self._nrun > 2 and not getattr(self, 'single_stream', False)
+        self._nrun += 1
+        use_graph = USE_BWD_GRAPH and self._nrun > 2 and not self.single_stream
         if not use_graph:
             for i, (lo, hi) in enumerate(ranges):
                 self._run_range(lo, hi, first=(i == 0), last=(i == len(ranges) - 1))
                 self._fire(hook, fire, hi)
             return [self.grads.get(id(p)) for p in self.param_order]
         key = tuple(ranges)
-        cache = self.__dict__.setdefault('_graphs', {})
+        cache = self._graphs
         if key not in cache:
             torch.cuda.synchronize(self.dev)
             pool = torch.cuda.graph_pool_handle()
@@ -244,8 +250,8 @@ class BackwardPlan(BackwardOpsMixin):
         control flow directly (planrun.EagerSink)."""
         if not planrun.USE_PLAN_RUN or torch.cuda.is_current_stream_capturing():
             return self._emit_range(planrun.EagerSink(), lo, hi, first, last)
-        cache = self.__dict__.setdefault('_programs', {})
-        key = (lo, hi, first, last, bool(getattr(self, 'single_stream', False)), len(self.zero_list))
+        cache = self._programs
+        key = (lo, hi, first, last, bool(self.single_stream), len(self.zero_list))
         segs = cache.get(key)
         if segs is None:
             sink = planrun.RecordSink()
@@ -258,7 +264,7 @@ class BackwardPlan(BackwardOpsMixin):
         if first:
             if self.zero_list:
                 # one multi-tensor launch per dtype (a mixed fp32 / fp64 list takes _foreach_zero_'s slow path: ~180 fill launches a step)
-                if getattr(self, '_zero_groups', None) is None or sum(len(g) for g in self._zero_groups) != len(self.zero_list):
+                if self._zero_groups is None or sum(len(g) for g in self._zero_groups) != len(self.zero_list):
                     by = {}
                     for t in self.zero_list:
                         by.setdefault(t.dtype, []).append(t)
@@ -267,7 +273,7 @@ class BackwardPlan(BackwardOpsMixin):
                 sink.host(lambda: [torch._foreach_zero_(grp) for grp in groups])
             for fn, args in getattr(self.plan, 'pre', ()):      # bf16 forward plan: fp32 copies of what the forward stored (Bf16Shadow)
                 self._emit_step(sink, fn, args, MAIN)
-        if getattr(self, 'single_stream', False) or not (self.hoisted or any(x >= LEAF_SID for x in self.step_sid)):
+        if self.single_stream or not (self.hoisted or any(x >= LEAF_SID for x in self.step_sid)):
             for si in range(lo, hi + 1):
                 fn, args = self.steps[si]
                 self._emit_step(sink, fn, args, MAIN)

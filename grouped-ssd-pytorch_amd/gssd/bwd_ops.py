@@ -77,7 +77,7 @@ class BackwardOpsMixin:
             d, Hout, _ = ops.make_conv_desc(s16, w16, g16, B=B, H=Hs, W=Hs, in_stride=Cout, cin_g=Cout // groups, Cout=Cin, groups=groups,
                                             k=k, pad=pd, dil=dil)
             self._add(lib.gssd_conv2d_nhwc_bf16, (C.byref(d),), keep=(d, s16, w16, g16))
-            self.__dict__.setdefault('_g16', {})[x_in.data_ptr()] = g16
+            self._g16[x_in.data_ptr()] = g16
             return
         if self.bf16_ops and (Cout // groups) % 8 == 0 and Cout % 8 == 0:
             # bf16 storage mode: d(input) on the bf16 matrix cores -- d(output) and the flipped / transposed weight rounded to bf16 once,
@@ -101,7 +101,7 @@ class BackwardOpsMixin:
     def _cast16(self, t):
         """bf16 copy of a FINAL fp32 gradient map (one cast launch where it is first asked for; the data-gradient conv and the weight
         gradient of a layer share it)."""
-        c = self.__dict__.setdefault('_c16', {})
+        c = self._c16
         k = t.data_ptr()
         if k not in c:
             t16 = torch.empty(t.shape, device=self.dev, dtype=torch.bfloat16)
@@ -148,7 +148,7 @@ class BackwardOpsMixin:
         if M % 16:
             return False
         d, _, _ = ops.make_conv_desc(x16, None, None, B=1, H=M // 16, W=16, in_stride=ld_x, cin_g=cin // groups, Cout=cout, groups=groups,
-                                     in_scale=in_xf[0] if in_xf else None, in_shift=in_xf[1] if in_xf else None)
+                                     **ops.xf_kw(in_xf, pad=False))
         if not lib.gssd_conv2d_wgrad_bf16_supported(C.byref(d)):
             return False
         self._add(lib.gssd_conv2d_wgrad_bf16, (C.byref(d), dy16.data_ptr(), dwp.data_ptr()), keep=(d, x16, dy16), leaf=leaf)
@@ -189,7 +189,7 @@ class BackwardOpsMixin:
             dyh16 = torch.empty(B, H, H, Cp, device=self.dev, dtype=torch.bfloat16)
             self.keep.append(dyh16)
             self._add(lib.gssd_cast_rows_f32_bf16, (dyh.data_ptr(), dyh16.data_ptr(), B * H * H, Cout, Cout, Cp))
-            self.__dict__.setdefault('_c16', {})[dyh.data_ptr()] = dyh16
+            self._c16[dyh.data_ptr()] = dyh16
             K = 9 * Cs
             dwp = self._buf(Cp, K, zero_each_run=True)
             self._add(lib.gssd_conv2d_wgrad_bf16, (C.byref(d16), dyh16.data_ptr(), dwp.data_ptr()), keep=d16, leaf=True)
@@ -222,7 +222,7 @@ class BackwardOpsMixin:
     def _convbn(self, r, need_dgrad=True):
         B, H, Ho, Hp, Cin, Cout, groups = self.B, r['H'], r['Ho'], r['Hp'], r['Cin'], r['Cout'], r['groups']
         conv, bn, raw = r['conv'], r['bn'], r['raw']
-        dout16 = self.__dict__.get('_g16', {}).pop(r['out'].data_ptr(), None)      # d(out) as a bf16 map (see _dgrad): this is its reader
+        dout16 = self._g16.pop(r['out'].data_ptr(), None)      # d(out) as a bf16 map (see _dgrad): this is its reader
         dout = dout16 if dout16 is not None else self._grad_of(r['out'])
         if dout is None:
             raise _lib.GssdError(f"no gradient reaches {r['name']}")
@@ -245,12 +245,11 @@ class BackwardOpsMixin:
         cin_g_real = conv.weight.shape[1]
         d16 = None
         if self.bf16_ops and r.get('x16') is not None and cin_g_real == cin_g_pad:
-            ix = r['in_xf']
             flat = r['k'] == 1 and r['stride'] == 1 and r['pad'] == 0 and (B * H * H) % 16 == 0    # 1x1: the map as (M / 16) x 16 pixels
             d16, _, _ = ops.make_conv_desc(r['x16'], None, None, B=1 if flat else B, H=B * H * H // 16 if flat else H, W=16 if flat else H,
                                            in_stride=r['Cin16'], cin_g=r['Cin16'] // groups, Cout=Cout,
                                            groups=groups, k=r['k'], stride=r['stride'], pad=r['pad'], dil=r['dil'],
-                                           in_scale=ix[0] if ix else None, in_shift=ix[1] if ix else None)
+                                           **ops.xf_kw(r['in_xf'], pad=False))
             if not lib.gssd_conv2d_wgrad_bf16_supported(C.byref(d16)):
                 d16 = None
         dg16 = bool(need_dgrad and self.bf16_ops and (Cout // groups) % 8 == 0 and Cout % 8 == 0 and r['stride'] == 1)   # (stride 2: the
@@ -262,7 +261,7 @@ class BackwardOpsMixin:
         dz16 = torch.empty(B, Ho, Ho, Cout, device=self.dev, dtype=torch.bfloat16) if want16 else None
         if want16:
             self.keep.append(dz16)
-            self.__dict__.setdefault('_c16', {})[dz.data_ptr()] = dz16      # _cast16(dz) finds it: no cast launch
+            self._c16[dz.data_ptr()] = dz16      # _cast16(dz) finds it: no cast launch
         if not mixed:
             self._need(raw)
         # without pooling the reduce pass only sums (dz = NULL) and the apply pass re-derives dz from d(out): 5 instead of 6 HBM passes
@@ -318,7 +317,7 @@ class BackwardOpsMixin:
 
     def _bn_outs16(self):
         """Outputs of conv + BatchNorm layers whose backward reads bf16 maps (gssd_bn_bwd_*_mixed takes a bf16 d(out) too)."""
-        s = self.__dict__.get('_bn_outs_set')
+        s = self._bn_outs_set
         if s is None:
             s = set()
             if self.bf16_ops:

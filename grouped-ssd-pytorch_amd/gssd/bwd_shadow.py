@@ -129,11 +129,9 @@ class Bf16Shadow:
                 if r['in_xf'] is not None:
                     prod = next(rr for kk, rr in plan.rec if kk == 'convbn' and rr.get('xf') is not None and rr['xf'][0] is r['in_xf'][0])
                     q['in_xf'] = XF(r['in_xf'], prod['bn'], prod['stats'], B * prod['Ho'] * prod['Ho'], prod['Cout'], prod.get('stats_rep', 0))
-                ix = q['in_xf']
                 d, _, _ = ops.make_conv_desc(q['x_in'], None, q['raw'], B=B, H=r['H'], W=r['H'], in_stride=q['Cin'],
                                              cin_g=q['Cin'] // r['groups'], Cout=r['Cout'], groups=r['groups'], k=r['k'], stride=r['stride'],
-                                             pad=r['pad'], dil=r['dil'], in_scale=ix[0] if ix else None, in_shift=ix[1] if ix else None,
-                                             in_pad=ix[2] if ix else None)
+                                             pad=r['pad'], dil=r['dil'], **ops.xf_kw(q['in_xf']))
                 q['desc'] = d
             elif kind == 'dcn':
                 OMC = r['omc']

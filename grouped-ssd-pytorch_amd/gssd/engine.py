@@ -15,7 +15,7 @@ Dataflow restated from models/ssd_multiphase_custom_group.py:217-400 (SURVEY.md 
 
 Weights are re-packed (OIHW -> K-major rows) only when a parameter's version counter changed.
 """
-import ctypes as C
+import contextlib
 import os
 
 import torch
@@ -25,7 +25,7 @@ from ._lib import lib
 from .plan_common import (VGG_CFG, EXTRAS_CFG, MBOX, SRC_HW, HEAD_OFF, FUSE_NAMES, USE_CONV_X6, USE_WINOGRAD, DCN_X6, USE_GRAPH, USE_FLASH_X6, USE_BRANCH_STREAMS, SN_STREAM, ALL_STREAMS, Tag, _Step, conv_tag)      # noqa: F401 (re-exported: backward.py, pixellink.py, bench.py)
 from .plan_exec import PlanExecMixin
 from .plan_graph import PlanGraphMixin
-from .plan_ops import PlanOpsMixin
+from .plan_ops import PlanOpsMixin, bn_arena
 
 
 class GssdEngine:
@@ -167,7 +167,7 @@ _SK_PENDING = []          # (device index, output pointer) of dropped plans whos
 
 
 def drain_sk_releases():
-    """Free the stream-K regions queued by _Plan.__del__: only when no stream of this thread is capturing, each on its own device."""
+    """Free the stream-K regions queued by _PlanBase.__del__: only when no stream of this thread is capturing, each on its own device."""
     if not _SK_PENDING or torch.cuda.is_current_stream_capturing():
         return 0
     n = 0
@@ -186,29 +186,42 @@ class _RecList(list):
         self._plan = plan
 
     def append(self, item):
-        item[1].setdefault('sid', getattr(self._plan, '_sid', 0))
+        item[1].setdefault('sid', self._plan._sid)
         super().append(item)
 
 
-class _PlanBase:
-    """State shared by the grouped and the vanilla launch plans."""
+class _PlanBase(PlanGraphMixin, PlanOpsMixin, PlanExecMixin):
+    """What every forward launch plan is made of: the state the emitters (plan_ops.PlanOpsMixin), the step placement and head helpers
+    (plan_graph.PlanGraphMixin) and eager / hipGraph execution (plan_exec.PlanExecMixin) read, all of it set by ONE constructor, plus the
+    step / buffer helpers.  A subclass calls the constructor, then emits its own graph."""
     generation = 0        # bumped by every run(): a backward checks it ran against the forward that produced it
     busy = False          # a grad-enabled forward awaits its backward (gssd/autograd.py::_Lease)
     _bwd = None
 
-    def backward_plan(self):
-        if getattr(self, 'nograd', False):
-            raise _lib.GssdError('this forward plan was built for a forward without backward (its pooled layers kept no raw maps)')
-        if self._bwd is None:
-            from .backward import BackwardPlan, Bf16Shadow
-            # bf16 storage mode: the fp32 backward plan over fp32 copies of the stored bf16 activations (mixed precision)
-            self._bwd = BackwardPlan(Bf16Shadow(self) if getattr(self, 'bf16', False) else self)
-        return self._bwd
-
-
-class _Plan(_PlanBase, PlanGraphMixin, PlanOpsMixin, PlanExecMixin):
-    """The launch plan of one (batch size, mode) of the detector.  The graph walk lives in plan_graph.PlanGraphMixin, the per-op emitters in
-    plan_ops.PlanOpsMixin, eager / hipGraph execution in plan_exec.PlanExecMixin; this class keeps construction and the buffer / step helpers."""
+    def __init__(self, eng, B, training, dev, *, bf16=False, nograd=False, want_maps=False):
+        self.eng, self.B, self.training, self.dev = eng, B, bool(training), dev
+        self.nograd = nograd                       # no backward will read this plan's activations
+        self.want_maps = want_maps                 # visualize=True: also materialise the attention maps
+        # BASELINE.json configs[4]: bf16 NHWC activations + bf16 packed weights + bf16 MFMA, fp32 accumulation / BatchNorm
+        # statistics / softmax / offsets / loc + conf / loss / NMS (net.compute_dtype = 'bf16'; parameters stay fp32 masters)
+        self.bf16 = bf16
+        self.adt = torch.bfloat16 if bf16 else torch.float32
+        self.conv_fn = lib.gssd_conv2d_nhwc_bf16 if bf16 else lib.gssd_conv2d_nhwc_f32
+        self.cpad = 8 if bf16 else 4               # stored channels per group of the packed input: whole 16-byte pieces
+        self.steps, self.bufs, self.head_descs = [], [], []
+        self.rec = _RecList(self)   # forward graph records, consumed by gssd/backward.py (each tagged with its branch stream id)
+        self.P, self.nc = 0, 0      # prior boxes, classes (the detector plans)
+        # emitter state: the stream id / layer the next launches belong to, a join the next launch carries, the spectral-norm launch's open join
+        self._sid, self._layer, self._pending_wait, self._sn_unjoined = 0, None, None, False
+        self.sn_items, self.sa_state, self.attn_maps, self.offsets = [], {}, {}, []
+        self.sources, self.sources_xf = [], {}
+        self._sk_outs = []          # deformable-conv outputs with a stream-K region (GSSD_DCN_X6=0), released with the plan
+        self._mark_conv7 = self._pack_step = self._in_desc = None
+        self._reduce_steps = ()
+        self.stats, self.stat_of, self.stat_rep, self.nbt = bn_arena(dev, (), ())
+        # execution state (plan_exec)
+        self._runs, self._side_streams, self._node_events = 0, {}, {}
+        self._graphs = self._last_in_ptr = self._gx = None          # (_graphs: None until the first capture, then {key: segments})
 
     def __del__(self):
         # csrc/dcn_fused.hip's stream-K regions belong to this plan's deformable-conv outputs (GSSD_DCN_X6=0 only).  The release frees device
@@ -216,47 +229,99 @@ class _Plan(_PlanBase, PlanGraphMixin, PlanOpsMixin, PlanExecMixin):
         # device current -- so the pointers are only QUEUED here, with their device; drain_sk_releases() frees them at the next plan build
         # that finds no capture open.
         try:
-            outs = self.__dict__.get('_sk_outs', ())
+            outs = self.__dict__.get('_sk_outs', ())          # (guarded: the constructor may have raised)
             if outs:
                 _SK_PENDING.extend((self.dev.index if self.dev.index is not None else torch.cuda.current_device(), ptr) for ptr in outs)
         except Exception:        # noqa: BLE001 -- interpreter teardown
             pass
 
+    def backward_plan(self):
+        if self.nograd:
+            raise _lib.GssdError('this forward plan was built for a forward without backward (its pooled layers kept no raw maps)')
+        if self._bwd is None:
+            from .backward import BackwardPlan, Bf16Shadow
+            # bf16 storage mode: the fp32 backward plan over fp32 copies of the stored bf16 activations (mixed precision)
+            self._bwd = BackwardPlan(Bf16Shadow(self) if self.bf16 else self)
+        return self._bwd
+
+    # ------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _on_stream(self, sid):
+        """The launches and records emitted inside belong to stream ``sid`` of the captured graph."""
+        prev, self._sid = self._sid, sid
+        try:
+            yield
+        finally:
+            self._sid = prev
+
+    @contextlib.contextmanager
+    def _in_layer(self, name):
+        """The launches emitted inside belong to layer ``name`` (Tag.layer: bench.py sums a layer's launches)."""
+        prev, self._layer = self._layer, name
+        try:
+            yield
+        finally:
+            self._layer = prev
+
+    def _add(self, fn, args, keep=None, tag=None):
+        d = None
+        if tag is None and fn in (lib.gssd_conv2d_nhwc_f32, lib.gssd_conv2d_nhwc_bf16):
+            d = keep[0] if isinstance(keep, tuple) else keep
+            tag = (None, 0.0, 0.0)                   # a conv: named by _name_convs() once the plan's descriptors are final
+        if tag is not None:
+            tag = Tag(tag)
+            tag.layer = self._layer
+            tag.desc = d
+        self.steps.append(_Step(fn, args, keep, tag, self._sid, self._pending_wait))
+        self._pending_wait = None
+
+    def _name_convs(self):
+        """Last step of a plan build: every conv step gets its (kernel instance, FLOPs, bytes) from the library's dispatcher
+        (plan_common.conv_tag), now that the heads have their outputs and conv1_1 its final input form.  A descriptor the
+        entry point would refuse raises GssdError here, not at the first launch."""
+        for st in self.steps:
+            if st.tag is not None and st.tag[0] is None:
+                tag = Tag(conv_tag(st.tag.desc, bf16=st.fn is lib.gssd_conv2d_nhwc_bf16))
+                tag.layer, tag.desc = st.tag.layer, st.tag.desc
+                st.tag = tag
+
+    def _abuf(self, *shape):
+        """Activation buffer in the plan's storage type (fp32, or bf16 in configs[4] mode)."""
+        t = torch.empty(*shape, device=self.dev, dtype=self.adt)
+        self.bufs.append(t)
+        return t
+
+    def _buf(self, *shape):
+        t = torch.empty(*shape, device=self.dev, dtype=torch.float32)
+        self.bufs.append(t)
+        return t
+
+    def _abuf_tail(self, tail, *shape):
+        """Activation buffer with ``tail`` more elements stored right behind it (one allocation): a raw conv output whose deferred
+        BatchNorm's padding vector sits at ``map + numel`` -- the fp32 Winograd kernel then fetches the padding value of an out-of-image
+        patch position through the load ADDRESS (32-bit offset from the map) instead of selecting it per loaded element
+        (include/gssd_hip.h: in_pad).  Returns (map, tail view)."""
+        if self.bf16:
+            return self._abuf(*shape), self._abuf(tail)          # (only the fp32 Winograd kernel uses the layout)
+        n = 1
+        for v in shape:
+            n *= v
+        flat = torch.empty(n + tail, device=self.dev, dtype=self.adt)
+        self.bufs.append(flat)
+        return flat[:n].view(*shape), flat[n:]
+
+
+class _Plan(_PlanBase):
+    """The launch plan of one (batch size, mode) of the grouped detector: the walk over its graph (plan_graph.PlanGraphMixin)."""
+
     def __init__(self, eng, B, training, dev, want_maps=False, nograd=False):
-        self.eng, self.B, self.training, self.dev = eng, B, training, dev
-        self.nograd = nograd                       # no backward will read this plan's activations
-        self.want_maps = want_maps                 # visualize=True: also materialise the attention maps
-        # BASELINE.json configs[4]: bf16 NHWC activations + bf16 packed weights + bf16 MFMA, fp32 accumulation / BatchNorm
-        # statistics / softmax / offsets / loc + conf / loss / NMS (net.compute_dtype = 'bf16'; parameters stay fp32 masters)
-        self.bf16 = getattr(eng.net, 'compute_dtype', 'f32') == 'bf16'
-        self.adt = torch.bfloat16 if self.bf16 else torch.float32
-        self.conv_fn = lib.gssd_conv2d_nhwc_bf16 if self.bf16 else lib.gssd_conv2d_nhwc_f32
+        net = eng.net
+        super().__init__(eng, B, training, dev, bf16=getattr(net, 'compute_dtype', 'f32') == 'bf16', nograd=nograd, want_maps=want_maps)
+        g = net.groups_vgg
         # channels per group of the packed input: 12 / groups_vgg real ones (3 per CT phase at the default 4 groups), zero-padded to whole
         # 16-byte pieces (fp32: 4 channels, bf16: 8)
-        self.cpad = ops.round_up(12 // eng.net.groups_vgg, 8 if self.bf16 else 4)
-        net = eng.net
-        self.steps = []
-        self.bufs = []
-        self.head_descs = []
-        self.rec = _RecList(self)   # forward graph records, consumed by gssd/backward.py (each tagged with its branch stream id)
-        self.P = 8732
-        self.nc = net.num_classes
-        g = net.groups_vgg
-        f32 = torch.float32
-
-        def buf(*shape):
-            t = torch.empty(*shape, device=dev, dtype=f32)
-            self.bufs.append(t)
-            return t
-        abuf = self._abuf
-
-        # ---- batch-stat arena ------------------------------------------------------------------
-        bn_mods = [m for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d)]
-        seen, uniq = set(), []
-        for m in bn_mods:
-            if id(m) not in seen:
-                seen.add(id(m))
-                uniq.append(m)
+        self.cpad = ops.round_up(12 // g, self.cpad)
+        self.P, self.nc = 8732, net.num_classes
         # The trunk's batch sums are kept in R replicas (include/gssd_hip.h: gssd_conv_desc::stats_rep): device-scope fp64 atomics on one
         # cache line are served serially, and the persistent trunk kernels flush every workgroup's sums at the END of the launch (conv2_1
         # in bf16: 131 k atomics on 16 lines = 60 of its 140 us, profiles/r04_thin_knockout.txt).  R * C <= 2048 (at most 32): every
@@ -265,23 +330,12 @@ class _Plan(_PlanBase, PlanGraphMixin, PlanOpsMixin, PlanExecMixin):
         # there to remove (scripts/thin_f32_probe.py: conv1_1 248 us with one array, 260 with 32 replicas, 224 without batch sums)
         trunk_bn = ({id(m) for m in net.vgg if isinstance(m, torch.nn.BatchNorm2d)}
                     if (self.bf16 and os.environ.get('GSSD_STATS_REP', '1') != '0') else set())
-        self.stat_rep = {id(m): (max(1, min(32, 2048 // m.num_features)) if id(m) in trunk_bn else 1) for m in uniq}
-        total = sum(2 * m.num_features * self.stat_rep[id(m)] for m in uniq)
-        self.stats = torch.zeros(max(total, 2), device=dev, dtype=torch.float64)
-        off = 0
-        self.stat_of = {}
-        for m in uniq:
-            n = 2 * m.num_features * self.stat_rep[id(m)]
-            self.stat_of[id(m)] = self.stats[off:off + n]
-            off += n
-        self.nbt = [m.num_batches_tracked for m in uniq]
-
+        self.stats, self.stat_of, self.stat_rep, self.nbt = bn_arena(dev, net.modules(), trunk_bn)
         self._setup_spectral_norm([(n, getattr(net, n)) for n in ('self_attn_base_list', 'self_attn_list')
                                    if getattr(net, n, None) is not None])
 
         # ---- input pack ------------------------------------------------------------------------------
-        self.x_in = None   # set per run
-        x16 = abuf(B, 300, 300, self.cpad * g)
+        x16 = self._abuf(B, 300, 300, self.cpad * g)
         self._pack_step = len(self.steps)
         if self.bf16:
             self._add(lib.gssd_pack_input_nhwc_bf16, [0, x16.data_ptr(), B, 12, 300, 300, g])
@@ -301,65 +355,15 @@ class _Plan(_PlanBase, PlanGraphMixin, PlanOpsMixin, PlanExecMixin):
         self._fuse_input_pack()
         self._name_convs()
 
-    # ------------------------------------------------------------------------------------------------
-    def _add(self, fn, args, keep=None, tag=None):
-        d = None
-        if tag is None and fn in (lib.gssd_conv2d_nhwc_f32, lib.gssd_conv2d_nhwc_bf16):
-            d = keep[0] if isinstance(keep, tuple) else keep
-            tag = (None, 0.0, 0.0)                   # a conv: named by _name_convs() once the plan's descriptors are final
-        if tag is not None:
-            tag = Tag(tag)
-            tag.layer = getattr(self, '_layer', None)
-            tag.desc = d
-        self.steps.append(_Step(fn, args, keep, tag, getattr(self, '_sid', 0), self.__dict__.pop('_pending_wait', None)))
 
-    def _name_convs(self):
-        """Last step of a plan build: every conv step gets its (kernel instance, FLOPs, bytes) from the library's dispatcher
-        (plan_common.conv_tag), now that the heads have their outputs and conv1_1 its final input form.  A descriptor the
-        entry point would refuse raises GssdError here, not at the first launch."""
-        for st in self.steps:
-            if st.tag is not None and st.tag[0] is None:
-                tag = Tag(conv_tag(st.tag.desc, bf16=st.fn is lib.gssd_conv2d_nhwc_bf16))
-                tag.layer, tag.desc = st.tag.layer, st.tag.desc
-                st.tag = tag
-
-    def _abuf(self, *shape):
-        """Activation buffer in the plan's storage type (fp32, or bf16 in configs[4] mode)."""
-        t = torch.empty(*shape, device=self.dev, dtype=getattr(self, 'adt', torch.float32))
-        self.bufs.append(t)
-        return t
-
-    def _buf(self, *shape):
-        t = torch.empty(*shape, device=self.dev, dtype=torch.float32)
-        self.bufs.append(t)
-        return t
-
-    def _abuf_tail(self, tail, *shape):
-        """Activation buffer with ``tail`` more elements stored right behind it (one allocation): a raw conv output whose deferred
-        BatchNorm's padding vector sits at ``map + numel`` -- the fp32 Winograd kernel then fetches the padding value of an out-of-image
-        patch position through the load ADDRESS (32-bit offset from the map) instead of selecting it per loaded element
-        (include/gssd_hip.h: in_pad).  Returns (map, tail view)."""
-        if getattr(self, 'bf16', False):
-            return self._abuf(*shape), self._abuf(tail)          # (only the fp32 Winograd kernel uses the layout)
-        n = 1
-        for v in shape:
-            n *= v
-        flat = torch.empty(n + tail, device=self.dev, dtype=getattr(self, 'adt', torch.float32))
-        self.bufs.append(flat)
-        return flat[:n].view(*shape), flat[n:]
-
-
-class _PlanVanilla(_Plan):
+class _PlanVanilla(_PlanBase):
     """models/ssd.py:48-108: dense VGG-SSD300 without BatchNorm (BASELINE.json configs[0]).  conv + ReLU is one launch
     (ReLU in the conv epilogue); pools are the identity-affine pool pass."""
 
-    def __init__(self, eng, B, training, dev):   # noqa: super().__init__ builds the grouped graph; not called on purpose
-        self.eng, self.B, self.training, self.dev = eng, B, training, dev
+    def __init__(self, eng, B, training, dev):
+        super().__init__(eng, B, training, dev)
         net = eng.net
-        self.steps, self.bufs, self.head_descs, self.rec = [], [], [], _RecList(self)
         self.P, self.nc = 8732, net.num_classes
-        self.stats = torch.zeros(2, device=dev, dtype=torch.float64)
-        self.nbt = []
         x4 = self._buf(B, 300, 300, 4)
         self._pack_step = 0
         self._add(lib.gssd_pack_input_nhwc, [0, x4.data_ptr(), B, 3, 300, 300, 1, 4])
@@ -379,13 +383,7 @@ class _PlanVanilla(_Plan):
                     self.rec.append(('l2norm', dict(x_in=cur, out=s, H=H, C=Cc, mod=net.L2Norm)))
                     sources.append((s, H, Cc))
             else:                                        # MaxPool2d
-                k, st, pd = m.kernel_size, m.stride, m.padding
-                Hp = ops.pool_out_size(H, k, st, pd, m.ceil_mode)
-                out = self._buf(B, Hp, Hp, Cc)
-                self._add(lib.gssd_bn_relu_pool_f32, (cur.data_ptr(), out.data_ptr(), B, H, H, Cc, Hp, Hp, k, st, pd, 0, 1.0, 0, 0,
-                                                      0, 0, 0.1, 1e-5, 0, 0, 0))
-                self.rec.append(('pool', dict(x_in=cur, out=out, H=H, C=Cc, k=k, s=st, p=pd, Hp=Hp)))
-                cur, H = out, Hp
+                cur, H = self._pool_only(cur, H, Cc, m.kernel_size, m.stride, m.padding, m.ceil_mode, tag=False)
                 i += 1
         sources.append((cur, H, Cc))                     # conv7
         for k, m in enumerate(net.extras):
@@ -393,75 +391,29 @@ class _PlanVanilla(_Plan):
             if k % 2 == 1:
                 sources.append((cur, H, Cc))
         self.sources = sources
-        off = 0
-        f32 = torch.float32
         for i, (s, Hs, Cs) in enumerate(sources):
-            A = MBOX[i]
-            nloc, nconf = A * 4, A * self.nc
-            lw, cw = net.loc[i], net.conf[i]
-            _, K = ops.packed_k(Cs, 3, 3)
-
-            def build_w(out, lw=lw, cw=cw, nloc=nloc, nconf=nconf, K=K):
-                if out is None:
-                    out = torch.empty(nloc + nconf, K, device=dev, dtype=f32)
-                ops.pack_weight(lw.weight, out, 0)
-                ops.pack_weight(cw.weight, out, nloc)
-                return out
-
-            def build_b(out, lw=lw, cw=cw, nloc=nloc):
-                if out is None:
-                    out = torch.empty(nloc + cw.bias.numel(), device=dev, dtype=f32)
-                ops.copy_into(out[:nloc], lw.bias)
-                ops.copy_into(out[nloc:], cw.bias)
-                return out
-            wp = eng._pack(f'heads.{i}.w', build_w)
-            bp = eng._pack(f'heads.{i}.b', build_b)
-            d, _, _ = ops.make_conv_desc(s, wp, None, B=B, H=Hs, W=Hs, in_stride=Cs, cin_g=Cs, Cout=nloc + nconf, k=3,
-                                         pad=1, bias=bp, out_mode=_lib.OUT_HEADS, out_b=None, split_n=nloc,
-                                         out_batch_stride=self.P * 4, outb_batch_stride=self.P * self.nc,
-                                         out_off=off * 4, outb_off=off * self.nc,
-                                         split_k=ops.auto_split_k(B * Hs * Hs, nloc + nconf, 1, K))
-            self.head_descs.append(d)
-            self._add(lib.gssd_conv2d_nhwc_f32, (C.byref(d),), keep=d)
-            self.rec.append(('head', dict(i=i, src=s, H=Hs, C=Cs, A=A, off=off, loc=lw, conf=cw, K=K)))
-            off += Hs * Hs * A
-        assert off == self.P, off
+            self._head(i, s, Hs, Cs)
         self._finish_heads()
         self._name_convs()
 
     def _conv_relu(self, name, conv, x, H, Cin):
-        B = self.B
-        k, s, p, dl = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
-        Cout = conv.out_channels
-
         def build(out, conv=conv, Cin=Cin):
             w = conv.weight
             if w.shape[1] != Cin:                        # conv1_1: 3 input channels stored in 4 (zero pad)
                 w = torch.nn.functional.pad(w.detach(), (0, 0, 0, 0, 0, Cin - w.shape[1]))
             return ops.pack_weight(w, out)
-        wp = self.eng._pack(name + '.w', build)
-        Ho = (H + 2 * p - dl * (k - 1) - 1) // s + 1
-        out = self._buf(B, Ho, Ho, Cout)
-        d, _, _ = ops.make_conv_desc(x, wp, out, B=B, H=H, W=H, in_stride=Cin, cin_g=Cin, Cout=Cout, k=k, stride=s, pad=p,
-                                     dil=dl, bias=conv.bias.detach(), relu=True)
-        self._add(lib.gssd_conv2d_nhwc_f32, (C.byref(d),), keep=d)
-        self.rec.append(('convrelu', dict(name=name, conv=conv, x_in=x, out=out, H=H, Cin=Cin, Ho=Ho, Cout=Cout, desc=d, k=k,
-                                          stride=s, pad=p, dil=dl)))
-        return out, Ho, Cout
+        return self._conv_bias(name, conv, x, H, Cin, relu=True, weight=build)
 
 
-class SelfAttnOp(_Plan):
+class SelfAttnOp(_PlanBase):
     """ONE Self_Attn block (layers/self_attn.py:46-89) as its own launch plan -- the op-level entry the parity tests use:
     x NHWC [B,H,H,C] -> (x + sigma*o, sigma*o, attention map [B,N,N]).  ``training`` runs the spectral-norm power iteration
     first (and mutates weight_u / weight_v in place), like the reference's forward pre-hook."""
 
-    def __init__(self, sa, B, H, training, dev):   # noqa: a stand-alone block; _Plan.__init__ builds the whole network
+    def __init__(self, sa, B, H, training, dev):
         holder = torch.nn.Module()
         holder.self_attn_list = torch.nn.ModuleList([sa])
-        self.eng = GssdEngine(holder)
-        self.B, self.training, self.dev = B, bool(training), dev
-        self.bf16, self.adt, self.conv_fn = False, torch.float32, lib.gssd_conv2d_nhwc_f32
-        self.steps, self.bufs, self.rec, self.head_descs = [], [], _RecList(self), []
+        super().__init__(GssdEngine(holder), B, training, dev)
         Cc = sa.in_channels
         self.H, self.C = H, Cc
         self.x = self._buf(B, H, H, Cc)
@@ -472,10 +424,6 @@ class SelfAttnOp(_Plan):
     def run(self, x_nhwc):
         self.generation += 1
         self.x.copy_(x_nhwc)
-        stream = torch.cuda.current_stream().cuda_stream
-        for st in self.steps:
-            rc = st.fn(*st.args, stream)
-            if rc != 0:
-                _lib.check(rc)
+        self._run_steps(torch.cuda.current_stream().cuda_stream)
         S, N, Np = self.attn_maps[('self_attn_list', 0)]
         return self.out, self.out2, S[:, :, :N]

@@ -158,6 +158,14 @@ def cast_bf16(x, out=None):
 # ------------------------------------------------------------------------------------------------
 # conv
 # ------------------------------------------------------------------------------------------------
+def xf_kw(xf, pad=True):
+    """make_conv_desc's keywords of a fused input transform ``xf`` = (scale, shift, padding vector) or None.  ``pad=False`` leaves the padding
+    vector out (the weight-gradient descriptors never read out-of-image positions through it)."""
+    if not xf:
+        return {}
+    return dict(in_scale=xf[0], in_shift=xf[1], in_pad=xf[2]) if pad else dict(in_scale=xf[0], in_shift=xf[1])
+
+
 def make_conv_desc(inp, wgt, out, *, B, H, W, in_stride, cin_g, Cout, groups=1, k=1, stride=1, pad=0, dil=1,
                    bias=None, in_ch_off=0, out_stride=None, out_ch_off=0, out_mode=_lib.OUT_NHWC, relu=False,
                    stats=None, alpha=None, gate=None, resid=None, out2=None, out_b=None, split_n=0,

@@ -13,7 +13,8 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
-from .engine import GssdEngine, _Plan, _RecList, USE_WINOGRAD, USE_CONV_X6
+from .engine import GssdEngine, _PlanBase
+from .plan_ops import bn_arena
 
 lib = _lib.lib
 
@@ -30,7 +31,7 @@ class PixelLinkEngine(GssdEngine):
         return out_1, out_2
 
 
-class _PlanPixelLink(_Plan):
+class _PlanPixelLink(_PlanBase):
     # PixelLink++'s VGG trunk is conv + ReLU without BatchNorm (model.py:40-77): nothing bounds its activation maps, so its launches never carry
     # GSSD_CONV_F16_OK (the split-operand kernels keep their bf16 planes)
     f16_ok = 0
@@ -41,27 +42,12 @@ class _PlanPixelLink(_Plan):
             self._bwd = PixelLinkBackwardPlan(self)
         return self._bwd
 
-    def __init__(self, eng, B, training, dev):   # noqa: _Plan.__init__ builds the detector graph; not called on purpose
-        self.eng, self.B, self.training, self.dev = eng, B, training, dev
-        self.want_maps = False
-        self.bf16, self.adt, self.conv_fn, self.cpad = False, torch.float32, lib.gssd_conv2d_nhwc_f32, 4
+    def __init__(self, eng, B, training, dev):
+        super().__init__(eng, B, training, dev)       # fp32; no prior boxes: the roots of the backward are d(out_1), d(out_2)
         net = eng.net
-        self.steps, self.bufs, self.head_descs = [], [], []
-        self.rec = _RecList(self)         # forward graph records, walked in reverse by gssd/backward.py::PixelLinkBackwardPlan
-        self.P, self.nc = 0, 0            # (no prior boxes: the roots of the backward are d(out_1), d(out_2))
         g = net.vgg_groups
-        # ---- batch-stat arena (the fuse BatchNorms) ----------------------------------------------------
-        uniq, seen = [], set()
-        for m in net.modules():
-            if isinstance(m, torch.nn.BatchNorm2d) and id(m) not in seen:
-                seen.add(id(m))
-                uniq.append(m)
-        self.stats = torch.zeros(max(sum(2 * m.num_features for m in uniq), 2), device=dev, dtype=torch.float64)
-        self.stat_of, off = {}, 0
-        for m in uniq:
-            self.stat_of[id(m)] = self.stats[off:off + 2 * m.num_features]
-            off += 2 * m.num_features
-        self.nbt = [m.num_batches_tracked for m in uniq]
+        # the fuse BatchNorms' batch sums, one array each; stat_rep stays empty, so their launches carry stats_rep = 0 (include/gssd_hip.h: 0 / 1 = one)
+        self.stats, self.stat_of, _, self.nbt = bn_arena(dev, net.modules(), ())
         self._setup_spectral_norm([(n, getattr(net, n)) for n in ('self_attn_base_list', 'self_attn_list')
                                    if getattr(net, n, None) is not None])
         self._relu_xf = {}
@@ -140,43 +126,17 @@ class _PlanPixelLink(_Plan):
     def _conv_raw(self, name, conv, x, H, Cin, groups, in_xf, relu_after=True):
         """conv + bias; ``relu_after``: the ReLU that follows in the graph is applied by the consumer (fused input transform) or by the
         next _relu_pool pass -- the backward masks this layer's output gradient with [raw > 0]."""
-        B = self.B
-        k, s, p, dl = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
-        Cout = conv.out_channels
-        cin_g = Cin // groups
-        wp = self._packed_conv(name, conv)
-        U = None
-        if USE_WINOGRAD and ops.winograd_eligible(k, s, p, dl, cin_g, Cout // groups, groups):
-            def build_u(out, key=name + '.w', groups=groups, cin_g=cin_g):
-                return ops.winograd_weight(self.eng._packed[key], groups, cin_g, out)
-            U = self.eng._pack(name + '.U', build_u)
-        Ho = (H + 2 * p - dl * (k - 1) - 1) // s + 1
-        raw = self._buf(B, Ho, Ho, Cout)
-        X6 = None
-        if not getattr(self, "bf16", False) and USE_CONV_X6 and ops.x6_wanted(k, cin_g, Cout // groups, groups, B * Ho * Ho, winograd=U is not None):      # conv6 / conv7
-            def build_x6(out, key=name + '.w', groups=groups, cin_g=cin_g, taps=k * k, bn=ops.x6_tile(Cout // groups, groups, B * Ho * Ho)):
-                return ops.x6_weight(self.eng._packed[key], groups, cin_g, taps, bn, out)
-            X6 = self.eng._pack(name + f'.x6@{ops.x6_tile(Cout // groups, groups, B * Ho * Ho)}', build_x6)       # the tile is part of the packed layout: part of the key
-        d, _, _ = ops.make_conv_desc(x, wp, raw, B=B, H=H, W=H, in_stride=Cin, cin_g=cin_g, Cout=Cout, groups=groups, k=k, stride=s,
-                                     pad=p, dil=dl, bias=conv.bias.detach(), wgt_wino=U, wgt_x6=X6,
-                                     in_scale=in_xf[0] if in_xf else None, in_shift=in_xf[1] if in_xf else None,
-                                     in_pad=in_xf[2] if in_xf else None)
-        self._add(self.conv_fn, (C.byref(d),), keep=(d, in_xf))
-        self.rec.append(('convrelu', dict(name=name, conv=conv, x_in=x, out=raw, H=H, Cin=Cin, Ho=Ho, Cout=Cout, desc=d, k=k, stride=s,
-                                          pad=p, dil=dl, groups=groups, relu=bool(relu_after))))
-        return raw, Ho, Cout
+        return self._conv_bias(name, conv, x, H, Cin, groups, in_xf=in_xf, forms=True, rec=dict(groups=groups, relu=bool(relu_after)))
 
     def _relu_pool(self, x, H, Cc, pool, relu=True):
         """ReLU and / or max-pool (ceil_mode) as the identity-affine BatchNorm pass."""
-        B = self.B
         if pool:
             pk, ps, pp, ceil = pool
             Hp = ops.pool_out_size(H, pk, ps, pp, ceil)
         else:
             pk, ps, pp, Hp = 0, 1, 0, H
-        out = self._buf(B, Hp, Hp, Cc)
-        self._add(lib.gssd_bn_relu_pool_f32, (x.data_ptr(), out.data_ptr(), B, H, H, Cc, Hp, Hp, pk, ps, pp, 0, 1.0, 0, 0, 0, 0, 0.1, 1e-5,
-                                              0, int(relu), 0))
+        out = self._buf(self.B, Hp, Hp, Cc)
+        self._identity_pool(x, out, H, Cc, Hp, pk, ps, pp, relu=relu, tag=False)
         self.rec.append(('relupool', dict(x_in=x, out=out, H=H, C=Cc, k=pk, s=ps, p=pp, Hp=Hp, relu=bool(relu))))
         return out, Hp
 
@@ -255,16 +215,7 @@ class _PlanPixelLink(_Plan):
         fin[self._final_out], fin[self._final_out + 1] = out_1.data_ptr(), out_2.data_ptr()
         if self.training:
             self.stats.zero_()
-        stream = torch.cuda.current_stream().cuda_stream
-        for st in self.steps:
-            if events is not None and st.tag is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                self._launch(st, stream)
-                e1.record()
-                events.append((st.tag, e0, e1))
-            else:
-                self._launch(st, stream)
+        self._run_steps(torch.cuda.current_stream().cuda_stream, events)
         if self.training and self.nbt:
             torch._foreach_add_(self.nbt, 1)
         self._x_keepalive = x

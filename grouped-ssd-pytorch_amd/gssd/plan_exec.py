@@ -1,5 +1,5 @@
 """Execution of a forward launch plan: eager launches (optionally bracketed by HIP events for bench.py) and hipGraph capture / replay with
-the branch streams forked and joined inside the graph.  Mixin of engine._Plan."""
+the branch streams forked and joined inside the graph.  Mixin of engine._PlanBase."""
 import ctypes as C
 import os
 import torch
@@ -50,7 +50,7 @@ class PlanExecMixin:
         x = x.contiguous().float()
         only = getattr(events, 'only', None) if events is not None else None
         nodes = getattr(events, 'nodes', None) if events is not None else None
-        self._runs = getattr(self, '_runs', 0) + 1
+        self._runs += 1
         if plan_common.USE_GRAPH and (events is None or only or nodes) and self._runs > 2:
             return self._run_graphs(x, events, only, nodes)
         return self._run_eager(x, events, only)
@@ -69,7 +69,15 @@ class PlanExecMixin:
         self._set_input(x.data_ptr())
         if self.training:
             self.stats.zero_()
-        stream = torch.cuda.current_stream().cuda_stream
+        self._run_steps(torch.cuda.current_stream().cuda_stream, events, only)
+        if self.training and self.nbt:
+            torch._foreach_add_(self.nbt, 1)
+        self._x_keepalive = x
+        return loc, conf
+
+    def _run_steps(self, stream, events=None, only=None):
+        """Every step as an eager launch on ``stream``; with ``events`` the tagged ones (those named in ``only``, if given) between a pair of
+        HIP events."""
         for st in self.steps:
             if events is not None and st.tag is not None and (only is None or st.tag[0] in only):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -79,23 +87,21 @@ class PlanExecMixin:
                 events.append((st.tag, e0, e1))
             else:
                 self._launch(st, stream)
-        if self.training and self.nbt:
-            torch._foreach_add_(self.nbt, 1)
-        self._x_keepalive = x
-        return loc, conf
 
     def _run_graphs(self, x, events, only, nodes=None):
         key = (tuple(sorted(only)) if only else None) if not nodes else ('nodes', tuple(sorted(nodes)), tuple(sorted(only)) if only else None)
-        cache = self.__dict__.setdefault('_graphs', {})
+        if self._graphs is None:
+            self._graphs = {}
+        cache = self._graphs
         # Zero-copy input (round 6): a caller that hands over the SAME device buffer step after step (a training loop's pinned staging buffer, the
         # benchmark's resident batch) gets a graph whose first node reads that buffer in place -- the 138 MB x -> static-buffer copy in front of
         # every replay was 50 us of an 8.3 ms step.  A pointer seen twice in a row is captured (at most two such graphs per plan); any other
         # input takes the generic graph over the plan's static input buffer.
         ptr = x.data_ptr()
         dkey = ('direct', ptr, key)
-        if dkey not in cache and self.__dict__.get('_last_in_ptr') == ptr and sum(1 for k in cache if isinstance(k, tuple) and k[:1] == ('direct',)) < 2:
+        if dkey not in cache and self._last_in_ptr == ptr and sum(1 for k in cache if isinstance(k, tuple) and k[:1] == ('direct',)) < 2:
             cache[dkey] = self._capture(x, only, in_ptr=ptr, nodes=nodes)
-        self.__dict__['_last_in_ptr'] = ptr
+        self._last_in_ptr = ptr
         if dkey in cache:
             segs = cache[dkey]
             self._x_keepalive = x
@@ -115,20 +121,19 @@ class PlanExecMixin:
                 e1.record()
                 events.append((obj.tag, e0, e1))
         if nodes:
-            events.extend(self.__dict__.get('_node_events', {}).get(id(segs), ()))
+            events.extend(self._node_events.get(id(segs), ()))
         return self._gloc.clone(), self._gconf.clone()
 
     def _side_stream(self, sid):
-        pool = self.__dict__.setdefault('_side_streams', {})
-        if sid not in pool:
-            pool[sid] = torch.cuda.Stream(device=self.dev)
-        return pool[sid]
+        if sid not in self._side_streams:
+            self._side_streams[sid] = torch.cuda.Stream(device=self.dev)
+        return self._side_streams[sid]
 
     def _capture(self, x, only, in_ptr=None, nodes=None):
         """Capture the plan as hipGraph segments over static input / output buffers; the steps named in ``only`` stay eager.  ``in_ptr``: the graph
         reads the input at this address instead of the plan's static input buffer (zero-copy replay, _run_graphs)."""
         B, dev = self.B, self.dev
-        if getattr(self, '_gx', None) is None:
+        if self._gx is None:
             self._gx = torch.empty_like(x)
             self._gloc = torch.zeros(B, self.P, 4, device=dev, dtype=torch.float32)
             self._gconf = torch.zeros(B, self.P, self.nc, device=dev, dtype=torch.float32)
@@ -202,5 +207,5 @@ class PlanExecMixin:
             segs.append(('graph', g))
         # the capture itself does not execute anything: the caller's replay is the run
         if nodes:
-            self.__dict__.setdefault('_node_events', {})[id(segs)] = node_evs
+            self._node_events[id(segs)] = node_evs
         return segs

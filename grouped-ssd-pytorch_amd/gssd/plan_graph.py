@@ -1,5 +1,5 @@
 """The WALK over the module tree (models/ssd_multiphase_custom_group.py:217-400 restated as launches): which layer follows which, where the
-branches fork, where the heads reduce.  Mixin of engine._Plan; the per-op emitters it calls live in plan_ops.py."""
+branches fork, where the heads reduce.  Mixin of engine._PlanBase; the per-op emitters it calls live in plan_ops.py."""
 import ctypes as C
 import os
 import torch
@@ -16,7 +16,7 @@ class PlanGraphMixin:
         instead, the branch forks there: the trunk's heavy layers run alone, and the branch fills the chip under the small-map tail
         (SA-base, extras), whose launches have 1 .. 100 workgroups.  GSSD_BRANCH0_LATE=0 keeps the registration order."""
         # (measured: GSSD++ 12.14 -> 12.10 ms fp32, 3.89 -> 3.86 ms bf16; plain GSSD, whose branch 0 is two small launches, 5.55 -> 5.63 ms)
-        if (os.environ.get('GSSD_BRANCH0_LATE', '1') == '0' or getattr(self, '_mark_conv7', None) is None
+        if (os.environ.get('GSSD_BRANCH0_LATE', '1') == '0' or self._mark_conv7 is None
                 or not self.eng.net.use_self_attention):
             return
         idx = [i for i, st in enumerate(self.steps) if st.sid == 1]
@@ -44,7 +44,7 @@ class PlanGraphMixin:
         batch 32).  Whenever the library's patch-staged kernel declines the descriptor (bf16 storage, other group counts, the plain
         graph's conv + ReLU launch) the pack step stays.  Called last: every step index behind the pack moves down by one."""
         i = self._pack_step
-        if (not plan_common.FUSE_PACK or not getattr(self, 'nograd', False) or self.bf16 or i + 1 >= len(self.steps)
+        if (not plan_common.FUSE_PACK or not self.nograd or self.bf16 or i + 1 >= len(self.steps)
                 or self.steps[i].fn is not lib.gssd_pack_input_nhwc):
             return
         st, x16_ptr = self.steps[i + 1], self.steps[i].args[1]
@@ -59,9 +59,8 @@ class PlanGraphMixin:
 
     def _set_input(self, ptr):
         """The address the step reads its NCHW batch from: the pack launch's source, or conv1_1's input (_fuse_input_pack)."""
-        d = self.__dict__.get('_in_desc')
-        if d is not None:
-            d.in_ = ptr
+        if self._in_desc is not None:
+            self._in_desc.in_ = ptr
         else:
             self.steps[self._pack_step].args[0] = ptr
 
@@ -194,17 +193,16 @@ class PlanGraphMixin:
         for d in self.head_descs:
             d.out, d.out_b = self._ws_loc.data_ptr(), self._ws_conf.data_ptr()
             d.flags |= _lib.CONV_HEADS_SLICES
-        prev, self._sid = getattr(self, '_sid', 0), 0
         self._pending_wait = ALL_STREAMS                      # the heads run on the branch streams: join them all first
-        if plan_common.FUSE_HEADS_REDUCE:                     # one launch for both heads (GSSD_FUSE_HEADS_REDUCE=0: one each)
-            self._reduce_steps = (len(self.steps),)
-            self._add(lib.gssd_heads_reduce2_f32, [self._ws_loc.data_ptr(), self._ws_conf.data_ptr(), self._head_splits.data_ptr(), 0, 0,
-                                                   B, self.P, self.nc])
-        else:
-            self._reduce_steps = (len(self.steps), len(self.steps) + 1)
-            self._add(lib.gssd_heads_reduce_f32, [self._ws_loc.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, 4])
-            self._add(lib.gssd_heads_reduce_f32, [self._ws_conf.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, self.nc])
-        self._sid = prev
+        with self._on_stream(0):
+            if plan_common.FUSE_HEADS_REDUCE:                 # one launch for both heads (GSSD_FUSE_HEADS_REDUCE=0: one each)
+                self._reduce_steps = (len(self.steps),)
+                self._add(lib.gssd_heads_reduce2_f32, [self._ws_loc.data_ptr(), self._ws_conf.data_ptr(), self._head_splits.data_ptr(), 0, 0,
+                                                       B, self.P, self.nc])
+            else:
+                self._reduce_steps = (len(self.steps), len(self.steps) + 1)
+                self._add(lib.gssd_heads_reduce_f32, [self._ws_loc.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, 4])
+                self._add(lib.gssd_heads_reduce_f32, [self._ws_conf.data_ptr(), self._head_splits.data_ptr(), 0, B, self.P, self.nc])
 
     def _set_outputs(self, loc, conf):
         if len(self._reduce_steps) == 1:
@@ -219,7 +217,7 @@ class PlanGraphMixin:
         both launches (plan_ops._sa_on_x6, the rule _self_attn itself uses; a descriptor the kernel then declines for another reason is an
         error at plan build, never a silently untransformed read)."""
         net = self.eng.net
-        return bool(plan_common.FUSE_SA_BN and getattr(self, 'nograd', False) and not self.bf16 and not self.want_maps
+        return bool(plan_common.FUSE_SA_BN and self.nograd and not self.bf16 and not self.want_maps
                     and net.use_self_attention_base and Cc <= 512 and (Cc // 4) % 64 == 0 and all(self._sa_on_x6(H, Cc)))
 
     def _after_conv4_3(self, x, H, Cc, xf=None):
@@ -229,7 +227,7 @@ class PlanGraphMixin:
         attn_g, cat_g = None, 0
         if net.use_self_attention_base:
             # no backward, fp32: the block's o conv writes slice_and_cat's result itself where its kernel can (plan_ops._self_attn)
-            cat_g = (net.groups_vgg if (plan_common.FUSE_CAT and getattr(self, 'nograd', False) and not self.bf16 and net.use_dcn
+            cat_g = (net.groups_vgg if (plan_common.FUSE_CAT and self.nograd and not self.bf16 and net.use_dcn
                                         and net.dcn_cat_sab) else 0)
             x, attn_g = self._self_attn('self_attn_base_list', 0, x, H, Cc, need_out2=bool(net.dcn_cat_sab), want_map=self.want_maps,
                                         cat_groups=cat_g, in_xf=xf)
@@ -250,15 +248,13 @@ class PlanGraphMixin:
             x, Cc = xin, Cin
         self.x_after_block = x
         s = self._abuf(B, H, H, Cc)
-        self._sid = 1                              # L2Norm opens branch 0
-        self._add(lib.gssd_l2norm_bf16 if self.bf16 else lib.gssd_l2norm_f32,
-                  (x.data_ptr(), net.L2Norm.weight.data_ptr(), s.data_ptr(), B * H * H, Cc, float(net.L2Norm.eps)))
-        self.rec.append(('l2norm', dict(x_in=x, out=s, H=H, C=Cc, mod=net.L2Norm)))
-        self._sid = 0
+        with self._on_stream(1):                   # L2Norm opens branch 0
+            self._add(lib.gssd_l2norm_bf16 if self.bf16 else lib.gssd_l2norm_f32,
+                      (x.data_ptr(), net.L2Norm.weight.data_ptr(), s.data_ptr(), B * H * H, Cc, float(net.L2Norm.eps)))
+            self.rec.append(('l2norm', dict(x_in=x, out=s, H=H, C=Cc, mod=net.L2Norm)))
         src0 = self._branch(s, H, Cc, 0, '11')
-        self._layer = 'vgg.33'                     # pool4: a trunk pass (conv5_1 reads it)
-        pooled, Hp = self._pool_only(x, H, Cc, 2, 2, 0)
-        self._layer = None
+        with self._in_layer('vgg.33'):             # pool4: a trunk pass (conv5_1 reads it)
+            pooled, Hp = self._pool_only(x, H, Cc, 2, 2, 0)
         return pooled, Hp, Cc, src0
 
     def _branch(self, s, H, Cc, sa_i, fuse):
@@ -267,20 +263,19 @@ class PlanGraphMixin:
         run beside the trunk's continuation (on the small maps a kernel has 1..100 workgroups for 256 CUs)."""
         net = self.eng.net
         xf = None
-        prev, self._sid = getattr(self, '_sid', 0), sa_i + 1
-        if net.use_self_attention:
-            s, _ = self._self_attn('self_attn_list', sa_i, s, H, Cc, need_out2=False, want_map=self.want_maps)
-        if net.use_fuseconv and net.batch_norm:
-            conv, bn = getattr(net, f'fuse_{fuse}'), getattr(net, f'bn_fuse_{fuse}')
-            # no backward, fp32: the activated source has ONE reader, its head conv, which applies the BatchNorm + ReLU on read (zero padding
-            # through in_pad); self.sources then holds the RAW map.  fuse_21 (1024 channels: beyond the kernels' 512-entry tables) keeps its pass
-            defer = bool(plan_common.FUSE_HEAD_BN and getattr(self, 'nograd', False) and not self.bf16 and not self.want_maps
-                         and conv.out_channels <= 512)
-            s, H, Cc, xf = self._conv_bn(f'fuse_{fuse}', conv, bn, s, H, Cc, 1, relu=True, defer_bn=defer)
-        elif net.use_fuseconv:
-            s, H, Cc = self._conv_act(f'fuse_{fuse}', getattr(net, f'fuse_{fuse}'), s, H, Cc, 1)
-        self._head(sa_i, s, H, Cc, in_xf=xf)
-        self._sid = prev
+        with self._on_stream(sa_i + 1):
+            if net.use_self_attention:
+                s, _ = self._self_attn('self_attn_list', sa_i, s, H, Cc, need_out2=False, want_map=self.want_maps)
+            if net.use_fuseconv and net.batch_norm:
+                conv, bn = getattr(net, f'fuse_{fuse}'), getattr(net, f'bn_fuse_{fuse}')
+                # no backward, fp32: the activated source has ONE reader, its head conv, which applies the BatchNorm + ReLU on read (zero padding
+                # through in_pad); self.sources then holds the RAW map.  fuse_21 (1024 channels: beyond the kernels' 512-entry tables) keeps its pass
+                defer = bool(plan_common.FUSE_HEAD_BN and self.nograd and not self.bf16 and not self.want_maps
+                             and conv.out_channels <= 512)
+                s, H, Cc, xf = self._conv_bn(f'fuse_{fuse}', conv, bn, s, H, Cc, 1, relu=True, defer_bn=defer)
+            elif net.use_fuseconv:
+                s, H, Cc = self._conv_act(f'fuse_{fuse}', getattr(net, f'fuse_{fuse}'), s, H, Cc, 1)
+            self._head(sa_i, s, H, Cc, in_xf=xf)
         # (scale, shift, pad) where the source map is RAW (its BatchNorm + ReLU deferred to the head), else None: readers of plan.sources
-        self.__dict__.setdefault('sources_xf', {})[sa_i] = xf
+        self.sources_xf[sa_i] = xf
         return (s, H, Cc)

@@ -1,6 +1,6 @@
 """Per-op emitters of the forward launch plan: conv + BatchNorm (+ ReLU / pool), stand-alone pools, the merged loc | conf heads, spectral
 norm, Self_Attn (layers/self_attn.py:46-89) and the deformable conv (layers/dcn_v2_custom.py:79-89).  Each appends its launches to the
-plan and a record for the backward.  Mixin of engine._Plan."""
+plan and a record for the backward.  Mixin of engine._PlanBase."""
 import ctypes as C
 import os
 import torch
@@ -10,6 +10,20 @@ from . import plan_common
 from .plan_common import DCN_X6, HEAD_OFF, MBOX, SN_STREAM, USE_CONV_X6, USE_FLASH_X6, USE_HEADS_WINO, USE_PATCH_X6, USE_WINOGRAD
 
 
+def bn_arena(dev, modules, replicated):
+    """The fp64 batch-sum arena of the BatchNorm layers among ``modules``: (sum, sum of squares) per channel of each, ``replicated`` (ids) in
+    R = max(1, min(32, 2048 // channels)) replicas.  Returns (arena, {id: its slice}, {id: replicas}, the num_batches_tracked counters)."""
+    uniq = list({id(m): m for m in modules if isinstance(m, torch.nn.BatchNorm2d)}.values())
+    rep = {id(m): (max(1, min(32, 2048 // m.num_features)) if id(m) in replicated else 1) for m in uniq}
+    stats = torch.zeros(max(sum(2 * m.num_features * rep[id(m)] for m in uniq), 2), device=dev, dtype=torch.float64)
+    stat_of, off = {}, 0
+    for m in uniq:
+        n = 2 * m.num_features * rep[id(m)]
+        stat_of[id(m)] = stats[off:off + n]
+        off += n
+    return stats, stat_of, rep, [m.num_batches_tracked for m in uniq]
+
+
 class PlanOpsMixin:
     @property
     def f16_ok(self):
@@ -17,24 +31,46 @@ class PlanOpsMixin:
         activation map by |gamma| sqrt(n) + |beta|, far inside fp16's range, so the split-operand kernels may use their fp16 planes (three MFMAs per
         product).  Eval mode normalises with running statistics, which bound nothing, and so does a graph built with batch_norm=False (tests/test_gpu_pixellink.py's synthetic eval graph reaches
         1e12): those launches keep the bf16 planes (include/gssd_hip.h: GSSD_CONV_F16_OK)."""
-        net = getattr(getattr(self, 'eng', None), 'net', None)
-        bn = bool(getattr(net, 'batch_norm', False))          # (a graph without BatchNorm -- batch_norm=False, the vanilla SSD -- bounds nothing either)
-        return _lib.CONV_F16_OK if (bn and not getattr(self, 'bf16', False) and getattr(self, 'training', False)) else 0
+        bn = bool(getattr(self.eng.net, 'batch_norm', False))          # (a graph without BatchNorm -- batch_norm=False, the vanilla SSD -- bounds nothing either)
+        return _lib.CONV_F16_OK if (bn and not self.bf16 and self.training) else 0
 
-    def _conv_act(self, name, conv, x, H, Cin, groups):
-        """(grouped) conv + bias + ReLU in ONE launch (ReLU in the conv epilogue): the batch_norm=False layers."""
+    def _weight_forms(self, name, groups, cin_g, wino=False, x6_tile=0, taps=9):
+        """Register the derived forms of the packed weight ``name``.w BEHIND it (pack jobs run in registration order, so they are refreshed after
+        it): ``name``.U, the Winograd F(2x2,3x3) transform (``wino``), and ``name``.x6@tile, csrc/conv_x6.hip's three-plane layout for column tile
+        ``x6_tile`` (the tile is part of the layout, so part of the key).  Returns (U, X6), None where not asked for."""
+        eng, key = self.eng, name + '.w'
+        U = X6 = None
+        if wino:
+            U = eng._pack(name + '.U', lambda out: ops.winograd_weight(eng._packed[key], groups, cin_g, out))
+        if x6_tile:
+            X6 = eng._pack(name + f'.x6@{x6_tile}', lambda out: ops.x6_weight(eng._packed[key], groups, cin_g, taps, x6_tile, out))
+        return U, X6
+
+    def _conv_bias(self, name, conv, x, H, Cin, groups=1, *, relu=False, in_xf=None, forms=False, weight=None, rec=()):
+        """(grouped) conv + bias in ONE fp32 launch, ``relu`` in its epilogue or left to the reader: every conv without BatchNorm.  ``in_xf`` =
+        (scale, shift, pad) of a transform applied on read; ``forms``: also the Winograd / x6 weight forms where the shape wants them;
+        ``weight``: the caller's own pack job for ``name``.w (the vanilla conv1_1's channel pad); ``rec``: what the caller's 'convrelu'
+        record carries beyond the common keys (the backward reads them)."""
         B = self.B
         k, s, p, dl = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
         Cout = conv.out_channels
-        wp = self._packed_conv(name, conv)
+        cin_g, cout_g = Cin // groups, Cout // groups
+        wp = self.eng._pack(name + '.w', weight) if weight else self._packed_conv(name, conv)
         Ho = (H + 2 * p - dl * (k - 1) - 1) // s + 1
+        wino = bool(forms and USE_WINOGRAD and ops.winograd_eligible(k, s, p, dl, cin_g, cout_g, groups))
+        x6 = forms and USE_CONV_X6 and ops.x6_wanted(k, cin_g, cout_g, groups, B * Ho * Ho, winograd=wino)
+        U, X6 = self._weight_forms(name, groups, cin_g, wino, ops.x6_tile(cout_g, groups, B * Ho * Ho) if x6 else 0, k * k)
         out = self._buf(B, Ho, Ho, Cout)
-        d, _, _ = ops.make_conv_desc(x, wp, out, B=B, H=H, W=H, in_stride=Cin, cin_g=Cin // groups, Cout=Cout, groups=groups, k=k,
-                                     stride=s, pad=p, dil=dl, bias=conv.bias.detach(), relu=True)
-        self._add(lib.gssd_conv2d_nhwc_f32, (C.byref(d),), keep=d)
+        d, _, _ = ops.make_conv_desc(x, wp, out, B=B, H=H, W=H, in_stride=Cin, cin_g=cin_g, Cout=Cout, groups=groups, k=k,
+                                     stride=s, pad=p, dil=dl, bias=conv.bias.detach(), relu=relu, wgt_wino=U, wgt_x6=X6, **ops.xf_kw(in_xf))
+        self._add(lib.gssd_conv2d_nhwc_f32, (C.byref(d),), keep=(d, in_xf) if in_xf else d)
         self.rec.append(('convrelu', dict(name=name, conv=conv, x_in=x, out=out, H=H, Cin=Cin, Ho=Ho, Cout=Cout, desc=d, k=k,
-                                          stride=s, pad=p, dil=dl, groups=groups)))
+                                          stride=s, pad=p, dil=dl, **dict(rec))))
         return out, Ho, Cout
+
+    def _conv_act(self, name, conv, x, H, Cin, groups):
+        """(grouped) conv + bias + ReLU in ONE launch (ReLU in the conv epilogue): the batch_norm=False layers."""
+        return self._conv_bias(name, conv, x, H, Cin, groups, relu=True, rec=dict(groups=groups))
 
     def _head(self, i, s, Hs, Cs, in_xf=None):
         """loc[i] / conf[i] (models/...group.py:375-380) as ONE merged 3x3 conv writing straight into the concatenated fp32
@@ -70,16 +106,12 @@ class PlanOpsMixin:
                 and ops.winograd_eligible(3, 1, 1, 1, Cs, nloc + nconf, 1)):
             # train-mode fp32 forward, large map (38 x 38 at batch >= 23): Winograd on fp16 planes with the heads' two-destination epilogue
             # (csrc/conv_wino_x6.hip: 95 us against 173 us for the implicit GEMM and its two reduction slices); one slice
-            def build_u(out, key=f'heads.{i}.w', cin=Cs):
-                return ops.winograd_weight(eng._packed[key], 1, cin, out)
-            U = eng._pack(f'heads.{i}.U', build_u)
+            U, _ = self._weight_forms(f'heads.{i}', 1, Cs, wino=True)
             split = 1
         d, _, _ = ops.make_conv_desc(s, wp, None, B=B, H=Hs, W=Hs, in_stride=Cs, cin_g=Cs, Cout=nloc + nconf, k=3,
                                      pad=1, bias=bp, out_mode=_lib.OUT_HEADS, out_b=None, split_n=nloc,
                                      out_batch_stride=self.P * 4, outb_batch_stride=self.P * self.nc,
-                                     out_off=off * 4, outb_off=off * self.nc, split_k=split, wgt_wino=U,
-                                     in_scale=in_xf[0] if in_xf else None, in_shift=in_xf[1] if in_xf else None,
-                                     in_pad=in_xf[2] if in_xf else None,
+                                     out_off=off * 4, outb_off=off * self.nc, split_k=split, wgt_wino=U, **ops.xf_kw(in_xf),
                                      flags=_lib.CONV_OUT_F32 | (self.f16_ok if U is not None else 0))
         self.head_descs.append(d)
         self._add(self.conv_fn, (C.byref(d),), keep=d)
@@ -88,8 +120,6 @@ class PlanOpsMixin:
     def _setup_spectral_norm(self, lists):
         """layers/spectral_norm.py:74-89 for every Self_Attn conv of ``lists`` = [(list name, ModuleList)]: ONE launch that
         (training) runs the power iteration in place and writes 1/sigma per output channel (the convs' ``alpha`` vectors)."""
-        self.sn_items = []
-        self.sa_state = {}
         for lst_name, lst in lists:
             for i, sa in enumerate(lst):
                 Cc = sa.in_channels
@@ -106,9 +136,8 @@ class PlanOpsMixin:
             self.sn_dev = ops.sn_items_tensor([(w.detach(), u, v, s) for (w, u, v, s) in self.sn_items], self.dev)
             # one workgroup per matrix (48 of 256 CUs, ~180 us): on its own stream beside conv1_1 .. conv4_3 inside the graph; the
             # first Self_Attn launch joins it (every later one forks from the trunk after that point)
-            prev, self._sid = getattr(self, '_sid', 0), SN_STREAM
-            self._add(lib.gssd_spectral_norm_f32, (self.sn_dev.data_ptr(), len(self.sn_items), int(self.training), 1e-12))
-            self._sid = prev
+            with self._on_stream(SN_STREAM):
+                self._add(lib.gssd_spectral_norm_f32, (self.sn_dev.data_ptr(), len(self.sn_items), int(self.training), 1e-12))
             self._sn_unjoined = True
 
     def _packed_conv(self, name, conv):
@@ -124,78 +153,56 @@ class PlanOpsMixin:
         """conv (raw output + fp64 batch sums) -> BN + ReLU (+ max-pool).  ``in_xf`` = (scale, shift, pad) of a producer
         whose BN + ReLU this conv applies on the fly; ``defer_bn`` leaves this layer's own BN + ReLU to its consumer and
         returns (raw, H, C, (scale, shift, pad))."""
+        with self._in_layer(name):
+            return self._conv_bn_steps(name, conv, bn, x, H, Cin, groups, relu, pool, in_xf, defer_bn)
+
+    def _conv_bn_steps(self, name, conv, bn, x, H, Cin, groups, relu, pool, in_xf, defer_bn):
         B = self.B
-        self._layer = name
         k, s, p, dl = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
         Cout = conv.out_channels
-        cin_g = Cin // groups
-        if defer_bn and Cout // groups > 512:
+        cin_g, cout_g = Cin // groups, Cout // groups
+        if defer_bn and cout_g > 512:
             defer_bn = False        # the consumer (same group count) would read more than 512 channels per group: the conv kernels' fused
             #                         input transform keeps at most 512 scale / shift pairs (ungrouped conv6 -> conv7 at groups_vgg = 1)
         wp = self._packed_conv(name, conv)
-        U = None
-        if not self.bf16 and USE_WINOGRAD and ops.winograd_eligible(k, s, p, dl, cin_g, Cout // groups, groups):
-            def build_u(out, key=name + '.w', groups=groups, cin_g=cin_g):
-                return ops.winograd_weight(self.eng._packed[key], groups, cin_g, out)
-            U = self.eng._pack(name + '.U', build_u)          # registered after '.w', so refreshed after it
         Ho = (H + 2 * p - dl * (k - 1) - 1) // s + 1
-        X6 = None
-        if not self.bf16 and USE_CONV_X6 and ops.x6_wanted(k, cin_g, Cout // groups, groups, B * Ho * Ho, winograd=U is not None, forward=bool(self.f16_ok)):
-            def build_x6(out, key=name + '.w', groups=groups, cin_g=cin_g, taps=k * k, bn=ops.x6_tile(Cout // groups, groups, B * Ho * Ho)):
-                return ops.x6_weight(self.eng._packed[key], groups, cin_g, taps, bn, out)
-            X6 = self.eng._pack(name + f'.x6@{ops.x6_tile(Cout // groups, groups, B * Ho * Ho)}', build_x6)       # the tile is part of the packed layout: part of the key       # (after '.w' as well)
+        wino = bool(not self.bf16 and USE_WINOGRAD and ops.winograd_eligible(k, s, p, dl, cin_g, cout_g, groups))
+        x6 = not self.bf16 and USE_CONV_X6 and ops.x6_wanted(k, cin_g, cout_g, groups, B * Ho * Ho, winograd=wino, forward=bool(self.f16_ok))
+        U, X6 = self._weight_forms(name, groups, cin_g, wino, ops.x6_tile(cout_g, groups, B * Ho * Ho) if x6 else 0, k * k)
         st = self.eng_stat(bn)
-        srep = getattr(self, 'stat_rep', {}).get(id(bn), 0) if self.training else 0
+        srep = self.stat_rep.get(id(bn), 0) if self.training else 0
+        common = dict(B=B, H=H, W=H, in_stride=Cin, cin_g=cin_g, Cout=Cout, groups=groups, k=k, stride=s, pad=p, dil=dl, bias=conv.bias.detach(),
+                      wgt_wino=U, stats=st if self.training else None, stats_rep=srep, **ops.xf_kw(in_xf))
+        rec = dict(name=name, conv=conv, bn=bn, x_in=x, in_xf=in_xf, H=H, Cin=Cin, groups=groups, Ho=Ho, Cout=Cout, stats=st, stats_rep=srep,
+                   pool=pool, relu=relu, k=k, stride=s, pad=p, dil=dl)
         # Pooled trunk layers of a no-backward forward (conv1_2, conv2_2, conv3_3): max-pooling commutes with the monotone BatchNorm +
         # ReLU, and the direction of monotonicity is the sign of the BatchNorm weight, known before the launch.  The conv's epilogue
         # writes max- (gamma >= 0) or min- (gamma < 0) pooled RAW outputs, a quarter of the map, with the batch sums of the full map;
         # the separate BatchNorm + ReLU + pool pass disappears and the next conv applies the deferred BatchNorm + ReLU to the pooled
         # raw map on read: bit-identical activations (include/gssd_hip.h: GSSD_CONV_POOL2), the full-resolution raw map is never
         # written or re-read (conv1_2 in bf16: 369 MB written + 369 MB re-read + 92 MB written become 92 MB written).
-        cout_g = Cout // groups
-        pooled = (getattr(self, 'nograd', False) and relu and pool is not None and pool[:3] == (2, 2, 0) and (pool[3] or Ho % 2 == 0) and k == 3 and s == 1
+        pooled = (self.nograd and relu and pool is not None and pool[:3] == (2, 2, 0) and (pool[3] or Ho % 2 == 0) and k == 3 and s == 1
                   and p == 1 and dl == 1 and groups == 4 and
-                  ((U is not None) if not self.bf16 else ((cin_g, cout_g) in ((16, 16), (32, 32)) and Ho % 2 == 0 and Ho * Ho >= 75 * 75)))
+                  (wino if not self.bf16 else ((cin_g, cout_g) in ((16, 16), (32, 32)) and Ho % 2 == 0 and Ho * Ho >= 75 * 75)))
         if pooled:
             Hp = ops.pool_out_size(Ho, 2, 2, 0, pool[3])
             raw, pd = self._abuf_tail(Cout, B, Hp, Hp, Cout)
-            d, _, _ = ops.make_conv_desc(x, wp, raw, B=B, H=H, W=H, in_stride=Cin, cin_g=cin_g, Cout=Cout, groups=groups, k=k,
-                                         stride=s, pad=p, dil=dl, bias=conv.bias.detach(), wgt_wino=U,
-                                         stats=st if self.training else None,
-                                         in_scale=in_xf[0] if in_xf else None, in_shift=in_xf[1] if in_xf else None,
-                                         in_pad=in_xf[2] if in_xf else None, flags=_lib.CONV_POOL2 | self.f16_ok, pool_sign=bn.weight.detach(), stats_rep=srep)
+            d, _, _ = ops.make_conv_desc(x, wp, raw, flags=_lib.CONV_POOL2 | self.f16_ok, pool_sign=bn.weight.detach(), **common)
             self._add(self.conv_fn, (C.byref(d),), keep=d)
-            sc, sh = self._buf(Cout), self._buf(Cout)
-            self._add(lib.gssd_bn_finalize_bf16 if self.bf16 else lib.gssd_bn_finalize_f32,
-                      (st.data_ptr(), float(B * Ho * Ho), bn.weight.data_ptr(), bn.bias.data_ptr(),
-                       bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps),
-                       int(self.training), Cout, sc.data_ptr(), sh.data_ptr(), pd.data_ptr(), srep))
-            self.rec.append(('convbn', dict(name=name, conv=conv, bn=bn, x_in=x, in_xf=in_xf, H=H, Cin=Cin, groups=groups, raw=raw, Ho=Ho,
-                                            Cout=Cout, desc=d, stats=st, stats_rep=srep, pool=pool, relu=relu, k=k, stride=s, pad=p, dil=dl, out=raw,
-                                            Hp=Hp, xf=(sc, sh, pd), pooled=True)))
-            self._layer = None
-            return raw, Hp, Cout, (sc, sh, pd)
-        raw, pd_tail = self._abuf_tail(Cout, B, Ho, Ho, Cout) if defer_bn else (self._abuf(B, Ho, Ho, Cout), None)
-        d, _, _ = ops.make_conv_desc(x, wp, raw, B=B, H=H, W=H, in_stride=Cin, cin_g=cin_g, Cout=Cout, groups=groups, k=k,
-                                     stride=s, pad=p, dil=dl, bias=conv.bias.detach(), wgt_wino=U, wgt_x6=X6,
-                                     stats=st if self.training else None,
-                                     in_scale=in_xf[0] if in_xf else None, in_shift=in_xf[1] if in_xf else None,
-                                     in_pad=in_xf[2] if in_xf else None, stats_rep=srep,
-                                     flags=self.f16_ok)      # fp32 mode, train-mode network: forward launches on activation maps may use the x6 kernels' fp16 planes
+            xf = self._bn_finalize(st, B * Ho * Ho, bn, Cout, pd, srep)
+            self.rec.append(('convbn', dict(rec, raw=raw, desc=d, out=raw, Hp=Hp, xf=xf, pooled=True)))
+            return raw, Hp, Cout, xf
+        raw, pd = self._abuf_tail(Cout, B, Ho, Ho, Cout) if defer_bn else (self._abuf(B, Ho, Ho, Cout), None)
+        # (fp32 mode, train-mode network: forward launches on activation maps may use the x6 kernels' fp16 planes)
+        d, _, _ = ops.make_conv_desc(x, wp, raw, wgt_x6=X6, flags=self.f16_ok, **common)
         self._add(self.conv_fn, (C.byref(d),), keep=d)
-        rec = dict(name=name, conv=conv, bn=bn, x_in=x, in_xf=in_xf, H=H, Cin=Cin, groups=groups, raw=raw, Ho=Ho, Cout=Cout,
-                   desc=d, stats=st, stats_rep=srep, pool=pool, relu=relu, k=k, stride=s, pad=p, dil=dl)
+        rec.update(raw=raw, desc=d)
         self.rec.append(('convbn', rec))
         if defer_bn:
             assert pool is None and relu
-            sc, sh, pd = self._buf(Cout), self._buf(Cout), pd_tail
-            self._add(lib.gssd_bn_finalize_bf16 if self.bf16 else lib.gssd_bn_finalize_f32,
-                      (st.data_ptr(), float(B * Ho * Ho), bn.weight.data_ptr(), bn.bias.data_ptr(),
-                       bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps),
-                       int(self.training), Cout, sc.data_ptr(), sh.data_ptr(), pd.data_ptr(), srep))
-            rec.update(out=raw, Hp=Ho, xf=(sc, sh, pd))
-            self._layer = None
-            return raw, Ho, Cout, (sc, sh, pd)
+            xf = self._bn_finalize(st, B * Ho * Ho, bn, Cout, pd, srep)
+            rec.update(out=raw, Hp=Ho, xf=xf)
+            return raw, Ho, Cout, xf
         if pool:
             pk, ps, pp, ceil = pool
             Hp = ops.pool_out_size(Ho, pk, ps, pp, ceil)
@@ -205,23 +212,36 @@ class PlanOpsMixin:
         self._add(lib.gssd_bn_relu_pool_bf16 if self.bf16 else lib.gssd_bn_relu_pool_f32,
                   (raw.data_ptr(), act.data_ptr(), B, Ho, Ho, Cout, Hp, Hp, pk, ps, pp, st.data_ptr(), float(B * Ho * Ho),
                    bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                   float(bn.momentum), float(bn.eps), int(self.training), int(relu), srep),
-                  tag=('bn_relu_pool_bf16' if self.bf16 else 'bn_relu_pool', 0.0,
-                       (2.0 if self.bf16 else 4.0) * B * Cout * (Ho * Ho + Hp * Hp)))
+                   float(bn.momentum), float(bn.eps), int(self.training), int(relu), srep), tag=self._pool_tag(Cout, Ho, Hp))
         rec.update(out=act, Hp=Hp, xf=None)
-        self._layer = None
         return act, Hp, Cout, None
+
+    def _bn_finalize(self, st, count, bn, Cout, pd, srep):
+        """The launch that turns a layer's batch sums ``st`` (or its running statistics) into the (scale, shift, padding value) vectors its
+        consumer applies on read, and updates the running statistics; returns (scale, shift, pad)."""
+        sc, sh = self._buf(Cout), self._buf(Cout)
+        self._add(lib.gssd_bn_finalize_bf16 if self.bf16 else lib.gssd_bn_finalize_f32,
+                  (st.data_ptr(), float(count), bn.weight.data_ptr(), bn.bias.data_ptr(),
+                   bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps),
+                   int(self.training), Cout, sc.data_ptr(), sh.data_ptr(), pd.data_ptr(), srep))
+        return sc, sh, pd
+
+    def _pool_tag(self, Cc, H, Hp):
+        return ('bn_relu_pool_bf16' if self.bf16 else 'bn_relu_pool', 0.0, (2.0 if self.bf16 else 4.0) * self.B * Cc * (H * H + Hp * Hp))
 
     def eng_stat(self, bn):
         return self.stat_of[id(bn)]
 
-    def _pool_only(self, x, H, Cc, k, s, p, ceil=False):
-        B = self.B
-        Hp = ops.pool_out_size(H, k, s, p, ceil)
-        out = self._abuf(B, Hp, Hp, Cc)
+    def _identity_pool(self, x, out, H, Cc, Hp, k, s, p, relu=False, tag=True):
+        """The BatchNorm + ReLU + pool pass with the identity affine (no statistics: scale 1, shift 0): a bare max-pool and / or ReLU."""
         self._add(lib.gssd_bn_relu_pool_bf16 if self.bf16 else lib.gssd_bn_relu_pool_f32,
-                  (x.data_ptr(), out.data_ptr(), B, H, H, Cc, Hp, Hp, k, s, p, 0, 1.0, 0, 0, 0, 0, 0.1, 1e-5, 0, 0, 0),
-                  tag=('bn_relu_pool_bf16' if self.bf16 else 'bn_relu_pool', 0.0, (2.0 if self.bf16 else 4.0) * B * Cc * (H * H + Hp * Hp)))
+                  (x.data_ptr(), out.data_ptr(), self.B, H, H, Cc, Hp, Hp, k, s, p, 0, 1.0, 0, 0, 0, 0, 0.1, 1e-5, 0, int(relu), 0),
+                  tag=self._pool_tag(Cc, H, Hp) if tag else None)
+
+    def _pool_only(self, x, H, Cc, k, s, p, ceil=False, tag=True):
+        Hp = ops.pool_out_size(H, k, s, p, ceil)
+        out = self._abuf(self.B, Hp, Hp, Cc)
+        self._identity_pool(x, out, H, Cc, Hp, k, s, p, tag=tag)
         self.rec.append(('pool', dict(x_in=x, out=out, H=H, C=Cc, k=k, s=s, p=p, Hp=Hp)))
         return out, Hp
 
@@ -245,8 +265,8 @@ class PlanOpsMixin:
         eng, B = self.eng, self.B
         sa = getattr(eng.net, lst_name)[idx]
         a_tpg, a_o = self.sa_state[(lst_name, idx)]
-        if self.__dict__.pop('_sn_unjoined', False):
-            self._pending_wait = SN_STREAM          # the next launch added (this block's projection) waits for the 1/sigma vectors
+        if self._sn_unjoined:
+            self._sn_unjoined, self._pending_wait = False, SN_STREAM          # the next launch added (this block's projection) waits for the 1/sigma vectors
         N = H * H
         Np = ops.round_up(N, 4)
         C8, C2, C4 = Cc // 8, Cc // 2, Cc // 4
@@ -287,20 +307,18 @@ class PlanOpsMixin:
         # fp32, N % 4 == 0 (38 x 38): all images as ONE M range -- 361 full row tiles instead of 12 per image with a ragged last one,
         # and the plain-GEMM dispatch (slot stream) instead of the per-image one
         flat = not self.bf16 and N % 4 == 0 and Np == N
-        xin = dict(in_scale=in_xf[0], in_shift=in_xf[1], in_pad=in_xf[2]) if in_xf else {}
+        xin = ops.xf_kw(in_xf)
         rxf = _lib.CONV_RESID_XF if in_xf else 0       # the o conv: in_scale / in_shift are its RESIDUAL's (include/gssd_hip.h)
         tpg_on_x6, o_on_x6 = self._sa_on_x6(H, Cc)
         x6_tpg = None
         if tpg_on_x6:
-            def build_x6p(out, key=name + '.tpg.w', bn=ops.x6_tile(C4 + C2, 1, B * N)):
-                return ops.x6_weight(eng._packed[key], 1, Cc, 1, bn, out)
-            x6_tpg = eng._pack(name + f'.tpg.x6@{ops.x6_tile(C4 + C2, 1, B * N)}', build_x6p)
+            _, x6_tpg = self._weight_forms(name + '.tpg', 1, Cc, x6_tile=ops.x6_tile(C4 + C2, 1, B * N), taps=1)
         # No backward, fp32, the three-plane core (38 x 38 blocks): the projection's epilogue writes the core's bf16 planes itself where
         # csrc/conv_x6.hip takes the flagged descriptor (GSSD_CONV_OUT_X6PLANES) -- no split pass, and the fp32 theta | phi / g^T arrays do not
         # exist (the record's tp / gT are None).  GSSD_FUSE_SPLIT=0, want_map (its logits GEMM reads the fp32 theta | phi), pooled keys and the
         # opt-in fp16-plane core keep the two-pass entry.
         d1 = ws_planes = tp = gT = None
-        if (plan_common.FUSE_SPLIT and getattr(self, 'nograd', False) and not want_map and x6_tpg is not None and flat and C4 % 64 == 0
+        if (plan_common.FUSE_SPLIT and self.nograd and not want_map and x6_tpg is not None and flat and C4 % 64 == 0
                 and max(H // int(sa.max_pool_factor), 1) == H and USE_FLASH_X6 and N >= 1024 and C8 == 64
                 and lib.gssd_self_attn_core_x6_supported(C8, C2) and os.environ.get('GSSD_FLASH_X6_F16', '0') != '1'):
             Np32 = ops.round_up(N, 32)
@@ -403,7 +421,6 @@ class PlanOpsMixin:
             self._add(lib.gssd_conv2d_nhwc_f32, (C.byref(d3),), keep=d3)        # fp32 operands in both modes
             self._add(lib.gssd_softmax_rows_f32, (S.data_ptr(), B * N, Nk, Nkp))
         self._add(fn, (C.byref(d5),), keep=d5)
-        self.attn_maps = getattr(self, 'attn_maps', {})
         self.attn_maps[(lst_name, idx)] = (S, Nk, Nkp)
         self.rec.append(('sa', dict(mod=sa, name=name, x_in=x, out=out, out2=out2, H=H, C=Cc, tp=tp, gT=gT, ag=ag, N=N, Np=Np,
                                     inv_sigma=(a_tpg, a_o), P=P, Nk=Nk, Nkp=Nkp, kp=kp, gTp=gTp, lse=lse)))
@@ -444,9 +461,7 @@ class PlanOpsMixin:
         out = self._abuf(B, H, H, Cout)
         u_om = None
         if not self.bf16 and USE_WINOGRAD and ops.winograd_eligible(3, 1, 1, 1, Cin, 27 * dg, 1):
-            def build_u(out, key=f'dcn_list.{li}.om.w', cin=Cin):
-                return ops.winograd_weight(eng._packed[key], 1, cin, out)
-            u_om = eng._pack(f'dcn_list.{li}.om.U', build_u)
+            u_om, _ = self._weight_forms(f'dcn_list.{li}.om', 1, Cin, wino=True)
         p_om = None
         if self.f16_ok and USE_PATCH_X6 and lib.gssd_conv_patch_x6_weight_elems(27 * dg, Cin) > 0:
             # train-mode fp32 forward: the patch-staged direct conv on fp16 planes (csrc/conv_patch_x6.hip: 1024 -> 108 channels, 483 -> 398 us)
@@ -465,9 +480,8 @@ class PlanOpsMixin:
                   keep=w_main, tag=('dcn_bf16<128x256>' if self.bf16 else 'dcn_x6<128x256>' if DCN_X6 else 'dcn_fused<128x256>', 2.0 * M * Cout * 9 * Cin,
                                     esz * (M * (Cin + Cout) + Cout * 9 * Cin) + 4.0 * M * 27 * dg))
         if not self.bf16 and not DCN_X6:
-            # the stream-K form keeps a flag / slab region per output buffer: released with the plan (engine._Plan.__del__)
-            self.__dict__.setdefault('_sk_outs', []).append(out.data_ptr())
-        self.offsets = getattr(self, 'offsets', [])
+            # the stream-K form keeps a flag / slab region per output buffer: released with the plan (engine._PlanBase.__del__)
+            self._sk_outs.append(out.data_ptr())
         self.offsets.append((om, H, dg))
         self.rec.append(('dcn', dict(mod=m, x_in=x, out=out, H=H, Cin=Cin, Cout=Cout, om=om, d_om=d1, dg=dg, li=li, omc=OMC)))
         return out, Cout

@@ -91,12 +91,18 @@ int gssd_pack_conv_weights_batched(const gssd_pack_item* items_dev, int n_items,
  *   K13    DCN offset/mask conv (layers/dcn_v2_custom.py:80)   K14  DCN main contraction
  */
 #define GSSD_OUT_NHWC 0
-#define GSSD_OUT_TRANSPOSED 1 /* per image [n][m] with row stride out_stride (needs m_per_image) */
+#define GSSD_OUT_TRANSPOSED 1 /* per image [n][m] with row stride out_stride (needs m_per_image).  Pad columns: the generic kernels write
+                                 zeros into columns [Ho*Wo, min(out_stride, Ho*Wo rounded up to the launch's row tile -- 32 / 64 / 128 rows,
+                                 the first number of the instance name)) of every row and nothing behind them; ReLU applies, out_ch_off
+                                 does not */
 #define GSSD_OUT_HEADS 2      /* n < split_n -> out (loc), else -> out_b (conf), SSD prior order */
 #define GSSD_OUT_SPLIT_T 3    /* merged projections (Self_Attn theta|phi|g, one pass over x): n < split_n -> out, NHWC rows of
                                  out_stride floats; n >= split_n -> out_b, per image TRANSPOSED [n - split_n][m] with rows of
                                  out_b_stride floats (zero padded), images outb_batch_stride apart; one group, split_n a multiple
-                                 of 64; m_per_image, or (fp32 entry) all images in one M range when Ho*Wo % 4 == 0 */
+                                 of 64; m_per_image, or (fp32 entry) all images in one M range when Ho*Wo % 4 == 0.  The zero padding
+                                 is that of GSSD_OUT_TRANSPOSED and only exists with m_per_image: a flat launch of the generic kernel
+                                 writes columns [0, Ho*Wo) of a transposed row and leaves [Ho*Wo, out_b_stride) as the caller filled
+                                 them.  The first range honours out_ch_off, the second does not */
 
 typedef struct gssd_conv_desc {
     const float* in;    /* NHWC activations */
@@ -141,7 +147,9 @@ typedef struct gssd_conv_desc {
     int m_per_image;    /* 1: grid.z = image, tiles do not cross images, *_batch_stride apply */
     int split_n;        /* GSSD_OUT_HEADS: channels [0, split_n) are loc, the rest conf */
     int split_k;        /* >= 1; > 1 slices K over grid.z and accumulates with fp32 atomics into a zero-filled
-                           output (small-M / long-K launches such as the heads); plain epilogues only */
+                           output (small-M / long-K launches such as the heads); plain epilogues only.  The slices are
+                           ceil(chunks / split_k) K chunks long (32 floats / 64 bf16 each); slices past the last chunk are
+                           allowed and add 0.0, the bias enters in slice 0 */
     int out_b_stride;   /* GSSD_OUT_SPLIT_T: floats between the transposed rows of out_b */
     int flags;          /* GSSD_CONV_* bits (bf16 entry point only) */
     int stats_rep;      /* 0 / 1: `stats` is one [2*Cout] array.  R > 1: `stats` holds R replicas of [2*Cout] doubles, R * 2 * Cout in all

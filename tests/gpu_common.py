@@ -34,6 +34,17 @@ def ops():
     return _ops
 
 
+def assert_kernel(desc, want, bf16=False):
+    """The conv dispatcher lands ``desc`` on the kernel instance ``want`` (gssd_conv2d_kernel_name, the launch path's own statement) -- asserted
+    before a launch, so a case keeps testing the kernel its comment names.  ``want`` may be a pair (by default, with GSSD_THIN_X6=0):
+    tests/test_gpu_thin_x6.py re-runs some kernel tests with csrc/conv_thin_x6.hip switched off."""
+    from gssd.plan_common import conv_tag
+    if isinstance(want, tuple):
+        want = want[1 if os.environ.get('GSSD_THIN_X6') == '0' else 0]
+    got = conv_tag(desc, bf16)[0]
+    assert got == want, f'this case runs {got}, not {want}'
+
+
 def nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 

@@ -6,14 +6,19 @@ round-to-nearest-even bf16 rounding at every point where the HIP path STORES bf1
 fp32 accumulation), <= 1e-2 per tensor and <= 1e-3 on the loss; index work (matching, mining, NMS) stays bit-exact on identical
 inputs.  Op level: against torch-CPU fp32 arithmetic on the bf16-rounded operands, within one bf16 ulp of the output.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import gssd_oracle as O          # noqa: E402
 from gssd import synth                       # noqa: E402
+from gpu_common import assert_kernel         # noqa: E402
 
 BF_ULP = 2.0 ** -8          # spacing of bf16 just below a power of two, relative to the value
 BF_ULP_LOW = 2.0 ** -7      # ... just above a power of two: one ulp of the tensor's largest element can be this much of it
@@ -48,28 +53,32 @@ def nchw(x):
     return x.permute(0, 3, 1, 2).contiguous()
 
 
+# The last two elements of a case: the kernel instance of the launch with a bf16 output and of the launch with an fp32 output
+# (GSSD_CONV_OUT_F32: the thin and flat-window kernels only store bf16, so that launch is always the generic kernel's), asserted before the
+# launch.  The maps are small: B Ho Wo <= 4096 rows take the generic kernel's three-stage 64 x 64 tile (<= 512: 32 x 64) whatever cout_g
+# is; all six of its tiles are run by tests/test_gpu_conv_leaves.py.
 CASES = [
     # B, H, Cin, Cout, k, s, p, d, groups
-    (2, 37, 32, 64, 3, 1, 1, 1, 4),      # conv1_1-like: 8 ch / group (3 real + 5 pad), cout_g 16: single-tile lanes (8-byte stores)
-    (2, 30, 64, 64, 3, 1, 1, 1, 4),      # conv1_2
-    (2, 21, 128, 128, 3, 1, 1, 1, 4),    # cout_g = 32
-    (2, 19, 256, 256, 3, 1, 1, 1, 4),    # cout_g = 64
-    (2, 19, 512, 512, 3, 1, 1, 1, 4),    # cout_g = 128
-    (2, 19, 512, 1024, 3, 1, 6, 6, 4),   # conv6: dilation 6
-    (3, 19, 1024, 1024, 1, 1, 0, 1, 4),  # conv7: grouped 1x1
-    (2, 19, 256, 512, 3, 2, 1, 1, 4),    # extras stride 2
-    (5, 3, 128, 256, 3, 1, 0, 1, 4),     # 3 -> 1
-    (2, 10, 512, 512, 1, 1, 0, 1, 1),    # dense 1x1 fuse
-    (1, 83, 32, 64, 3, 1, 1, 1, 4),      # patch-staged thin kernels (maps >= 75 x 75, bf16 output): <8,16>, ragged 8 x 16 tiles
-    (1, 83, 64, 64, 3, 1, 1, 1, 4),      # <16,16>
-    (1, 80, 64, 128, 3, 1, 1, 1, 4),     # <16,32>
-    (1, 77, 128, 128, 3, 1, 1, 1, 4),    # <32,32>
-    (2, 77, 128, 256, 3, 1, 1, 1, 4),    # conv3_1 shape on a large map (generic kernel)
-    (2, 75, 256, 256, 3, 1, 1, 1, 4),    # conv3_2 / conv3_3: flat-window kernel <64, 64> (csrc/conv_flat_bf16.hip), last tile ragged
-    (3, 38, 256, 512, 3, 1, 1, 1, 4),    # conv4_1: flat <64, 128>
-    (2, 38, 512, 512, 3, 1, 1, 1, 4),    # conv4_2 / conv4_3: flat <128, 128>, two staged channel halves
-    (1, 12, 128, 256, 3, 1, 1, 1, 4),    # flat <32, 64> on a map of 144 pixels: one full tile + 16 pixels, windows mostly outside the image
-    (2, 13, 512, 1024, 3, 1, 3, 3, 4),   # flat, dilation 3, two 128-channel tiles per group
+    (2, 37, 32, 64, 3, 1, 1, 1, 4, 'conv_bf16<128x16>', 'conv_bf16<128x16>'),      # conv1_1-like: 8 ch / group (3 real + 5 pad), cout_g 16: single-tile lanes (8-byte stores)
+    (2, 30, 64, 64, 3, 1, 1, 1, 4, 'conv_bf16<128x16>', 'conv_bf16<128x16>'),      # conv1_2 on a map below the thin kernels' 75 x 75
+    (2, 21, 128, 128, 3, 1, 1, 1, 4, 'conv_bf16<128x32>', 'conv_bf16<128x32>'),    # cout_g = 32
+    (2, 19, 256, 256, 3, 1, 1, 1, 4, 'conv_flat_bf16<64,64,128>', 'conv_bf16<64x64>'),        # cout_g = 64: the flat-window kernel; fp32 output: generic
+    (2, 19, 512, 512, 3, 1, 1, 1, 4, 'conv_flat_bf16<128,128,128>', 'conv_bf16<64x64>'),      # cout_g = 128
+    (2, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_flat_bf16<128,128,128>', 'conv_bf16<64x64>'),     # conv6: dilation 6
+    (3, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_bf16<64x64>', 'conv_bf16<64x64>'),    # conv7: grouped 1x1
+    (2, 19, 256, 512, 3, 2, 1, 1, 4, 'conv_bf16<32x64>', 'conv_bf16<32x64>'),      # extras stride 2
+    (5, 3, 128, 256, 3, 1, 0, 1, 4, 'conv_bf16<32x64>', 'conv_bf16<32x64>'),       # 3 -> 1
+    (2, 10, 512, 512, 1, 1, 0, 1, 1, 'conv_bf16<32x64>', 'conv_bf16<32x64>'),      # dense 1x1 fuse
+    (1, 83, 32, 64, 3, 1, 1, 1, 4, 'conv_thin_bf16<8,16>', 'conv_bf16<128x16>'),   # patch-staged thin kernels (maps >= 75 x 75, bf16 output): <8,16>, ragged 8 x 16 tiles
+    (1, 83, 64, 64, 3, 1, 1, 1, 4, 'conv_thin_bf16<16,16>', 'conv_bf16<128x16>'),  # <16,16>
+    (1, 80, 64, 128, 3, 1, 1, 1, 4, 'conv_thin_bf16<16,32>', 'conv_bf16<128x32>'),    # <16,32>
+    (1, 77, 128, 128, 3, 1, 1, 1, 4, 'conv_thin_bf16<32,32>', 'conv_bf16<128x32>'),   # <32,32>
+    (2, 77, 128, 256, 3, 1, 1, 1, 4, 'conv_flat_bf16<32,64,128>', 'conv_bf16<128x64>'),     # conv3_1 shape on a large map: flat <32, 64>; fp32 output: the generic kernel's 128-row tile
+    (2, 75, 256, 256, 3, 1, 1, 1, 4, 'conv_flat_bf16<64,64,128>', 'conv_bf16<128x64>'),     # conv3_2 / conv3_3: flat-window kernel <64, 64> (csrc/conv_flat_bf16.hip), last tile ragged
+    (3, 38, 256, 512, 3, 1, 1, 1, 4, 'conv_flat_bf16<64,128,128>', 'conv_bf16<128x64>'),    # conv4_1: flat <64, 128>
+    (2, 38, 512, 512, 3, 1, 1, 1, 4, 'conv_flat_bf16<128,128,128>', 'conv_bf16<64x64>'),    # conv4_2 / conv4_3: flat <128, 128>, two staged channel halves
+    (1, 12, 128, 256, 3, 1, 1, 1, 4, 'conv_flat_bf16<32,64,128>', 'conv_bf16<32x64>'),      # flat <32, 64> on a map of 144 pixels: one full tile + 16 pixels, windows mostly outside the image
+    (2, 13, 512, 1024, 3, 1, 3, 3, 4, 'conv_flat_bf16<128,128,128>', 'conv_bf16<32x64>'),   # flat, dilation 3, two 128-channel tiles per group
 ]
 
 
@@ -77,8 +86,8 @@ CASES = [
 def test_conv_bf16(dev, case):
     from gssd import ops, _lib
     import ctypes as C
-    B, H, Cin, Cout, k, s, p, d, g = case
-    rng = np.random.default_rng(hash(case) % (2 ** 31))
+    B, H, Cin, Cout, k, s, p, d, g, want_bf16, want_f32 = case
+    rng = np.random.default_rng(hash(case[:9]) % (2 ** 31))
     x = q(torch.from_numpy(rng.normal(size=(B, Cin, H, H)).astype(np.float32)))
     w = q(torch.from_numpy(rng.normal(0, 0.1, size=(Cout, Cin // g, k, k)).astype(np.float32)))
     b = torch.from_numpy(rng.normal(size=(Cout,)).astype(np.float32))
@@ -92,6 +101,7 @@ def test_conv_bf16(dev, case):
         stats.zero_()
         dsc, _, _ = ops.make_conv_desc(xd, wp, out, B=B, H=H, W=H, in_stride=Cin, cin_g=Cin // g, Cout=Cout, groups=g, k=k, stride=s,
                                        pad=p, dil=d, bias=b.to(dev), stats=stats, flags=_lib.CONV_OUT_F32 if f32 else 0)
+        assert_kernel(dsc, want_f32 if f32 else want_bf16, bf16=True)
         _lib.check(_lib.lib.gssd_conv2d_nhwc_bf16(C.byref(dsc), torch.cuda.current_stream().cuda_stream))
         y = nchw(out.float())
         # fp32 accumulation of exact bf16 products; the bf16 output is that rounded once
@@ -103,6 +113,15 @@ def test_conv_bf16(dev, case):
         n = ref.numel() / Cout
         assert rel(stats[:Cout] / n, ref.double().mean(dim=(0, 2, 3))) < 1e-5
         assert rel(stats[Cout:] / n, (ref.double() ** 2).mean(dim=(0, 2, 3))) < 1e-5
+
+
+# (Cin, Cout, forced pixel tile) -> kernel instance <cin_g, output-channel tile, pixels>, with or without the fused input transform
+FLAT_KERNELS = {
+    (256, 256, 128): 'conv_flat_bf16<64,64,128>', (256, 256, 256): 'conv_flat_bf16<64,64,256>',
+    (512, 512, 128): 'conv_flat_bf16<128,128,128>', (512, 512, 256): 'conv_flat_bf16<128,128,256>',
+    (128, 256, 128): 'conv_flat_bf16<32,64,128>', (128, 256, 256): 'conv_flat_bf16<32,64,256>',
+    (512, 1024, 128): 'conv_flat_bf16<128,128,128>', (512, 1024, 256): 'conv_flat_bf16<128,128,256>',
+}
 
 
 @pytest.mark.parametrize('Cin,Cout,H,W', [(256, 256, 21, 37), (512, 512, 9, 40), (128, 256, 33, 14), (512, 1024, 17, 23)])
@@ -136,6 +155,7 @@ def test_conv_flat_bf16(dev, Cin, Cout, H, W, xf, bm):
     try:
         took = _lib.lib.gssd_conv_flat_bf16_takes(C.byref(d))
         assert took == bm                                     # the flat kernel, in the forced form
+        assert_kernel(d, FLAT_KERNELS[(Cin, Cout, bm)], bf16=True)
         _lib.check(_lib.lib.gssd_conv2d_nhwc_bf16(C.byref(d), torch.cuda.current_stream().cuda_stream))
     finally:
         _lib.lib.gssd_conv_flat_bf16_tile(prev)
@@ -200,8 +220,13 @@ def test_conv_thin_bf16_pooled_epilogue(dev, Cin, Cout, H, xf):
     assert torch.equal(f(want), torch.nn.functional.max_pool2d(f(nchw(full.float().cpu())), 2, 2, 0, ceil_mode=True))
 
 
-@pytest.mark.parametrize('Cin,Cout,H,k,st,pd', [(64, 64, 40, 3, 1, 1), (128, 128, 40, 3, 1, 1), (512, 512, 19, 3, 1, 1),
-                                               (1024, 1024, 19, 1, 1, 0), (256, 512, 19, 3, 2, 1), (256, 256, 77, 3, 1, 1)])
+FUSED_INPUT_KERNELS = {          # case -> kernel instance (fp32 output: always the generic kernel)
+    (64, 64, 40, 3, 1, 1): 'conv_bf16<128x16>', (128, 128, 40, 3, 1, 1): 'conv_bf16<128x32>', (512, 512, 19, 3, 1, 1): 'conv_bf16<64x64>',
+    (1024, 1024, 19, 1, 1, 0): 'conv_bf16<64x64>', (256, 512, 19, 3, 2, 1): 'conv_bf16<32x64>', (256, 256, 77, 3, 1, 1): 'conv_bf16<128x64>',
+}
+
+
+@pytest.mark.parametrize('Cin,Cout,H,k,st,pd', list(FUSED_INPUT_KERNELS))
 def test_conv_bf16_fused_input_bn_relu(dev, Cin, Cout, H, k, st, pd):
     """Consumer-side BatchNorm + ReLU on bf16 raw input: conv2d(q(relu(q(x) * scale + shift))) with zero padding after the transform."""
     from gssd import ops, _lib
@@ -230,6 +255,7 @@ def test_conv_bf16_fused_input_bn_relu(dev, Cin, Cout, H, k, st, pd):
     d, _, _ = ops.make_conv_desc(nhwc(x).to(dev).to(torch.bfloat16), wp, out, B=B, H=H, W=H, in_stride=Cin, cin_g=Cin // g, Cout=Cout,
                                  groups=g, k=k, stride=st, pad=pd, bias=b.to(dev), in_scale=sc, in_shift=sh, in_pad=pdv,
                                  flags=_lib.CONV_OUT_F32)
+    assert_kernel(d, FUSED_INPUT_KERNELS[(Cin, Cout, H, k, st, pd)], bf16=True)
     _lib.check(_lib.lib.gssd_conv2d_nhwc_bf16(C.byref(d), st_))
     # a bf16 rounding flip of an activation (fp32 fma vs mul + add) moves single outputs by ~1e-3 of the tensor's scale
     assert rel(nchw(out), ref) < 2e-3 and l2rel(nchw(out), ref) < 2e-4

@@ -20,37 +20,45 @@ from gpu_common import O, synth, ROOT, _stage_errors     # noqa: E402,F401
 pytestmark = pytest.mark.gpu
 
 
+# The last element of a case is the kernel instance the dispatcher lands it on (gssd_conv2d_kernel_name, asserted before the launch); a pair
+# is (by default, with GSSD_THIN_X6=0 -- the mode tests/test_gpu_thin_x6.py re-runs some of these tests in).  The maps here are small:
+# B Ho Wo <= 4096 rows take the three-stage 64 x 64 tile (<= 512: 32 x 64) whatever cout_g is; the 128-row tiles of the generic kernel are
+# run by tests/test_gpu_conv_leaves.py.
 CONV_CASES = [
     # B, H, Cin, Cout, k, s, p, d, groups
-    (2, 37, 16, 64, 3, 1, 1, 1, 4),      # conv1_1-like: 4 ch / group (3 real + 1 pad)
-    (2, 30, 64, 64, 3, 1, 1, 1, 4),      # cout_g = 16 tile
-    (2, 21, 128, 128, 3, 1, 1, 1, 4),    # cout_g = 32
-    (2, 19, 256, 256, 3, 1, 1, 1, 4),    # cout_g = 64
-    (2, 19, 512, 512, 3, 1, 1, 1, 4),    # cout_g = 128
-    (2, 19, 512, 1024, 3, 1, 6, 6, 4),   # conv6: dilation 6
-    (3, 19, 1024, 1024, 1, 1, 0, 1, 4),  # conv7: grouped 1x1
-    (2, 19, 256, 512, 3, 2, 1, 1, 4),    # extras stride 2
-    (2, 5, 128, 256, 3, 1, 0, 1, 4),     # extras valid 3x3 (5 -> 3)
-    (5, 3, 128, 256, 3, 1, 0, 1, 4),     # 3 -> 1
-    (2, 10, 512, 512, 1, 1, 0, 1, 1),    # dense 1x1 fuse
-    (2, 38, 512, 108, 3, 1, 1, 1, 1),    # DCN offset conv shape (Cout not a tile multiple)
-    (2, 83, 16, 64, 3, 1, 1, 1, 4),      # thin patch-staged kernel <4,16>, ragged 8x16 tiles
-    (2, 80, 64, 64, 3, 1, 1, 1, 4),      # thin <16,16>
-    (3, 75, 64, 128, 3, 1, 1, 1, 4),     # thin <16,32>, exact 5x25 tiles
-    (1, 150, 64, 128, 3, 1, 1, 1, 4),
+    (2, 37, 16, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # conv1_1-like: 4 ch / group (3 real + 1 pad); a map below the thin kernel's 75 x 75
+    (2, 30, 64, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # cout_g = 16 tile
+    (2, 21, 128, 128, 3, 1, 1, 1, 4, 'conv_igemm<128x32>'),    # cout_g = 32
+    (2, 19, 256, 256, 3, 1, 1, 1, 4, 'conv_igemm<64x64>'),     # cout_g = 64, M = 722
+    (2, 19, 512, 512, 3, 1, 1, 1, 4, 'conv_igemm<64x64>'),     # cout_g = 128: two column tiles of the 64 x 64 tile
+    (2, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_igemm<64x64>'),    # conv6: dilation 6
+    (3, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_igemm<64x64>'),   # conv7: grouped 1x1, M = 1083
+    (2, 19, 256, 512, 3, 2, 1, 1, 4, 'conv_igemm<32x64>'),     # extras stride 2 (19 -> 10: M = 200)
+    (2, 5, 128, 256, 3, 1, 0, 1, 4, 'conv_igemm<32x64>'),      # extras valid 3x3 (5 -> 3)
+    (5, 3, 128, 256, 3, 1, 0, 1, 4, 'conv_igemm<32x64>'),      # 3 -> 1
+    (2, 10, 512, 512, 1, 1, 0, 1, 1, 'conv_igemm<32x64>'),     # dense 1x1 fuse
+    (2, 38, 512, 108, 3, 1, 1, 1, 1, 'conv_igemm<64x64>'),     # DCN offset conv shape (Cout not a tile multiple), M = 2888
+    (2, 83, 16, 64, 3, 1, 1, 1, 4, 'conv_thin<4,16>'),         # thin patch-staged kernel <4,16>, ragged 8x16 tiles
+    (2, 80, 64, 64, 3, 1, 1, 1, 4, ('conv_thin_x6<16,16>/plain', 'conv_thin<16,16>')),      # the thin kernels: three-plane form, patch-staged fp32 form
+    (3, 75, 64, 128, 3, 1, 1, 1, 4, ('conv_thin_x6<16,32>/plain', 'conv_thin<16,32>')),     # exact 5x25 tiles
+    (1, 150, 64, 128, 3, 1, 1, 1, 4, ('conv_thin_x6<16,32>/plain', 'conv_thin<16,32>')),
 ]
 
 
 @pytest.mark.parametrize('case', CONV_CASES)
 def test_conv_igemm(dev, ops, case):
-    B, H, Cin, Cout, k, s, p, d, g = case
-    rng = np.random.default_rng(hash(case) % (2 ** 31))
+    B, H, Cin, Cout, k, s, p, d, g, want = case
+    rng = np.random.default_rng(hash(case[:9]) % (2 ** 31))
     x = torch.from_numpy(rng.normal(size=(B, Cin, H, H)).astype(np.float32))
     w = torch.from_numpy(rng.normal(0, 0.1, size=(Cout, Cin // g, k, k)).astype(np.float32))
     b = torch.from_numpy(rng.normal(size=(Cout,)).astype(np.float32))
     ref = torch.nn.functional.conv2d(x, w, b, s, p, d, g)
     stats = torch.zeros(2 * Cout, dtype=torch.float64, device=dev)
-    y = ops.conv2d_nhwc(nhwc(x).to(dev), w.to(dev), b.to(dev), s, p, d, g, stats=stats)
+    keep = []
+    desc = ops.conv2d_nhwc(nhwc(x).to(dev), w.to(dev), b.to(dev), s, p, d, g, stats=stats, _keep=keep)
+    assert_kernel(desc, want)
+    ops.run_conv(desc)
+    y = keep[-1]
     assert rel(nchw(y), ref) < TOL
     # fused batch statistics (what BatchNorm consumes)
     n = ref.numel() / Cout
@@ -58,9 +66,14 @@ def test_conv_igemm(dev, ops, case):
     assert rel(stats[Cout:] / n, (ref.double() ** 2).mean(dim=(0, 2, 3))) < 1e-5
 
 
-@pytest.mark.parametrize('Cin,Cout,H,k,st,pd', [(64, 64, 80, 3, 1, 1), (64, 128, 75, 3, 1, 1), (16, 64, 77, 3, 1, 1),
-                                               (128, 128, 40, 3, 1, 1), (512, 512, 19, 3, 1, 1), (1024, 1024, 19, 1, 1, 0),
-                                               (256, 512, 19, 3, 2, 1), (64, 256, 21, 3, 1, 1)])
+FUSED_INPUT_KERNELS = {          # case -> kernel instance (a pair: by default, with GSSD_THIN_X6=0)
+    (64, 64, 80, 3, 1, 1): ('conv_thin_x6<16,16>', 'conv_thin<16,16>'), (64, 128, 75, 3, 1, 1): ('conv_thin_x6<16,32>', 'conv_thin<16,32>'),
+    (16, 64, 77, 3, 1, 1): 'conv_thin<4,16>', (128, 128, 40, 3, 1, 1): 'conv_igemm<128x32>', (512, 512, 19, 3, 1, 1): 'conv_igemm<64x64>',
+    (1024, 1024, 19, 1, 1, 0): 'conv_igemm<64x64>', (256, 512, 19, 3, 2, 1): 'conv_igemm<32x64>', (64, 256, 21, 3, 1, 1): 'conv_igemm<64x64>',
+}
+
+
+@pytest.mark.parametrize('Cin,Cout,H,k,st,pd', list(FUSED_INPUT_KERNELS))
 def test_conv_fused_input_bn_relu(dev, ops, Cin, Cout, H, k, st, pd):
     """A consumer conv applying its producer's BatchNorm + ReLU on the fly (conv1_1 -> conv1_2 in the engine): equals
     conv2d(relu(bn(x))) with zero padding applied AFTER the transform."""
@@ -83,6 +96,7 @@ def test_conv_fused_input_bn_relu(dev, ops, Cin, Cout, H, k, st, pd):
     out = torch.empty(B, Ho, Ho, Cout, device=dev)
     d, _, _ = ops.make_conv_desc(nhwc(x).to(dev), wp, out, B=B, H=H, W=H, in_stride=Cin, cin_g=Cin // g, Cout=Cout, groups=g,
                                  k=k, stride=st, pad=pd, bias=b.to(dev), in_scale=sc, in_shift=sh, in_pad=pdv)
+    assert_kernel(d, FUSED_INPUT_KERNELS[(Cin, Cout, H, k, st, pd)])
     ops.run_conv(d)
     assert rel(nchw(out), ref) < TOL
     rm_ref, rv_ref = rm.clone(), rv.clone()
@@ -115,18 +129,26 @@ def test_conv_wgrad_fused_input(dev, ops, B, H, Cin, Cout, k, pd, dl):
     assert rel(dw, w.grad) < TOL
 
 
+# The last element of a case: the kernel instances of its four launches -- with Winograd weights + batch sums, without Winograd weights, with
+# Winograd weights + the fused input transform, the data gradient (None: not a Winograd shape) -- as the dispatcher names them; a pair is
+# (by default, with GSSD_THIN_X6=0).  By default the conv1_2 / conv2_2 classes on maps of 75 x 75 and more belong to csrc/conv_thin_x6.hip
+# with or without Winograd weights; tests/test_gpu_thin_x6.py re-runs this test with that kernel switched off.
+_W64, _W32 = ('conv_wino<64>/plain', 'conv_igemm<64x64>', 'conv_wino<64>'), ('conv_wino<32>/plain', 'conv_igemm<128x32>', 'conv_wino<32>')
+_T16 = (('conv_thin_x6<16,16>/plain', 'conv_thin_wino<16,16>'), ('conv_thin_x6<16,16>/plain', 'conv_thin<16,16>'),
+        ('conv_thin_x6<16,16>', 'conv_thin_wino<16,16>'), 'conv_igemm<128x16>')      # (the data gradient adds into a residual: not a thin kernel's epilogue)
 WINO_CASES = [
     # B, H, Cin, Cout, groups          (3x3 / stride 1 / pad 1)
-    (2, 38, 512, 512, 4),      # conv4_2: cout_g 128 -> two 64-channel blocks, 8 chunks, even map
-    (3, 19, 512, 512, 4),      # conv5_x: odd map (ragged last tile row / column), tile list crosses images
-    (2, 75, 128, 256, 4),      # conv3_1: cin_g 32 -> 2 chunks, odd map
-    (2, 37, 128, 128, 4),      # conv2_2 shape class: cout_g 32 -> persistent 32-channel variant, several items per workgroup
-    (5, 9, 64, 32, 1),         # dense, one group, one chunk; fewer tiles than one wave in places
-    (1, 150, 128, 128, 4),     # many items per persistent workgroup
-    (2, 38, 256, 108, 1),      # DCN offset / mask conv: 108 output channels padded to 128 inside U
-    (2, 13, 64, 24, 1),        # padded to one 32-channel block
-    (2, 83, 64, 64, 4),        # conv1_2 class: patch-staged Winograd (conv_thin_wino.hip), ragged 8 x 16 tiles
-    (1, 160, 64, 64, 4),       # ... several tiles per persistent workgroup
+    (2, 38, 512, 512, 4, _W64 + ('conv_wino<64>/plain',)),      # conv4_2: cout_g 128 -> two 64-channel blocks, 8 chunks, even map
+    (3, 19, 512, 512, 4, _W64 + ('conv_wino<64>/plain',)),      # conv5_x: odd map (ragged last tile row / column), tile list crosses images
+    (2, 75, 128, 256, 4, ('conv_wino<64>/plain', 'conv_igemm<128x64>', 'conv_wino<64>', 'conv_wino<32>/plain')),   # conv3_1: cin_g 32 -> 2 chunks, odd map
+    (2, 37, 128, 128, 4, _W32 + ('conv_wino<32>/plain',)),      # conv2_2 shape class on a small map: cout_g 32 -> persistent 32-channel variant, several items per workgroup
+    (5, 9, 64, 32, 1, _W32 + ('conv_wino<64>/plain',)),         # dense, one group, one chunk; fewer tiles than one wave in places
+    (1, 150, 128, 128, 4, (('conv_thin_x6<32,32>/plain', 'conv_wino<32>/plain'), ('conv_thin_x6<32,32>/plain', 'conv_igemm<128x32>'),
+                           ('conv_thin_x6<32,32>', 'conv_wino<32>'), 'conv_wino<32>/plain')),      # conv2_2 at its own size; GSSD_THIN_X6=0: many items per persistent workgroup
+    (2, 38, 256, 108, 1, _W64 + (None,)),      # DCN offset / mask conv: 108 output channels padded to 128 inside U
+    (2, 13, 64, 24, 1, _W32 + (None,)),        # padded to one 32-channel block
+    (2, 83, 64, 64, 4, _T16),        # conv1_2 class, ragged 8 x 16 tiles; GSSD_THIN_X6=0: patch-staged Winograd (conv_thin_wino.hip)
+    (1, 160, 64, 64, 4, _T16),       # ... several tiles per persistent workgroup
 ]
 
 
@@ -134,22 +156,29 @@ WINO_CASES = [
 def test_conv_winograd(dev, ops, case):
     """Winograd F(2x2,3x3) kernel (csrc/conv_wino.hip) against CPU conv2d: plain, with fused batch statistics, with the
     producer's BatchNorm + ReLU applied on the fly, and as a data gradient accumulating into an existing gradient."""
-    B, H, Cin, Cout, g = case
-    rng = np.random.default_rng(hash(case) % (2 ** 31))
+    B, H, Cin, Cout, g, want = case
+    rng = np.random.default_rng(hash(case[:5]) % (2 ** 31))
     x = torch.from_numpy(rng.normal(0.1, 1.0, size=(B, Cin, H, H)).astype(np.float32))
     w = torch.from_numpy(rng.normal(0, 0.1, size=(Cout, Cin // g, 3, 3)).astype(np.float32))
     b = torch.from_numpy(rng.normal(size=(Cout,)).astype(np.float32))
     assert ops.winograd_eligible(3, 1, 1, 1, Cin // g, Cout // g, g)
+
+    def conv(name, *a, **kw):          # ops.conv2d_nhwc, after asserting which kernel instance the launch is
+        keep = []
+        desc = ops.conv2d_nhwc(*a, _keep=keep, **kw)
+        assert_kernel(desc, name)
+        ops.run_conv(desc)
+        return keep[-1]
     ref = torch.nn.functional.conv2d(x, w, b, 1, 1, 1, g)
     stats = torch.zeros(2 * Cout, dtype=torch.float64, device=dev)
     xd = nhwc(x).to(dev)
-    y = ops.conv2d_nhwc(xd, w.to(dev), b.to(dev), 1, 1, 1, g, stats=stats, winograd=True)
+    y = conv(want[0], xd, w.to(dev), b.to(dev), 1, 1, 1, g, stats=stats, winograd=True)
     assert rel(nchw(y), ref) < 2e-5
     n = ref.numel() / Cout
     assert rel(stats[:Cout] / n, ref.double().mean(dim=(0, 2, 3))) < 1e-5
     assert rel(stats[Cout:] / n, (ref.double() ** 2).mean(dim=(0, 2, 3))) < 1e-5
-    # the direct implicit GEMM on the same descriptor agrees to fp32 rounding
-    y2 = ops.conv2d_nhwc(xd, w.to(dev), b.to(dev), 1, 1, 1, g)
+    # the launch without Winograd weights (the direct implicit GEMM, or a thin kernel) agrees to fp32 rounding
+    y2 = conv(want[1], xd, w.to(dev), b.to(dev), 1, 1, 1, g)
     assert rel(y, y2) < 2e-5
     # fused producer BatchNorm + ReLU, zero padding AFTER the transform
     gm = torch.from_numpy(rng.uniform(-1.5, 1.5, size=Cin).astype(np.float32))
@@ -160,9 +189,9 @@ def test_conv_winograd(dev, ops, case):
     sc, sh, pdv = (torch.empty(Cin, device=dev) for _ in range(3))
     ops.bn_finalize(st_in, B * H * H, gm.to(dev), bt.to(dev), torch.zeros(Cin, device=dev), torch.ones(Cin, device=dev), True, sc,
                     sh, pdv)
-    yx = ops.conv2d_nhwc(xd, w.to(dev), b.to(dev), 1, 1, 1, g, winograd=True, in_scale=sc, in_shift=sh, in_pad=pdv)
+    yx = conv(want[2], xd, w.to(dev), b.to(dev), 1, 1, 1, g, winograd=True, in_scale=sc, in_shift=sh, in_pad=pdv)
     assert rel(nchw(yx), refx) < 2e-5
-    # data gradient through the same kernel: dX = existing + conv(dY, flipped weights)
+    # data gradient as a forward launch with Winograd weights: dX = existing + conv(dY, flipped weights)
     xg = x.clone().requires_grad_()
     yg = torch.nn.functional.conv2d(xg, w, None, 1, 1, 1, g)
     dy = torch.from_numpy(rng.normal(size=tuple(yg.shape)).astype(np.float32))
@@ -174,39 +203,44 @@ def test_conv_winograd(dev, ops, case):
         dx = torch.empty(B, H, H, Cin, device=dev)
         dd, _, _ = ops.make_conv_desc(nhwc(dy).to(dev), wd, dx, B=B, H=H, W=H, in_stride=Cout, cin_g=Cout // g, Cout=Cin, groups=g,
                                       k=3, pad=1, resid=existing, wgt_wino=ud)
+        assert_kernel(dd, want[3])
         ops.run_conv(dd)
         assert rel(nchw(dx - existing), xg.grad) < 2e-5
+    else:
+        assert want[3] is None
 
 
+# The comments describe the weight-gradient kernel of a case; its last element is the kernel instance of the data gradient's forward launch
+# (None: stride 2, no data gradient here; a pair: by default, with GSSD_THIN_X6=0).
 BWD_CASES = [
     # B, H, Cin, Cout, k, s, p, d, groups
-    (2, 30, 64, 64, 3, 1, 1, 1, 4),      # cout_g 16 (scalar dY path)
-    (2, 21, 64, 128, 3, 1, 1, 1, 4),     # cout_g 32
-    (2, 19, 128, 256, 3, 1, 1, 1, 4),    # cout_g 64 (b128 path, 64 x 256 tile)
-    (2, 19, 512, 512, 3, 1, 1, 1, 4),    # cout_g 128
-    (2, 19, 512, 1024, 3, 1, 6, 6, 4),   # dilation 6
-    (2, 19, 1024, 1024, 1, 1, 0, 1, 4),  # grouped 1x1
-    (2, 19, 256, 512, 3, 2, 1, 1, 4),    # stride 2 (wgrad only)
-    (2, 10, 512, 512, 1, 1, 0, 1, 1),    # dense 1x1
-    (2, 10, 512, 36, 3, 1, 1, 1, 1),     # head
-    (3, 33, 16, 64, 3, 1, 1, 1, 4),      # conv1_1: 4 (3 real) input channels per group
-    (2, 83, 16, 64, 3, 1, 1, 1, 4),      # thin patch-staged wgrad <4>, ragged tiles
-    (2, 80, 64, 64, 3, 1, 1, 1, 4),      # thin wgrad <16>
-    (8, 38, 512, 512, 1, 1, 0, 1, 1),    # large dense 1x1: slot-scheduled TN wgrad (csrc/wgrad_slot.hip) + NT dgrad (gemm_slot.hip)
-    (5, 37, 480, 120, 1, 1, 0, 1, 1),    # ... ragged: 6845 pixels (reduction tail), 120 of 128 rows, 480 of 512 columns
-    (4, 38, 512, 512, 3, 1, 1, 1, 4),    # conv4_x: slot-scheduled TN wgrad with taps and groups (one tap per 128 columns)
-    (12, 19, 512, 1024, 3, 1, 6, 6, 4),  # conv6: dilation 6, cout_g 256 (two row tiles per group)
-    (16, 38, 512, 512, 3, 2, 1, 1, 4),   # stride 2 (wgrad only)
-    (4, 38, 512, 108, 3, 1, 1, 1, 1),    # DCN offset conv: 108 of 128 rows, K = 4608
-    (12, 19, 1024, 1024, 1, 1, 0, 1, 4), # conv7: grouped 1x1
+    (2, 30, 64, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # cout_g 16 (scalar dY path)
+    (2, 21, 64, 128, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),     # cout_g 32
+    (2, 19, 128, 256, 3, 1, 1, 1, 4, 'conv_igemm<128x32>'),    # cout_g 64 (b128 path, 64 x 256 tile)
+    (2, 19, 512, 512, 3, 1, 1, 1, 4, 'conv_igemm<64x64>'),     # cout_g 128
+    (2, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_igemm<64x64>'),    # dilation 6
+    (2, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_igemm<64x64>'),   # grouped 1x1
+    (2, 19, 256, 512, 3, 2, 1, 1, 4, None),                    # stride 2 (wgrad only)
+    (2, 10, 512, 512, 1, 1, 0, 1, 1, 'conv_igemm<32x64>'),     # dense 1x1
+    (2, 10, 512, 36, 3, 1, 1, 1, 1, 'conv_igemm<32x64>'),      # head
+    (3, 33, 16, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # conv1_1: 4 (3 real) input channels per group
+    (2, 83, 16, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # thin patch-staged wgrad <4>, ragged tiles
+    (2, 80, 64, 64, 3, 1, 1, 1, 4, ('conv_thin_x6<16,16>/plain', 'conv_thin<16,16>')),      # thin wgrad <16>
+    (8, 38, 512, 512, 1, 1, 0, 1, 1, 'gemm_slot<128x128>'),    # large dense 1x1: slot-scheduled TN wgrad (csrc/wgrad_slot.hip) + NT dgrad (gemm_slot.hip)
+    (5, 37, 480, 120, 1, 1, 0, 1, 1, 'conv_igemm<128x64>'),    # ... ragged: 6845 pixels (reduction tail), 120 of 128 rows, 480 of 512 columns; its dgrad (480 outputs: 3.75 column tiles) stays generic
+    (4, 38, 512, 512, 3, 1, 1, 1, 4, 'conv_igemm<128x64>'),    # conv4_x: slot-scheduled TN wgrad with taps and groups (one tap per 128 columns)
+    (12, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_igemm<128x64>'),  # conv6: dilation 6, cout_g 256 (two row tiles per group)
+    (16, 38, 512, 512, 3, 2, 1, 1, 4, None),                   # stride 2 (wgrad only)
+    (4, 38, 512, 108, 3, 1, 1, 1, 1, 'conv_igemm<128x64>'),    # DCN offset conv: 108 of 128 rows, K = 4608
+    (12, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_igemm<128x64>'), # conv7: grouped 1x1
 ]
 
 
 @pytest.mark.parametrize('case', BWD_CASES)
 def test_conv_backward(dev, ops, case):
     """wgrad kernel and dgrad-as-forward-conv against CPU autograd."""
-    B, H, Cin, Cout, k, s, p, d, g = case
-    rng = np.random.default_rng(hash(case) % (2 ** 31))
+    B, H, Cin, Cout, k, s, p, d, g, want = case
+    rng = np.random.default_rng(hash(case[:9]) % (2 ** 31))
     x = torch.from_numpy(rng.normal(size=(B, Cin, H, H)).astype(np.float32)).requires_grad_()
     w = torch.from_numpy(rng.normal(0, 0.1, size=(Cout, Cin // g, k, k)).astype(np.float32)).requires_grad_()
     y = torch.nn.functional.conv2d(x, w, None, s, p, d, g)
@@ -224,8 +258,11 @@ def test_conv_backward(dev, ops, case):
         pd = d * (k - 1) - p
         dd, _, _ = ops.make_conv_desc(dyd, wd, dx, B=B, H=Ho, W=Ho, in_stride=Cout, cin_g=Cout // g, Cout=Cin, groups=g, k=k,
                                       pad=pd, dil=d)
+        assert_kernel(dd, want)
         ops.run_conv(dd)
         assert rel(nchw(dx), x.grad) < TOL
+    else:
+        assert want is None
 
 
 @pytest.mark.parametrize('H,pool', [(30, None), (30, (2, 2, 0, False)), (75, (2, 2, 0, True)), (19, (3, 1, 1, False))])
@@ -569,11 +606,23 @@ def test_dcn_fused_vs_scalar_restatement(dev, ops, B, Cc, H, dg, Cout, std):
     assert np.abs(a - bq)[sel].max() / np.abs(a).max() < TOL
 
 
+# (Cin, Cout, xf) -> the kernel instances of the pooled and of the plain launch; a pair is (by default, with GSSD_THIN_X6=0)
+POOLED_KERNELS = {
+    (64, 64, False): (('conv_thin_x6<16,16>/plain/pool2', 'conv_thin_wino<16,16>'), ('conv_thin_x6<16,16>/plain', 'conv_thin_wino<16,16>')),
+    (64, 64, True): (('conv_thin_x6<16,16>/pool2', 'conv_thin_wino<16,16>'), ('conv_thin_x6<16,16>', 'conv_thin_wino<16,16>')),
+    (128, 128, False): (('conv_thin_x6<32,32>/plain/pool2', 'conv_wino<32>/plain/pool2'), ('conv_thin_x6<32,32>/plain', 'conv_wino<32>/plain')),
+    (128, 128, True): (('conv_thin_x6<32,32>/pool2', 'conv_wino<32>/pool2'), ('conv_thin_x6<32,32>', 'conv_wino<32>')),
+    (256, 256, False): ('conv_wino<64>/plain/pool2', 'conv_wino<64>/plain'),
+    (256, 256, True): ('conv_wino<64>/pool2', 'conv_wino<64>'),
+}
+
+
 @pytest.mark.parametrize('Cin,Cout,H,W', [(64, 64, 84, 84), (128, 128, 78, 78), (256, 256, 75, 75), (256, 256, 21, 37)])
 @pytest.mark.parametrize('xf', [False, True])
 def test_conv_winograd_pooled_epilogue(dev, ops, Cin, Cout, H, W, xf):
-    """GSSD_CONV_POOL2 on the fp32 Winograd trunk kernels (conv1_2: conv_thin_wino, conv2_2: conv_wino<32>, conv3_3: conv_wino<64> with
-    its ceil-mode 75 -> 38 pool; a non-square map): the launch stores max- / min-pooled raw outputs by the sign of the BatchNorm weight
+    """GSSD_CONV_POOL2 on the fp32 trunk kernels that have the pooled epilogue (conv1_2, conv2_2: conv_thin_x6 -- with GSSD_THIN_X6=0
+    conv_thin_wino and conv_wino<32>; conv3_3: conv_wino<64> with its ceil-mode 75 -> 38 pool; a non-square map), every launch with Winograd
+    weights: the launch stores max- / min-pooled raw outputs by the sign of the BatchNorm weight
     with the batch sums of the full map -- exactly the pooled image of what the plain launch stores -- and the deferred BatchNorm +
     ReLU of that map equals BatchNorm + ReLU + max-pool of the full map bit for bit."""
     import ctypes as C
@@ -606,6 +655,8 @@ def test_conv_winograd_pooled_epilogue(dev, ops, Cin, Cout, H, W, xf):
     d, _, _ = ops.make_conv_desc(nhwc(x).to(dev), wp, out, stats=stats, flags=_lib.CONV_POOL2, pool_sign=gd_, **kw)
     d0, _, _ = ops.make_conv_desc(nhwc(x).to(dev), wp, full, stats=stats_full, **kw)
     st_ = torch.cuda.current_stream().cuda_stream
+    assert_kernel(d, POOLED_KERNELS[(Cin, Cout, xf)][0])
+    assert_kernel(d0, POOLED_KERNELS[(Cin, Cout, xf)][1])
     _lib.check(_lib.lib.gssd_conv2d_nhwc_f32(C.byref(d), st_))
     _lib.check(_lib.lib.gssd_conv2d_nhwc_f32(C.byref(d0), st_))
 

@@ -58,6 +58,11 @@ class SnItem(C.Structure):
     _fields_ = [('w', c_fp), ('u', c_fp), ('v', c_fp), ('inv_sigma', c_fp), ('rows', c_i), ('cols', c_i)]
 
 
+class SgdHyper(C.Structure):
+    """struct gssd_sgd_hyper: one param group's hyperparameters, a host-side argument of gssd_sgd_step_f32."""
+    _fields_ = [('lr', c_f), ('weight_decay', c_f), ('momentum', c_f), ('dampening', c_f), ('nesterov', C.c_int32)]
+
+
 OUT_NHWC, OUT_TRANSPOSED, OUT_HEADS, OUT_SPLIT_T = 0, 1, 2, 3
 CONV_OUT_F32, CONV_OUTB_BF16_PERM32, CONV_HEADS_SLICES, CONV_POOL2, CONV_RESID_F32, CONV_F16_OK = 1, 2, 4, 8, 16, 32
 CONV_IN_NCHW3, CONV_OUT_GROUPCAT, CONV_OUT_X6PLANES, CONV_RESID_XF = 64, 128, 256, 512
@@ -214,6 +219,11 @@ SIGNATURES = {
     'gssd_loss_backward': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     'gssd_detect': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
     'gssd_softmax_lastdim_f32': (c_i, [c_fp, c_fp, c_i64, c_i, c_fp]),
+    'gssd_optim_chunk_elems': (c_i, []),
+    'gssd_optim_sumsq_blocks': (c_i, [c_i]),
+    'gssd_grad_sumsq_f32': (c_i, [c_fp, c_fp, c_i, c_fp, c_fp]),
+    'gssd_sgd_step_f32': (c_i, [c_fp, c_fp, c_i, C.POINTER(SgdHyper), c_i, c_fp, c_i, c_f, c_fp, c_fp]),
+    'gssd_grad_scale_clip_f32': (c_i, [c_fp, c_fp, c_i, c_fp, c_i, c_f, c_fp, c_fp]),
 }
 
 

@@ -1,0 +1,229 @@
+// The optimizer step of the reference driver (train_lesion_multiphase_v2.py:252-253: clip_grad_norm_ then SGD.step() with momentum,
+// weight decay and a second learning-rate group) as two launches over a device table of tensors: gssd_grad_sumsq_f32 leaves one fp64
+// partial sum of g^2 per workgroup, gssd_sgd_step_f32 (or, stand-alone, gssd_grad_scale_clip_f32) adds them up again in EVERY workgroup
+// -- same order everywhere, so every workgroup holds the same clip coefficient to the bit and no grid-wide hand-off is needed -- and
+// updates p and buf in place: 5 memory passes (read g, p, buf; write p, buf) + 1 for the norm, where the ATen foreach form makes 11 + 3.
+//
+// Work is cut into chunks of CHUNK elements of ONE tensor (the host lists them: gssd/optim.py), one workgroup per chunk in the update
+// kernels, so the 2.4 M-element DCN weight and the one-element sigma load the machine alike.  A chunk starts at a multiple of CHUNK
+// elements, so its alignment is that of the tensors' base pointers.
+//
+// p and buf are read and written through the same pointer: none of the pointers below is __restrict__.
+#include "common.h"
+#include "kernel_util.h"
+
+namespace {
+
+constexpr int CHUNK = 4096;            // elements per chunk: 4 x 16 bytes per thread and array
+constexpr int THREADS = 256;
+constexpr int SUMSQ_MAX_BLOCKS = 1024; // partial sums every update workgroup re-reads (8 KiB, L2 resident)
+constexpr int HYPER_CAP = 8;           // param groups per launch of the step kernel (by-value kernel argument)
+
+struct HyperArgs {
+    gssd_sgd_hyper h[HYPER_CAP];
+    int g0, ng;                        // this launch updates the groups [g0, g0 + ng)
+};
+
+// The tensors' pointers come out of the table, where the compiler cannot see their address space: saying "global" here turns the
+// flat_load / flat_store it would emit (counted by vmcnt AND lgkmcnt) into global_load / global_store.
+typedef __attribute__((address_space(1))) float gfloat;
+typedef __attribute__((address_space(1))) f32x4 gfloat4;
+__device__ __forceinline__ gfloat* as_global(const float* p) { return (gfloat*)p; }
+
+__device__ __forceinline__ bool aligned16(const gfloat* p) { return ((uintptr_t)p & 15) == 0; }
+
+// sum over the workgroup, the same value (to the bit) in every thread: xor-butterfly inside the waves, then the four waves in order
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__device__ __forceinline__ int chunk_len(const gssd_sgd_item& it, const gssd_sgd_chunk& ch) {
+    const int64_t left = it.n - ch.off;
+    return left < CHUNK ? (int)left : CHUNK;
+}
+
+__global__ __launch_bounds__(THREADS) void grad_sumsq_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks,
+                                                             double* partials) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const gssd_sgd_chunk ch = chunks[c];
+        const gssd_sgd_item it = items[ch.item];
+        const gfloat* g = as_global(it.g) + ch.off;
+        const int len = chunk_len(it, ch);
+        int done = 0;
+        if (aligned16(g)) {
+            const gfloat4* g4 = (const gfloat4*)g;
+            const int nv = len >> 2;
+#pragma unroll 4
+            for (int i = threadIdx.x; i < nv; i += THREADS) {
+                const f32x4 v = g4[i];
+                acc += (double)v.x * (double)v.x + (double)v.y * (double)v.y + ((double)v.z * (double)v.z + (double)v.w * (double)v.w);
+            }
+            done = nv << 2;
+        }
+        for (int i = done + threadIdx.x; i < len; i += THREADS) acc += (double)g[i] * (double)g[i];
+    }
+    const double s = block_sum(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// torch.nn.utils.clip_grad_norm_: total = ||g||_2, coefficient = clamp(max_norm / (total + 1e-6), max = 1) -- a NaN stays a NaN
+__device__ __forceinline__ float clip_coef(const double* partials, int n_partials, float max_norm, double* red, float& total) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_partials; i += THREADS) s += partials[i];
+    s = block_sum(s, red);
+    total = (float)sqrt(s);
+    const float coef = max_norm / (total + 1e-6f);
+    return coef > 1.f ? 1.f : coef;
+}
+
+struct Hyper {
+    float lr, wd, mom, omd;            // omd = 1 - dampening
+    bool nesterov, has_buf, first;
+};
+
+__device__ __forceinline__ void sgd_update(float& p, const float g, float& b, const float c, const Hyper& h) {
+    const float cg = c * g;
+    const float d = h.wd != 0.f ? fmaf(h.wd, p, cg) : cg;
+    float step = d;
+    if (h.has_buf) {
+        b = h.first ? d : fmaf(h.mom, b, h.omd * d);
+        step = h.nesterov ? fmaf(h.mom, b, d) : b;
+    }
+    p = fmaf(-h.lr, step, p);
+}
+
+// NV: 16-byte vectors per thread, known at compile time for a full chunk (all loads of a thread issue before the first use)
+template <int NV>
+__device__ __forceinline__ void sgd_vec(gfloat4* p4, const gfloat4* g4, gfloat4* b4, int nv, const float c, const Hyper& h) {
+    const bool rd_b = h.has_buf && !h.first;
+    f32x4 pv[NV], gv[NV], bv[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int i = threadIdx.x + k * THREADS;
+        if (i < nv) {
+            pv[k] = p4[i];
+            gv[k] = g4[i];
+            bv[k] = rd_b ? b4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int i = threadIdx.x + k * THREADS;
+        if (i < nv) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = pv[k][e], be = bv[k][e];
+                sgd_update(pe, gv[k][e], be, c, h);
+                pv[k][e] = pe, bv[k][e] = be;
+            }
+            p4[i] = pv[k];
+            if (h.has_buf) b4[i] = bv[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void sgd_step_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, const HyperArgs hy,
+                                                           const double* partials, int n_partials, float max_norm, float* norm_out) {
+    __shared__ double red[4];
+    float c = 1.f;
+    if (max_norm >= 0.f) {
+        float total;
+        c = clip_coef(partials, n_partials, max_norm, red, total);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && hy.g0 == 0) norm_out[0] = total;
+    }
+    const gssd_sgd_chunk ch = chunks[blockIdx.x];
+    const gssd_sgd_item it = items[ch.item];
+    const int gi = __builtin_amdgcn_readfirstlane(it.group) - hy.g0;
+    if (gi < 0 || gi >= hy.ng) return;                    // a group of another launch
+    const gssd_sgd_hyper gh = hy.h[gi];
+    Hyper h;
+    h.lr = gh.lr, h.wd = gh.weight_decay, h.mom = gh.momentum, h.omd = 1.f - gh.dampening;
+    h.nesterov = gh.nesterov != 0, h.has_buf = it.buf != nullptr, h.first = (it.flags & 1) != 0;
+    gfloat* p = as_global(it.p) + ch.off;
+    const gfloat* g = as_global(it.g) + ch.off;
+    gfloat* b = h.has_buf ? as_global(it.buf) + ch.off : nullptr;
+    const int len = chunk_len(it, ch);
+    int done = 0;
+    if (aligned16(p) && aligned16(g) && aligned16(b)) {
+        constexpr int NV = CHUNK / 4 / THREADS;
+        const int nv = len >> 2;
+        sgd_vec<NV>((gfloat4*)p, (const gfloat4*)g, (gfloat4*)b, nv, c, h);
+        done = nv << 2;
+    }
+    for (int i = done + threadIdx.x; i < len; i += THREADS) {
+        float pv = p[i], bv = (h.has_buf && !h.first) ? b[i] : 0.f;
+        sgd_update(pv, g[i], bv, c, h);
+        p[i] = pv;
+        if (h.has_buf) b[i] = bv;
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void grad_scale_clip_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks,
+                                                                  const double* partials, int n_partials, float max_norm, float* norm_out) {
+    __shared__ double red[4];
+    float total;
+    const float c = clip_coef(partials, n_partials, max_norm, red, total);
+    if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = total;
+    const gssd_sgd_chunk ch = chunks[blockIdx.x];
+    const gssd_sgd_item it = items[ch.item];
+    gfloat* g = as_global(it.g) + ch.off;                 // (the table's gradients are plain device memory: this kernel writes them)
+    const int len = chunk_len(it, ch);
+    int done = 0;
+    if (aligned16(g)) {
+        gfloat4* g4 = (gfloat4*)g;
+        const int nv = len >> 2;
+#pragma unroll 4
+        for (int i = threadIdx.x; i < nv; i += THREADS) g4[i] = g4[i] * c;
+        done = nv << 2;
+    }
+    for (int i = done + threadIdx.x; i < len; i += THREADS) g[i] = g[i] * c;
+}
+
+int sumsq_blocks(int n_chunks) { return n_chunks < SUMSQ_MAX_BLOCKS ? n_chunks : SUMSQ_MAX_BLOCKS; }
+
+}  // namespace
+
+extern "C" int gssd_optim_chunk_elems(void) { return CHUNK; }
+
+extern "C" int gssd_optim_sumsq_blocks(int n_chunks) { return n_chunks > 0 ? sumsq_blocks(n_chunks) : 0; }
+
+extern "C" int gssd_grad_sumsq_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, double* partials,
+                                   gssd_stream_t stream) {
+    GSSD_CHECK_ARG(items && chunks && n_chunks > 0 && partials);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(sumsq_blocks(n_chunks)), dim3(THREADS), 0, as_stream(stream), items, chunks, n_chunks,
+                       partials);
+    GSSD_CHECK_LAUNCH();
+    return GSSD_OK;
+}
+
+extern "C" int gssd_sgd_step_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const gssd_sgd_hyper* hyper,
+                                 int n_groups, const double* partials, int n_partials, float max_norm, float* norm_out,
+                                 gssd_stream_t stream) {
+    GSSD_CHECK_ARG(items && chunks && n_chunks > 0 && hyper && n_groups > 0);
+    const bool clip = max_norm >= 0.f;
+    GSSD_CHECK_ARG(!clip || (partials && n_partials > 0 && norm_out));
+    for (int g0 = 0; g0 < n_groups; g0 += HYPER_CAP) {
+        HyperArgs hy = {};
+        hy.g0 = g0;
+        hy.ng = n_groups - g0 < HYPER_CAP ? n_groups - g0 : HYPER_CAP;
+        for (int i = 0; i < hy.ng; ++i) hy.h[i] = hyper[g0 + i];
+        hipLaunchKernelGGL(sgd_step_kernel, dim3(n_chunks), dim3(THREADS), 0, as_stream(stream), items, chunks, hy, partials, n_partials,
+                           max_norm, norm_out);
+        GSSD_CHECK_LAUNCH();
+    }
+    return GSSD_OK;
+}
+
+extern "C" int gssd_grad_scale_clip_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const double* partials,
+                                        int n_partials, float max_norm, float* norm_out, gssd_stream_t stream) {
+    GSSD_CHECK_ARG(items && chunks && n_chunks > 0 && partials && n_partials > 0 && norm_out);
+    hipLaunchKernelGGL(grad_scale_clip_kernel, dim3(n_chunks), dim3(THREADS), 0, as_stream(stream), items, chunks, partials, n_partials,
+                       max_norm, norm_out);
+    GSSD_CHECK_LAUNCH();
+    return GSSD_OK;
+}

@@ -1,0 +1,263 @@
+"""The optimizer step on the device: ``SGD`` (torch.optim.SGD's update rule and state layout, optionally with the gradient-norm clip
+fused in) and a stand-alone ``clip_grad_norm_``, each two launches of csrc/optim.hip over a device table of tensors.
+
+The reference driver's step (train_lesion_multiphase_v2.py:242-253) then runs on this library's kernels alone:
+
+    optimizer = gssd.optim.SGD(groups, lr=..., momentum=0.9, weight_decay=5e-4, max_grad_norm=max_norm)   # :603-626
+    ...
+    loss.backward(); optimizer.step()                                                                     # :251-253, clip included
+
+Nothing here reads back to the host.  There is no CPU fallback: a parameter or gradient that is not a contiguous fp32 device tensor
+raises GssdError.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import GssdError, check, lib
+
+CHUNK = lib.gssd_optim_chunk_elems()      # elements per chunk (csrc/optim.hip)
+
+_ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('buf', np.uint64), ('n', np.int64), ('group', np.int32), ('flags', np.int32)])
+_CHUNK = np.dtype([('off', np.int64), ('item', np.int32), ('reserved', np.int32)])
+FIRST_STEP = 1
+
+
+def build_chunks(numels, chunk=None):
+    """The chunk list of a table whose item i has numels[i] elements: (item index, element offset) arrays, item by item, offsets
+    0, chunk, 2 chunk, ... below numels[i].  Every element lies in exactly one chunk, no chunk crosses an item, an empty item has none."""
+    chunk = chunk or CHUNK
+    items, offs = [], []
+    for i, n in enumerate(numels):
+        k = -(-int(n) // chunk)
+        items.append(np.full(k, i, np.int32))
+        offs.append(np.arange(k, dtype=np.int64) * chunk)
+    if not items:
+        return np.zeros(0, np.int32), np.zeros(0, np.int64)
+    return np.concatenate(items), np.concatenate(offs)
+
+
+class _Table:
+    """Device copies of gssd_sgd_item[n] / gssd_sgd_chunk[m] and the partial-sum workspace that goes with them."""
+
+    def __init__(self, rows, device):
+        # rows: (p ptr, g ptr, buf ptr, numel, group, flags), numel > 0
+        items = np.zeros(len(rows), _ITEM)
+        for i, r in enumerate(rows):
+            items[i] = r
+        ci, co = build_chunks([r[3] for r in rows])
+        chunks = np.zeros(len(ci), _CHUNK)
+        chunks['item'], chunks['off'] = ci, co
+        self.n_chunks = len(ci)
+        self.n_partials = lib.gssd_optim_sumsq_blocks(self.n_chunks)
+        self.items = torch.from_numpy(items.view(np.uint8).copy()).to(device)
+        self.chunks = torch.from_numpy(chunks.view(np.uint8).copy()).to(device)
+        self.partials = torch.empty(max(self.n_partials, 1), device=device, dtype=torch.float64)
+
+    def sumsq(self, stream, partials=None):
+        partials = self.partials if partials is None else partials
+        check(lib.gssd_grad_sumsq_f32(self.items.data_ptr(), self.chunks.data_ptr(), self.n_chunks, partials.data_ptr(), stream))
+
+
+def _check_tensor(t, what, device=None):
+    if not isinstance(t, torch.Tensor) or t.layout != torch.strided or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        d = f'{t.layout}, {t.device}, {t.dtype}, shape {tuple(t.shape)}, strides {t.stride() if t.layout == torch.strided else None}'
+        raise GssdError(f'gssd.optim: {what} must be a contiguous fp32 tensor on the MI355X (got {d}); there is no CPU fallback')
+    if device is not None and t.device != device:
+        raise GssdError(f'gssd.optim: {what} is on {t.device}, the other tensors on {device}')
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+class SGD(torch.optim.Optimizer):
+    """torch.optim.SGD's constructor, update rule, ``param_groups`` and ``state[p]['momentum_buffer']`` -- checkpoints go either way --
+    with the whole step in ONE launch of csrc/optim.hip for all parameters of all groups.
+
+    ``max_grad_norm`` (extra keyword): when set, step() is ``clip_grad_norm_(all params, max_grad_norm)`` + the update in two launches.
+    The clip coefficient is applied inside the update; the gradients themselves are left UNSCALED (read ``p.grad`` after step() and you
+    see what backward wrote).  The total norm of the step is left in ``self.grad_norm``, a 0-dim device tensor that the next step
+    overwrites (None without max_grad_norm).
+
+    Momentum buffers are created on the first step as slices of one flat tensor (a gradient or group that appears later gets another);
+    after ``load_state_dict`` they are whatever torch put there.
+
+    ``maximize``, ``foreach``, ``fused`` and ``differentiable`` are accepted for signature compatibility and must keep their defaults.
+    Hyperparameters are read from ``param_groups`` at every step (Python numbers), so editing ``param_groups[i]['lr']`` takes effect at
+    once.  Parameters whose ``grad`` is None are skipped, as in torch.  After the launch every updated parameter's version counter is
+    bumped: GssdEngine re-packs its weights on that signal."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False, foreach=None,
+                 differentiable=False, fused=None, max_grad_norm=None):
+        if isinstance(lr, torch.Tensor):
+            raise NotImplementedError('gssd.optim.SGD: lr must be a Python number (a tensor lr would need a host read per step)')
+        if lr < 0.0:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if momentum < 0.0:
+            raise ValueError(f'Invalid momentum value: {momentum}')
+        if weight_decay < 0.0:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        for name, v in (('maximize', maximize), ('foreach', foreach), ('differentiable', differentiable), ('fused', fused)):
+            if v:
+                raise NotImplementedError(f'gssd.optim.SGD: {name}={v!r} is not implemented')
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f'Invalid max_grad_norm: {max_grad_norm}')
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=False,
+                        foreach=None, differentiable=False, fused=None)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None
+        self._table = None         # (_Table, key, updated params, table holds first-step flags, device)
+        super().__init__(params, defaults)
+
+    # ------------------------------------------------------------------------------------------
+    def _table_key(self):
+        """Everything the device table depends on: per group whether it keeps momentum, per parameter the storage pointers of the
+        parameter, its gradient and its momentum buffer (0: none), and the gradient's dtype and size (a new gradient that the allocator
+        put at the old address must be validated again)."""
+        key, state = [], self.state.get                 # (.get: asking creates no state entry)
+        for g in self.param_groups:
+            key.append(g['momentum'] != 0)
+            for p in g['params']:
+                s, grad = state(p), p.grad
+                buf = s.get('momentum_buffer') if s else None
+                if grad is None:
+                    key.append((p.data_ptr(), 0, 0 if buf is None else buf.data_ptr()))
+                else:
+                    key.append((p.data_ptr(), grad.data_ptr(), 0 if buf is None else buf.data_ptr(), grad.dtype, grad.numel()))
+        return tuple(key)
+
+    def _build(self):
+        todo, device = [], None
+        for gi, g in enumerate(self.param_groups):
+            for name in ('maximize', 'foreach', 'differentiable', 'fused'):
+                if g.get(name):
+                    raise NotImplementedError(f'gssd.optim.SGD: param_groups[{gi}][{name!r}]={g[name]!r} is not implemented')
+            for pi, p in enumerate(g['params']):
+                if p.grad is None:
+                    continue
+                what = f'param_groups[{gi}]["params"][{pi}] (shape {tuple(p.shape)})'
+                _check_tensor(p.detach(), what, device)
+                device = p.device
+                _check_tensor(p.grad, 'the gradient of ' + what, device)
+                if p.grad.shape != p.shape:
+                    raise GssdError(f'gssd.optim: the gradient of {what} has shape {tuple(p.grad.shape)}')
+                if p.numel() == 0:
+                    continue
+                buf = None
+                if g['momentum'] != 0:
+                    buf = self.state[p].get('momentum_buffer') if p in self.state else None
+                    if buf is not None:
+                        _check_tensor(buf, 'the momentum buffer of ' + what, device)
+                        if buf.numel() != p.numel():
+                            raise GssdError(f'gssd.optim: the momentum buffer of {what} has {buf.numel()} elements')
+                todo.append((gi, p, buf, g['momentum'] != 0))
+        # new momentum buffers: 16-byte aligned slices of one flat tensor (the views keep it alive).  All of them on the first step; a
+        # gradient or group that appears later gets a flat tensor of its own
+        fresh = [p for _, p, buf, mom in todo if mom and buf is None]
+        if fresh:
+            flat = torch.empty(sum(-(-p.numel() // 4) * 4 for p in fresh), device=device, dtype=torch.float32)
+            o = 0
+            for p in fresh:
+                self.state[p]['momentum_buffer'] = flat[o:o + p.numel()].view(p.shape)
+                o += -(-p.numel() // 4) * 4
+        fresh = set(fresh)
+        rows, params = [], []
+        for gi, p, buf, mom in todo:
+            first = p in fresh
+            if mom and buf is None:
+                buf = self.state[p]['momentum_buffer']
+            rows.append((p.data_ptr(), p.grad.data_ptr(), 0 if buf is None else buf.data_ptr(), p.numel(), gi, FIRST_STEP if first else 0))
+            params.append(p)
+        table = _Table(rows, device) if rows else None
+        if table is not None and self.max_grad_norm is not None and self.grad_norm is None:
+            self.grad_norm = torch.zeros((), device=device, dtype=torch.float32)
+        return table, params, bool(fresh), device
+
+    def _hyper(self):
+        arr = (_lib.SgdHyper * len(self.param_groups))()
+        for h, g in zip(arr, self.param_groups):
+            for name in ('lr', 'weight_decay', 'momentum', 'dampening'):
+                if isinstance(g[name], torch.Tensor):
+                    raise NotImplementedError(f'gssd.optim.SGD: {name} must be a Python number')
+            h.lr, h.weight_decay, h.momentum, h.dampening, h.nesterov = g['lr'], g['weight_decay'], g['momentum'], g['dampening'], \
+                bool(g['nesterov'])
+        return arr
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        key = self._table_key() if self._table is not None else None
+        if self._table is None or self._table[1] != key:
+            table, params, first, device = self._build()
+            self._table = (table, self._table_key(), params, first, device)
+        table, _, params, first, device = self._table
+        if table is None:
+            return loss
+        hyper = self._hyper()
+        clip = self.max_grad_norm is not None
+        with torch.cuda.device(device):
+            stream = _stream(device)
+            if clip:
+                table.sumsq(stream)
+            check(lib.gssd_sgd_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, hyper, len(hyper),
+                                        table.partials.data_ptr(), table.n_partials, self.max_grad_norm if clip else -1.0,
+                                        self.grad_norm.data_ptr() if clip else None, stream))
+        torch.autograd.graph.increment_version(params)
+        if first:
+            self._table = None       # the table carries first-step flags: the next step builds one without them
+        return loss
+
+
+# (device, ((grad ptr, numel), ...)) -> _Table, the few most recent: building a table costs a host-to-device copy, and a training loop
+# clips the same gradients every step.  Only the read-only item / chunk lists are shared; every call brings its own partial sums, so
+# calls on several streams do not meet.  At most _CLIP_TABLES_MAX tables (~100 KB each for this network) outlive their model.
+_CLIP_TABLES = {}
+_CLIP_TABLES_MAX = 4
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False):
+    """torch.nn.utils.clip_grad_norm_ (the driver's line 252) for contiguous fp32 device gradients, in two launches: the gradients are
+    scaled in place by min(1, max_norm / (total_norm + 1e-6)), and the total norm comes back as a 0-dim device tensor.  Only the 2-norm;
+    ``error_if_nonfinite`` would need a host read and is not implemented."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError(f'gssd.optim.clip_grad_norm_: norm_type={norm_type!r} (only 2)')
+    if error_if_nonfinite:
+        raise NotImplementedError('gssd.optim.clip_grad_norm_: error_if_nonfinite=True needs a host read of the norm')
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads, device = [], None
+    for i, p in enumerate(parameters):
+        if p.grad is None:
+            continue
+        _check_tensor(p.grad, f'the gradient of parameter {i} (shape {tuple(p.shape)})', device)
+        device = p.grad.device
+        if p.grad.numel():
+            grads.append(p.grad)
+    if not grads:
+        if device is None:
+            raise GssdError('gssd.optim.clip_grad_norm_: no parameter has a gradient (and so no device to put the norm on)')
+        return torch.zeros((), device=device, dtype=torch.float32)
+    key = (device, tuple((g.data_ptr(), g.numel()) for g in grads))
+    table = _CLIP_TABLES.pop(key, None)
+    if table is None:
+        table = _Table([(0, g.data_ptr(), 0, g.numel(), 0, 0) for g in grads], device)
+        while len(_CLIP_TABLES) >= _CLIP_TABLES_MAX:
+            _CLIP_TABLES.pop(next(iter(_CLIP_TABLES)))
+    _CLIP_TABLES[key] = table
+    norm = torch.empty((), device=device, dtype=torch.float32)
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        partials = torch.empty(table.n_partials, device=device, dtype=torch.float64)
+        table.sumsq(stream, partials)
+        check(lib.gssd_grad_scale_clip_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, partials.data_ptr(),
+                                           table.n_partials, float(max_norm), norm.data_ptr(), stream))
+    torch.autograd.graph.increment_version(grads)
+    return norm

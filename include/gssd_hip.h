@@ -903,6 +903,47 @@ int gssd_conv_thin_x6_takes(const gssd_conv_desc* d);
 /* 1 when gssd_conv2d_nhwc_f32 runs the descriptor (with or without the flag set) in its GSSD_CONV_IN_NCHW3 form */
 int gssd_conv_thin_nchw3_takes(const gssd_conv_desc* d);
 
+/* ------------------------------------------------------------------------------------------
+ * Optimizer step (csrc/optim.hip): clip_grad_norm_ + SGD.step() of train_lesion_multiphase_v2.py:252-253 in two launches
+ * ------------------------------------------------------------------------------------------
+ * All three kernels walk a device table of tensors (one item per parameter that has a gradient) and a device list of chunks: chunk k is
+ * the elements [off, min(off + CH, n)) of items[item], CH = gssd_optim_chunk_elems() and off a multiple of CH, so a 2.4 M-element DCN
+ * weight and the one-element sigma spread over the workgroups alike.  A chunk whose p, g and buf are all 16-byte aligned at `off` moves
+ * as 16-byte vectors, any other element by element.  p and buf are updated in place.
+ * Hyperparameters are NOT in the table: `hyper` is a HOST array of n_groups entries read during the call (items[i].group indexes it), so
+ * a changed learning rate needs no new table. */
+typedef struct gssd_sgd_item {
+    float* p;       /* parameter, n floats */
+    const float* g; /* its gradient */
+    float* buf;     /* momentum buffer; NULL: the group's momentum is 0 */
+    int64_t n;
+    int32_t group;
+    int32_t flags;  /* bit 0: first step of this buffer: buf = d, no dampening (torch's rule) */
+} gssd_sgd_item;
+typedef struct gssd_sgd_chunk {
+    int64_t off;
+    int32_t item, reserved;
+} gssd_sgd_chunk;
+typedef struct gssd_sgd_hyper {
+    float lr, weight_decay, momentum, dampening;
+    int32_t nesterov;
+} gssd_sgd_hyper;
+int gssd_optim_chunk_elems(void);
+/* length of `partials` for a list of n_chunks chunks: the workgroup count of gssd_grad_sumsq_f32, fixed by n_chunks alone */
+int gssd_optim_sumsq_blocks(int n_chunks);
+/* partials[b] = the fp64 sum of g * g over the chunks b, b + blocks, b + 2 blocks, ... -- no atomics: bitwise reproducible */
+int gssd_grad_sumsq_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, double* partials, gssd_stream_t stream);
+/* max_norm >= 0: every workgroup adds `partials` up in one fixed order, total = sqrt of the sum, c = min(1, max_norm / (total + 1e-6))
+ * (torch.nn.utils.clip_grad_norm_, norm_type 2; a non-finite total propagates as it does there) and workgroup 0 writes total to
+ * norm_out[0].  max_norm < 0: c = 1, partials and norm_out are not touched.  Then per element, with its group's hyperparameters:
+ *   d = c g + weight_decay p;  buf = first ? d : momentum buf + (1 - dampening) d;  step = nesterov ? d + momentum buf : buf
+ *   (buf NULL: step = d);  p -= lr step.      The gradients are left as they are (unscaled). */
+int gssd_sgd_step_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const gssd_sgd_hyper* hyper, int n_groups,
+                      const double* partials, int n_partials, float max_norm, float* norm_out, gssd_stream_t stream);
+/* the stand-alone clip_grad_norm_: the same c, g *= c in place (p and buf of the items are not read), total to norm_out[0] */
+int gssd_grad_scale_clip_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const double* partials,
+                             int n_partials, float max_norm, float* norm_out, gssd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,7 +99,7 @@ __device__ __forceinline__ int wave_sum(int v) {
 }
 
 // What the conv dispatchers hand down their gssd_try_* / launch chain: the stream to launch on, or (name != nullptr) the buffer
-// gssd_conv2d_kernel_name wants the chosen kernel instance's name in.  A launch site names its instance FIRST -- before any HIP call
+// gssd_conv2d_kernel_name / gssd_conv2d_wgrad_kernel_name want the chosen kernel instance's name in.  A launch site names its instance FIRST -- before any HIP call
 // or claimed resource -- so the query runs the dispatch's own control flow and touches no device.
 struct gssd_conv_ctx {
     hipStream_t stream = nullptr;
@@ -159,13 +159,15 @@ int gssd_try_conv_patch_x6(const gssd_conv_desc& d, gssd_conv_ctx& c);
 int gssd_try_conv_thin_x6(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // conv_thin_wino.hip: conv1_2's shape class (4 x 16 -> 16 channels, large map) with Winograd weights; else returns 1
 int gssd_try_conv_thin_wino(const gssd_conv_desc& d, gssd_conv_ctx& c);
-int gssd_try_conv_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream);
+// The weight gradient's chain (conv_wgrad.hip: gssd_conv2d_wgrad_f32 and, with a name sink in `c`, gssd_conv2d_wgrad_kernel_name):
+// conv_thin_wgrad.hip: conv1_1 / conv1_2 shapes (patch-staged, wave = phase group); else returns 1
+int gssd_try_conv_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c);
 // conv_patch_wgrad.hip: conv2_1 .. conv3_3 shapes (patch-staged, one phase group per workgroup); else returns 1
-int gssd_try_conv_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream);
+int gssd_try_conv_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c);
 // gemm_slot.hip: large plain 1x1 convs / GEMMs as a slot-scheduled 128 x 256 MFMA stream; returns 1 for every other shape
 int gssd_try_gemm_slot(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // wgrad_slot.hip: weight gradient of large plain 1x1 convs (and the DCN contraction) as a slot-scheduled TN GEMM; else returns 1
-int gssd_try_wgrad_slot(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream);
+int gssd_try_wgrad_slot(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c);
 // conv_thin_bf16.hip: bf16 thin trunk layers (conv1_1 .. conv2_2); returns 1 when the descriptor is not one of them
 int gssd_try_conv_thin_bf16(const gssd_conv_desc& d, gssd_conv_ctx& c);
 // conv_flat_bf16.hip: bf16 grouped 3x3 trunk layers with 32 .. 128 channels per group (conv3_1 .. conv6); returns 1 when not one of them

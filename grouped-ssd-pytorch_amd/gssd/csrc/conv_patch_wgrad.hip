@@ -133,7 +133,8 @@ __global__ __launch_bounds__(256, 2) void conv_patch_wgrad_kernel(const PatchWgr
 }
 
 template <int CIN_G, int COUT_G, bool XF>
-int launch_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream) {
+int launch_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_patch_wgrad<%d,%d>%s", CIN_G, COUT_G, XF ? "" : "/plain");
     constexpr int QPR = CIN_G / 4, PPI = 64 / QPR;
     PatchWgradParams p;
     p.in = d.in;
@@ -163,7 +164,7 @@ int launch_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipS
     int gx = 256 * per_cu / d.groups;
     if (gx < 1) gx = 1;
     if (ntiles < gx) gx = (int)ntiles;
-    hipLaunchKernelGGL(kern, dim3(gx, d.groups), dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(gx, d.groups), dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -171,7 +172,7 @@ int launch_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipS
 }  // namespace
 
 // returns 1 when the descriptor is not one of the patch-staged shapes
-int gssd_try_conv_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream) {
+int gssd_try_conv_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c) {
     const int cout_g = d.Cout / d.groups;
     const bool ok = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.dil == 1 && !d.m_per_image && d.H * d.W >= 38 * 38 &&
                     d.in_stride % 4 == 0 && d.in_ch_off % 4 == 0 && (long long)d.B * d.H * d.W * d.in_stride < (1ll << 31) &&
@@ -179,7 +180,7 @@ int gssd_try_conv_patch_wgrad(const gssd_conv_desc& d, const float* dy, float* d
     if (!ok) return 1;
 #define GSSD_PW(CI, CO)                                                                                     \
     if (d.cin_g == CI && cout_g == CO)                                                                       \
-        return d.in_scale ? launch_patch_wgrad<CI, CO, true>(d, dy, dw, stream) : launch_patch_wgrad<CI, CO, false>(d, dy, dw, stream);
+        return d.in_scale ? launch_patch_wgrad<CI, CO, true>(d, dy, dw, c) : launch_patch_wgrad<CI, CO, false>(d, dy, dw, c);
     GSSD_PW(16, 32)
     GSSD_PW(32, 32)
     GSSD_PW(32, 64)

@@ -142,7 +142,8 @@ __global__ __launch_bounds__(256, 2) void conv_thin_wgrad_kernel(const ThinWgrad
 }
 
 template <int CIN_G, bool XF>
-int launch_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream) {
+int launch_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_thin_wgrad<%d>%s", CIN_G, XF ? "" : "/plain");
     constexpr int CIN = 4 * CIN_G, PPI = 64 / (CIN / 4);
     ThinWgradParams p;
     p.in = d.in;
@@ -163,7 +164,7 @@ int launch_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipSt
     const long long ntiles = (long long)d.B * p.tiles_y * p.tiles_x;
     int grid = 512;
     if (ntiles < grid) grid = (int)ntiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -171,12 +172,12 @@ int launch_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipSt
 }  // namespace
 
 // returns 1 when the descriptor is not a thin shape
-int gssd_try_conv_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream) {
+int gssd_try_conv_thin_wgrad(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c) {
     const int cout_g = d.Cout / d.groups;
     const bool ok = d.groups == 4 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.dil == 1 && cout_g == 16 &&
                     (d.cin_g == 4 || d.cin_g == 16) && d.in_stride == 4 * d.cin_g && d.in_ch_off == 0 && !d.m_per_image &&
                     d.H * d.W >= 75 * 75 && (long long)d.B * d.H * d.W * 64 < (1ll << 31);
     if (!ok) return 1;
-    if (d.cin_g == 4) return d.in_scale ? launch_thin_wgrad<4, true>(d, dy, dw, stream) : launch_thin_wgrad<4, false>(d, dy, dw, stream);
-    return d.in_scale ? launch_thin_wgrad<16, true>(d, dy, dw, stream) : launch_thin_wgrad<16, false>(d, dy, dw, stream);
+    if (d.cin_g == 4) return d.in_scale ? launch_thin_wgrad<4, true>(d, dy, dw, c) : launch_thin_wgrad<4, false>(d, dy, dw, c);
+    return d.in_scale ? launch_thin_wgrad<16, true>(d, dy, dw, c) : launch_thin_wgrad<16, false>(d, dy, dw, c);
 }

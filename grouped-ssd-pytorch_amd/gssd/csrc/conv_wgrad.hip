@@ -223,8 +223,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
 }
 
 template <int MT, int WM, int WN>
-int launch_wgrad(WgradParams& p, hipStream_t stream) {
+int launch_wgrad(WgradParams& p, gssd_conv_ctx& c) {
     constexpr int BMW = WM * MT * 16, BNW = WN * 64;
+    if (c.name) return gssd_name_kernel(c, "conv_wgrad<%dx%d>", BMW, BNW);
     const int cout_g = p.Cout / p.groups;
     p.m_tiles = (cout_g + BMW - 1) / BMW;
     p.n_tiles = (p.K + BNW - 1) / BNW;
@@ -241,7 +242,7 @@ int launch_wgrad(WgradParams& p, hipStream_t stream) {
     auto kern = conv_wgrad_kernel<MT, WM, WN>;
     static unsigned attr_mask = 0;     // one bit per device (the attribute is per device)
     if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
-    hipLaunchKernelGGL(kern, dim3(gx, (unsigned)tiles), dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(gx, (unsigned)tiles), dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
@@ -279,7 +280,8 @@ __global__ void pack_weight_dgrad_kernel(const float* __restrict__ w, float* __r
 
 }  // namespace
 
-extern "C" int gssd_conv2d_wgrad_f32(const gssd_conv_desc* dp, const float* dy, float* dw_packed, gssd_stream_t stream) {
+// gssd_conv2d_wgrad_f32 and, with a name sink in `c`, gssd_conv2d_wgrad_kernel_name: one walk through validation and dispatch for both
+static int wgrad_dispatch_f32(const gssd_conv_desc* dp, const float* dy, float* dw_packed, gssd_conv_ctx& c) {
     GSSD_CHECK_ARG(dp && dy && dw_packed);
     const gssd_conv_desc& d = *dp;
     GSSD_CHECK_ARG(d.in && d.groups > 0 && d.Cout % d.groups == 0 && d.cin_g % 4 == 0 && !d.m_per_image);
@@ -287,16 +289,16 @@ extern "C" int gssd_conv2d_wgrad_f32(const gssd_conv_desc* dp, const float* dy, 
     GSSD_CHECK_ARG((d.Cout / d.groups) % 4 == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)d.in % 16) == 0);
     GSSD_CHECK_ARG((d.in_scale == nullptr) == (d.in_shift == nullptr) && (d.in_scale == nullptr) == (d.in_pad == nullptr));
     {
-        const int rc = gssd_try_conv_thin_wgrad(d, dy, dw_packed, as_stream(stream));    // conv1_1 / conv1_2: patch-staged
+        const int rc = gssd_try_conv_thin_wgrad(d, dy, dw_packed, c);    // conv1_1 / conv1_2: patch-staged
         if (rc != 1) return rc;
     }
     {
-        const int rc = gssd_try_conv_patch_wgrad(d, dy, dw_packed, as_stream(stream));   // conv2_1 .. conv3_3: patch-staged per group
+        const int rc = gssd_try_conv_patch_wgrad(d, dy, dw_packed, c);   // conv2_1 .. conv3_3: patch-staged per group
         if (rc != 1) return rc;
     }
     {
         static const bool no_slot = getenv("GSSD_NO_GEMM_SLOT") != nullptr || getenv("GSSD_NO_WGRAD_SLOT") != nullptr;   // ablation switches
-        const int rc = no_slot ? 1 : gssd_try_wgrad_slot(d, dy, dw_packed, as_stream(stream));   // large plain 1x1 / DCN contraction
+        const int rc = no_slot ? 1 : gssd_try_wgrad_slot(d, dy, dw_packed, c);   // large plain 1x1 / dense convs with taps / DCN contraction
         if (rc != 1) return rc;
     }
     WgradParams p;
@@ -313,11 +315,22 @@ extern "C" int gssd_conv2d_wgrad_f32(const gssd_conv_desc* dp, const float* dy, 
     GSSD_CHECK_ARG(M < (1ll << 31));
     p.M = (int)M;
     const int cout_g = d.Cout / d.groups;
-    hipStream_t s = as_stream(stream);
-    if (cout_g >= 128) return launch_wgrad<4, 2, 2>(p, s);      // 128 co x 128 k
-    if (cout_g >= 64) return launch_wgrad<4, 1, 4>(p, s);       // 64 co x 256 k
-    if (cout_g > 16) return launch_wgrad<1, 2, 2>(p, s);        // 32 co x 128 k
-    return launch_wgrad<1, 1, 4>(p, s);                         // 16 co x 256 k
+    if (cout_g >= 128) return launch_wgrad<4, 2, 2>(p, c);      // 128 co x 128 k
+    if (cout_g >= 64) return launch_wgrad<4, 1, 4>(p, c);       // 64 co x 256 k
+    if (cout_g > 16) return launch_wgrad<1, 2, 2>(p, c);        // 32 co x 128 k
+    return launch_wgrad<1, 1, 4>(p, c);                         // 16 co x 256 k
+}
+
+extern "C" int gssd_conv2d_wgrad_f32(const gssd_conv_desc* dp, const float* dy, float* dw_packed, gssd_stream_t stream) {
+    gssd_conv_ctx c{as_stream(stream)};
+    return wgrad_dispatch_f32(dp, dy, dw_packed, c);
+}
+
+extern "C" int gssd_conv2d_wgrad_kernel_name(const gssd_conv_desc* dp, const float* dy, const float* dw_packed, char* buf, int cap) {
+    GSSD_CHECK_ARG(buf != nullptr && cap > 0);
+    buf[0] = 0;
+    gssd_conv_ctx c{nullptr, buf, cap};
+    return wgrad_dispatch_f32(dp, dy, const_cast<float*>(dw_packed), c);     // (naming writes nothing through dw_packed: its alignment is read)
 }
 
 extern "C" int gssd_unpack_conv_weight_grad(const float* w_packed, float* w_oihw, int Cout, int cin_g, int KH, int KW,

@@ -12,7 +12,7 @@ void gssd_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// gssd_conv2d_kernel_name's sink (common.h): the whole name or an error, never a truncated one
+// the sink of gssd_conv2d_kernel_name / gssd_conv2d_wgrad_kernel_name (common.h): the whole name or an error, never a truncated one
 int gssd_name_kernel(const gssd_conv_ctx& c, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -20,7 +20,7 @@ int gssd_name_kernel(const gssd_conv_ctx& c, const char* fmt, ...) {
     va_end(ap);
     if (n >= 0 && n < c.cap) return GSSD_OK;
     if (c.cap > 0) c.name[0] = 0;
-    gssd_set_error("gssd_conv2d_kernel_name: the name needs %d bytes, the buffer holds %d", n + 1, c.cap);
+    gssd_set_error("kernel name query: the name needs %d bytes, the buffer holds %d", n + 1, c.cap);
     return GSSD_EINVAL;
 }
 

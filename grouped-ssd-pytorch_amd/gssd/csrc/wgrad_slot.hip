@@ -252,18 +252,19 @@ static int pick_split(int tiles, int nchunks) {
 }
 
 template <bool CONV>
-static int launch_ws(const WsParams& p, int groups, hipStream_t stream) {
+static int launch_ws(const WsParams& p, int groups, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "wgrad_slot<%s>", CONV ? "conv" : "gemm");
     static unsigned attr_mask = 0;
     constexpr int smem = LDS_FLOATS * (int)sizeof(float);
     auto kern = wgrad_slot_kernel<CONV>;
     if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
-    hipLaunchKernelGGL(kern, dim3(p.ntn * p.mtiles, groups, p.split), dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(p.ntn * p.mtiles, groups, p.split), dim3(256), smem, c.stream, p);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
 
 // returns 1 when the descriptor is not a shape this kernel takes (the caller falls through to conv_wgrad / the patch kernels)
-int gssd_try_wgrad_slot(const gssd_conv_desc& d, const float* dy, float* dw, hipStream_t stream) {
+int gssd_try_wgrad_slot(const gssd_conv_desc& d, const float* dy, float* dw, gssd_conv_ctx& c) {
     if (d.m_per_image) return 1;
     const long long R = (long long)d.B * d.Ho * d.Wo;
     if (R < 4096 || R >= (1ll << 31) || ((uintptr_t)dw % 16) != 0 || d.in_stride % 4 != 0 || d.in_ch_off % 4 != 0) return 1;
@@ -286,7 +287,7 @@ int gssd_try_wgrad_slot(const gssd_conv_desc& d, const float* dy, float* dw, hip
         // tile fill (ragged Cout / K tails waste MFMA work): stay on the generic kernel below 0.7
         if (((double)d.Cout / (p.mtiles * BM)) * ((double)d.K / (p.ntn * BN)) < 0.7) return 1;
         p.split = pick_split(p.ntn * p.mtiles, nchunks);
-        return launch_ws<false>(p, 1, stream);
+        return launch_ws<false>(p, 1, c);
     }
     // convolutions with taps (stride / dilation / padding; the group index is a grid dimension)
     // Dense layers only (the DCN offset conv: 1.75 -> 1.06 ms).  Measured and rejected for the grouped trunk layers: conv4_2 (4 groups x
@@ -303,5 +304,5 @@ int gssd_try_wgrad_slot(const gssd_conv_desc& d, const float* dy, float* dw, hip
     if (((double)cout_g / (p.mtiles * BM)) * ((double)d.K / (p.ntn * BN)) < 0.7) return 1;
     p.H = d.H; p.W = d.W; p.Ho = d.Ho; p.Wo = d.Wo; p.KW = d.KW; p.stride = d.stride; p.pad = d.pad; p.dil = d.dil;
     p.split = pick_split(p.ntn * p.mtiles * d.groups, nchunks);
-    return launch_ws<true>(p, d.groups, stream);
+    return launch_ws<true>(p, d.groups, c);
 }

@@ -302,11 +302,23 @@ def conv2d_nhwc(x, w_oihw, bias=None, stride=1, pad=0, dil=1, groups=1, relu=Fal
     return out
 
 
-def conv_wgrad(desc, dy, Cout, cin_g_real, k, cin_g_pad=None, out=None, accumulate=False):
-    """OIHW weight gradient of the conv described by ``desc`` for the dense NHWC output gradient ``dy``."""
+def conv_wgrad_kernel_name(desc, dy, dw):
+    """The kernel instance gssd_conv2d_wgrad_f32 would launch for (desc, dy, packed gradient dw): the dispatcher's own statement
+    (gssd_conv2d_wgrad_kernel_name walks the launch path; no device is touched, so host tensors will do).  Arguments the launch would
+    refuse raise GssdError."""
+    buf = C.create_string_buffer(64)
+    check(lib.gssd_conv2d_wgrad_kernel_name(C.byref(desc), _p(dy), _p(dw), buf, len(buf)))
+    return buf.value.decode()
+
+
+def conv_wgrad(desc, dy, Cout, cin_g_real, k, cin_g_pad=None, out=None, accumulate=False, packed=None):
+    """OIHW weight gradient of the conv described by ``desc`` for the dense NHWC output gradient ``dy``.  ``packed``: the caller's own
+    zero-filled [Cout][k * k * cin_g_pad] buffer for the launch to accumulate into (a caller that asks conv_wgrad_kernel_name about the
+    very pointers of the launch); by default one is allocated here."""
     cin_g_pad = cin_g_pad or desc.cin_g
     K = k * k * cin_g_pad
-    dwp = torch.zeros(Cout, K, device=dy.device, dtype=torch.float32)
+    dwp = torch.zeros(Cout, K, device=dy.device, dtype=torch.float32) if packed is None else packed
+    assert dwp.is_contiguous() and dwp.numel() == Cout * K and dwp.dtype == torch.float32
     check(lib.gssd_conv2d_wgrad_f32(C.byref(desc), _p(dy), _p(dwp), _stream()))
     if out is None:
         out = torch.empty(Cout, cin_g_real, k, k, device=dy.device, dtype=torch.float32)

@@ -295,6 +295,18 @@ int gssd_winograd_weight_f32(const float* w_packed, float* U, int Cout, int grou
  * Data gradient: a stride-1 conv's dgrad is a forward gssd_conv2d_nhwc_f32 over dy with the weights packed by
  * gssd_pack_conv_weight_dgrad (rows = input channels, k' = flipped tap * cout_g + co) and pad' = dil*(k-1) - pad. */
 int gssd_conv2d_wgrad_f32(const gssd_conv_desc* d, const float* dy, float* dw_packed, gssd_stream_t stream);
+/* Name of the kernel instance gssd_conv2d_wgrad_f32 would launch for (*d, dy, dw_packed), as a NUL-terminated string in buf[cap]: the
+ * contract of gssd_conv2d_kernel_name.  Makes no HIP runtime call, touches no device state and dereferences neither pointer (the
+ * validation and csrc/wgrad_slot.hip read their alignment).  Returns what the launch would return for arguments it refuses (GSSD_EINVAL,
+ * gssd_last_error set, buf empty), GSSD_OK otherwise; a name that does not fit cap is GSSD_EINVAL too, never a truncated name.  The
+ * name comes from the launch path itself -- validation, the chain thin -> patch -> slot -> generic tile, the switches GSSD_NO_GEMM_SLOT /
+ * GSSD_NO_WGRAD_SLOT -- which names the template instance it arrives at instead of launching it:
+ *   conv_wgrad<128x128>, <64x256>, <32x128>, <16x256>   output channels x im2col columns of a workgroup (the transform is a run-time branch)
+ *   conv_thin_wgrad<4>, <16>                             input channels per group
+ *   conv_patch_wgrad<ci,co>                              <16,32>, <32,32>, <32,64>, <64,64>
+ *   wgrad_slot<gemm>, wgrad_slot<conv>                   plain 1x1 / dense conv with taps
+ * conv_thin_wgrad and conv_patch_wgrad carry "/plain" when the instance has no fused input transform (d->in_scale == NULL). */
+int gssd_conv2d_wgrad_kernel_name(const gssd_conv_desc* d, const float* dy, const float* dw_packed, char* buf, int cap);
 /* The same weight gradient on the bf16 matrix cores (training step of the bf16 storage mode): d->in and dy are bf16 (dy [B*Ho*Wo][Cout]),
  * dw_packed is fp32 and zero-filled; a deferred BatchNorm + ReLU on the input (d->in_scale / d->in_shift, fp32) is applied to the staged
  * input in fp32 and rounded to bf16 like the forward does (d->in_pad is not read: out-of-image pixels are zero).  Shapes: the grouped 3x3

@@ -45,6 +45,14 @@ def assert_kernel(desc, want, bf16=False):
     assert got == want, f'this case runs {got}, not {want}'
 
 
+def assert_wgrad_kernel(desc, dy, dw, want):
+    """The weight-gradient dispatcher lands (``desc``, ``dy``, packed gradient ``dw``) on the kernel instance ``want``
+    (gssd_conv2d_wgrad_kernel_name on the launch's own pointers) -- asserted before the launch, like assert_kernel."""
+    from gssd import ops as _ops
+    got = _ops.conv_wgrad_kernel_name(desc, dy, dw)
+    assert got == want, f'this case runs {got}, not {want}'
+
+
 def nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 

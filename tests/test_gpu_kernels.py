@@ -106,8 +106,10 @@ def test_conv_fused_input_bn_relu(dev, ops, Cin, Cout, H, k, st, pd):
 
 @pytest.mark.parametrize('B,H,Cin,Cout,k,pd,dl', [(4, 38, 512, 512, 3, 1, 1), (12, 19, 512, 1024, 3, 6, 6), (4, 37, 1024, 512, 1, 0, 1)])
 def test_conv_wgrad_fused_input(dev, ops, B, H, Cin, Cout, k, pd, dl):
-    """Weight gradient of a conv that applies its producer's BatchNorm + ReLU on the fly (csrc/wgrad_slot.hip XF path for the wide
-    layers): d/dw of conv2d(relu(x * scale + shift)) with zero padding AFTER the transform."""
+    """Weight gradient of a conv that applies its producer's BatchNorm + ReLU on the fly: d/dw of conv2d(relu(x * scale + shift)) with zero
+    padding AFTER the transform.  All three cases run the generic kernel's 128 x 128 tile (128 / 256 channels per group; csrc/wgrad_slot.hip
+    refuses every descriptor with an input transform), where the transform is a run-time branch on the im2col operand.  The transform on the
+    other tiles and on the thin / patch-staged kernels: tests/test_gpu_wgrad_leaves.py."""
     rng = np.random.default_rng(B * 1000 + H)
     g = 4
     x = torch.from_numpy(rng.normal(0.1, 1.0, size=(B, Cin, H, H)).astype(np.float32))
@@ -125,7 +127,9 @@ def test_conv_wgrad_fused_input(dev, ops, B, H, Cin, Cout, k, pd, dl):
     keep = [nhwc(x).to(dev), sc.to(dev), sh.to(dev), pad.to(dev)]
     desc, _, _ = ops.make_conv_desc(keep[0], None, None, B=B, H=H, W=H, in_stride=Cin, cin_g=Cin // g, Cout=Cout, groups=g, k=k, stride=1,
                                     pad=pd, dil=dl, in_scale=keep[1], in_shift=keep[2], in_pad=keep[3])
-    dw = ops.conv_wgrad(desc, nhwc(dy).to(dev), Cout, Cin // g, k)
+    dyd, packed = nhwc(dy).to(dev), torch.zeros(Cout, k * k * (Cin // g), device=dev)
+    assert_wgrad_kernel(desc, dyd, packed, 'conv_wgrad<128x128>')
+    dw = ops.conv_wgrad(desc, dyd, Cout, Cin // g, k, packed=packed)
     assert rel(dw, w.grad) < TOL
 
 
@@ -210,36 +214,39 @@ def test_conv_winograd(dev, ops, case):
         assert want[3] is None
 
 
-# The comments describe the weight-gradient kernel of a case; its last element is the kernel instance of the data gradient's forward launch
-# (None: stride 2, no data gradient here; a pair: by default, with GSSD_THIN_X6=0).
+# A case ends in two kernel instances, each asserted before its launch: the data gradient's forward launch (gssd_conv2d_kernel_name; None:
+# stride 2, no data gradient here; a pair: by default, with GSSD_THIN_X6=0) and the weight gradient's (gssd_conv2d_wgrad_kernel_name).
+# The comments describe the weight-gradient kernel.  Every instance at its edges: tests/test_gpu_wgrad_leaves.py.
 BWD_CASES = [
     # B, H, Cin, Cout, k, s, p, d, groups
-    (2, 30, 64, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # cout_g 16 (scalar dY path)
-    (2, 21, 64, 128, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),     # cout_g 32
-    (2, 19, 128, 256, 3, 1, 1, 1, 4, 'conv_igemm<128x32>'),    # cout_g 64 (b128 path, 64 x 256 tile)
-    (2, 19, 512, 512, 3, 1, 1, 1, 4, 'conv_igemm<64x64>'),     # cout_g 128
-    (2, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_igemm<64x64>'),    # dilation 6
-    (2, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_igemm<64x64>'),   # grouped 1x1
-    (2, 19, 256, 512, 3, 2, 1, 1, 4, None),                    # stride 2 (wgrad only)
-    (2, 10, 512, 512, 1, 1, 0, 1, 1, 'conv_igemm<32x64>'),     # dense 1x1
-    (2, 10, 512, 36, 3, 1, 1, 1, 1, 'conv_igemm<32x64>'),      # head
-    (3, 33, 16, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # conv1_1: 4 (3 real) input channels per group
-    (2, 83, 16, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>'),      # thin patch-staged wgrad <4>, ragged tiles
-    (2, 80, 64, 64, 3, 1, 1, 1, 4, ('conv_thin_x6<16,16>/plain', 'conv_thin<16,16>')),      # thin wgrad <16>
-    (8, 38, 512, 512, 1, 1, 0, 1, 1, 'gemm_slot<128x128>'),    # large dense 1x1: slot-scheduled TN wgrad (csrc/wgrad_slot.hip) + NT dgrad (gemm_slot.hip)
-    (5, 37, 480, 120, 1, 1, 0, 1, 1, 'conv_igemm<128x64>'),    # ... ragged: 6845 pixels (reduction tail), 120 of 128 rows, 480 of 512 columns; its dgrad (480 outputs: 3.75 column tiles) stays generic
-    (4, 38, 512, 512, 3, 1, 1, 1, 4, 'conv_igemm<128x64>'),    # conv4_x: slot-scheduled TN wgrad with taps and groups (one tap per 128 columns)
-    (12, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_igemm<128x64>'),  # conv6: dilation 6, cout_g 256 (two row tiles per group)
-    (16, 38, 512, 512, 3, 2, 1, 1, 4, None),                   # stride 2 (wgrad only)
-    (4, 38, 512, 108, 3, 1, 1, 1, 1, 'conv_igemm<128x64>'),    # DCN offset conv: 108 of 128 rows, K = 4608
-    (12, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_igemm<128x64>'), # conv7: grouped 1x1
+    (2, 30, 64, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>', 'conv_wgrad<16x256>'),      # cout_g 16 (scalar dY path)
+    (2, 21, 64, 128, 3, 1, 1, 1, 4, 'conv_igemm<128x16>', 'conv_wgrad<32x128>'),     # cout_g 32
+    (2, 19, 128, 256, 3, 1, 1, 1, 4, 'conv_igemm<128x32>', 'conv_wgrad<64x256>'),    # cout_g 64 (b128 path, 64 x 256 tile)
+    (2, 19, 512, 512, 3, 1, 1, 1, 4, 'conv_igemm<64x64>', 'conv_wgrad<128x128>'),    # cout_g 128
+    (2, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_igemm<64x64>', 'conv_wgrad<128x128>'),   # dilation 6
+    (2, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_igemm<64x64>', 'conv_wgrad<128x128>'),  # grouped 1x1
+    (2, 19, 256, 512, 3, 2, 1, 1, 4, None, 'conv_wgrad<128x128>'),                   # stride 2 (wgrad only)
+    (2, 10, 512, 512, 1, 1, 0, 1, 1, 'conv_igemm<32x64>', 'conv_wgrad<128x128>'),    # dense 1x1 on a small map (200 rows: below the slot kernel's 4096)
+    (2, 10, 512, 36, 3, 1, 1, 1, 1, 'conv_igemm<32x64>', 'conv_wgrad<32x128>'),      # head
+    (3, 33, 16, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>', 'conv_wgrad<16x256>'),      # conv1_1's channels (4 per group) on a map below the thin kernel's 75 x 75
+    (2, 83, 16, 64, 3, 1, 1, 1, 4, 'conv_igemm<128x16>', 'conv_thin_wgrad<4>/plain'),      # thin patch-staged wgrad <4>, ragged tiles
+    (2, 80, 64, 64, 3, 1, 1, 1, 4, ('conv_thin_x6<16,16>/plain', 'conv_thin<16,16>'), 'conv_thin_wgrad<16>/plain'),      # thin wgrad <16>
+    (8, 38, 512, 512, 1, 1, 0, 1, 1, 'gemm_slot<128x128>', 'wgrad_slot<gemm>'),      # large dense 1x1: slot-scheduled TN wgrad (csrc/wgrad_slot.hip) + NT dgrad (gemm_slot.hip)
+    (5, 37, 480, 120, 1, 1, 0, 1, 1, 'conv_igemm<128x64>', 'wgrad_slot<gemm>'),      # ... ragged: 6845 pixels (reduction tail), 120 of 128 rows, 480 of 512 columns; its dgrad (480 outputs: 3.75 column tiles) stays generic
+    # grouped layers never take the slot kernel (its conv form asks for groups == 1: measured and rejected for the grouped trunk, see
+    # gssd_try_wgrad_slot), and 128 / 256 channels per group are not a patch-staged shape: the generic 128 x 128 tile at workload-like sizes
+    (4, 38, 512, 512, 3, 1, 1, 1, 4, 'conv_igemm<128x64>', 'conv_wgrad<128x128>'),   # conv4_x: 5776 pixels, K = 1152 = 9 column tiles
+    (12, 19, 512, 1024, 3, 1, 6, 6, 4, 'conv_igemm<128x64>', 'conv_wgrad<128x128>'), # conv6: dilation 6, cout_g 256 (two row tiles per group)
+    (16, 38, 512, 512, 3, 2, 1, 1, 4, None, 'conv_wgrad<128x128>'),                  # stride 2 (wgrad only)
+    (4, 38, 512, 108, 3, 1, 1, 1, 1, 'conv_igemm<128x64>', 'wgrad_slot<conv>'),      # DCN offset conv (dense): the slot kernel's conv form, 108 of 128 rows, K = 4608
+    (12, 19, 1024, 1024, 1, 1, 0, 1, 4, 'conv_igemm<128x64>', 'conv_wgrad<128x128>'),      # conv7: grouped 1x1
 ]
 
 
 @pytest.mark.parametrize('case', BWD_CASES)
 def test_conv_backward(dev, ops, case):
     """wgrad kernel and dgrad-as-forward-conv against CPU autograd."""
-    B, H, Cin, Cout, k, s, p, d, g, want = case
+    B, H, Cin, Cout, k, s, p, d, g, want, want_wgrad = case
     rng = np.random.default_rng(hash(case[:9]) % (2 ** 31))
     x = torch.from_numpy(rng.normal(size=(B, Cin, H, H)).astype(np.float32)).requires_grad_()
     w = torch.from_numpy(rng.normal(0, 0.1, size=(Cout, Cin // g, k, k)).astype(np.float32)).requires_grad_()
@@ -249,7 +256,9 @@ def test_conv_backward(dev, ops, case):
     xd, dyd = nhwc(x.detach()).to(dev), nhwc(dy).to(dev)
     desc, _, _ = ops.make_conv_desc(xd, None, None, B=B, H=H, W=H, in_stride=Cin, cin_g=Cin // g, Cout=Cout, groups=g, k=k,
                                     stride=s, pad=p, dil=d)
-    dw = ops.conv_wgrad(desc, dyd, Cout, Cin // g, k)
+    packed = torch.zeros(Cout, k * k * (Cin // g), device=dev)
+    assert_wgrad_kernel(desc, dyd, packed, want_wgrad)
+    dw = ops.conv_wgrad(desc, dyd, Cout, Cin // g, k, packed=packed)
     assert rel(dw, w.grad) < TOL
     if s == 1:
         wd = ops.pack_weight_dgrad(w.detach().to(dev), g)

@@ -191,6 +191,9 @@ SIGNATURES = {
     'gssd_self_attn_flash_bwd_f32_supported': (c_i, [c_i, c_i]),
     'gssd_self_attn_flash_bwd_f32': (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i,
                                            c_i, c_fp]),
+    'gssd_self_attn_core_any_f32': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp]),
+    'gssd_self_attn_flash_bwd_any_f32': (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i,
+                                               c_i, c_i, c_fp]),
     'gssd_eval_match': (c_i, [c_fp, C.c_longlong, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_d, c_fp, c_i, c_i, c_fp, c_fp, c_fp]),
     'gssd_eval_workspace_bytes': (C.c_longlong, [c_i]),
     'gssd_eval_ap': (c_i, [c_fp, c_fp, c_i, c_i, c_d, c_i, c_fp, C.c_longlong, c_fp, c_fp]),

@@ -51,7 +51,9 @@ class SNConv1x1(nn.Module):
 
 
 class Self_Attn(nn.Module):
-    """layers/self_attn.py:29-89 (state only; ``GssdEngine`` runs it)."""
+    """layers/self_attn.py:29-89.  Inside build_ssd / PixelLink ``GssdEngine`` runs it; ``forward`` is the standalone, differentiable
+    block (gssd/self_attn_op.py) for any ``in_channels`` that is a multiple of 8 up to 2048, any square map and any
+    ``max_pool_factor``."""
 
     def __init__(self, in_channels, max_pool_factor=1):
         super().__init__()
@@ -62,6 +64,13 @@ class Self_Attn(nn.Module):
         self.snconv1x1_attn = SNConv1x1(in_channels // 2, in_channels)
         self.sigma = nn.Parameter(torch.zeros(1))
         self.max_pool_factor = max_pool_factor
+
+    def forward(self, x, return_attn_map=False):
+        """NCHW fp32 on the device in; (out, sigma * attn_g) or, with ``return_attn_map``, (out, sigma * attn_g, attn) with attn
+        [B, H*H, Nk], Nk = max(H // max_pool_factor, 1) ** 2.  ``attn`` is not differentiable (nothing in the reference differentiates
+        its map); in train mode one power iteration updates ``weight_u`` / ``weight_v`` in place, also under ``torch.no_grad()``."""
+        from .self_attn_op import self_attn_forward
+        return self_attn_forward(self, x, return_attn_map)
 
 
 def _pair(v):

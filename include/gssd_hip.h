@@ -862,6 +862,20 @@ int gssd_self_attn_flash_bwd_f32(const float* tp, int qstride, const float* keys
                                  const float* lse, const float* dvec, float* dq, int ld_q, float* dk, float* dv, int ld_kv, int B, int N, int Nk,
                                  int D, int C2, gssd_stream_t stream);
 
+/* The same two entries for ANY width (csrc/sa_any.hip; the standalone Self_Attn module, gssd/self_attn_op.py): D and C2 multiples of 4
+ * with 4 <= D <= 256 and 4 <= C2 <= 1024 (real widths that are not are carried with zero pad channels), every row stride a multiple of
+ * 4 floats, every pointer 16-byte aligned; anything else is GSSD_EINVAL before any launch.
+ * gssd_self_attn_core_any_f32: the contract of gssd_self_attn_core_kv_f32 with fp32 output (tp [B][N][2 D], kp rows of kstride floats,
+ * gT [B][C2][Nkp] with zero pad columns, out [B][N][C2], lse optional).  The kernel of the specialised entry at the D bucket {16, 32, 64,
+ * 128, 256} that holds D, one launch per slice of 256 value channels.
+ * gssd_self_attn_flash_bwd_any_f32: the contract of gssd_self_attn_flash_bwd_f32; all five products on the fp32 matrix cores, two
+ * launches, no atomics (bit-reproducible), no map.  Columns beyond D / C2 of the ld_q / ld_kv-wide rows are not written. */
+int gssd_self_attn_core_any_f32(const float* tp, const float* kp, const float* gT, float* out, int B, int N, int Nk, int Nkp, int D, int C2,
+                                int kstride, float* lse, gssd_stream_t stream);
+int gssd_self_attn_flash_bwd_any_f32(const float* tp, int qstride, const float* keys, int krow, const float* gT, int Nkp, const float* dag,
+                                     const float* lse, const float* dvec, float* dq, int ld_q, float* dk, float* dv, int ld_kv, int B, int N,
+                                     int Nk, int D, int C2, gssd_stream_t stream);
+
 /* The fp32 Self_Attn core on the BF16 matrix cores with fp32-equivalent products (csrc/flash_attn_x6.hip; layers/self_attn.py:68-80): the
  * contract of gssd_self_attn_core_f32 (tp [B][N][2D] fp32 theta | phi, gT [B][C2][Np] fp32, out [B][N][C2] fp32, optional lse [B][N]) with both
  * products as six v_mfma_f32_16x16x32_bf16 over operands split into three bf16 planes.  `ws`: gssd_self_attn_core_x6_ws_bytes(B, N, D, C2) bytes

@@ -24,6 +24,19 @@
 //     registers instead of 64 NBT accumulators;
 //   * per block two barriers: A -- the block's planes are in LDS and its U planes have landed; B -- the consumers hold the planes in registers,
 //     the producers may write the next block's.  U stages (4 xi x 3 planes x NB x 32 bf16) are double buffered.
+//
+// The PAIRED form (conv_wino_x6_kernel<.., PAIR = true>; two-plane fp16 launches with the plain / stats epilogue and an even number of 64-channel output blocks
+// per group: conv4_x): the producers' work does not depend on the output block, so one workgroup owns 64 tiles and TWO adjacent blocks (cb, cb + 1).
+// Producers run exactly as above; the consumers read a block's operand planes once and run the block's MFMAs and fold twice, HALF 0 against the U
+// stage of output block cb (LDS slot 0), then half 1 against that of cb + 1 (slot 1), strictly one after the other (one half's products live at a
+// time: 2 x 64 output registers + 32 of planes leave no room for more).  A third barrier per block, M, between the halves and executed by all eight
+// waves, is what lets two U stages do: behind A every wave has left the previous block's half 1, so half 0 streams this block's half-1 stage into
+// slot 1; behind M every wave has left half 0, so half 1 streams the next block's half-0 stage into slot 0 (a ring of three stages without M
+// would need a fourth: both stages of a block have to land before its A while both of the previous block are still read).  Per output element the
+// products, the chunk order and the fold order are those of the unpaired form: raw outputs are bit-identical.  Registers (256 per wave): 128 of
+// outputs, 32 of planes, weight fragments one xi at a time (24), each product folded into the row sums as it arrives -- and the batch sums in LDS
+// (32 floats per consumer thread behind the planes, touched once per item: LDS 64 + 32 + 32 = 128 KB).  The batch sums regroup their fp32
+// partial sums (a workgroup owns other items, a lane adds its tile pair r, r ^ 8 per item).  GSSD_WINO_X6_PAIR=0: unpaired.
 #include "common.h"
 #include "kernel_util.h"
 #include <cstdlib>
@@ -31,6 +44,9 @@
 #ifndef WX6_KO
 #define WX6_KO 0              // knock-outs (scripts/wino_x6_knockout.sh; results wrong by construction): 1 no vector work (transform / split), 2 no MFMAs,
 #endif                        // 4 no U DMA, 8 no patch loads, 16 no fragment reads
+#ifndef WX6_UR
+#define WX6_UR 3              // paired form: ring of weight-fragment sets (one xi each), WX6_UR - 1 ahead of their MFMAs
+#endif
 #ifndef WX6_LOCAL_SUM
 #define WX6_LOCAL_SUM 1       // the six products of a chunk are summed from zero and added to the running sum by the vector ALU (the bf16 MFMA's
 #endif                        // adder truncates: conv_x6.hip)
@@ -72,8 +88,11 @@ struct Step {                // a step = one 32-channel chunk of one item + the 
 };
 
 // PSEL: out-of-image patch positions are replaced by the padding value with a select (else: the loads already fetched it, WinoX6Params::pad_off)
-template <int NBT, bool XF, int EPI, bool PSEL, bool F16>      // NB = 16 NBT output channels per workgroup; EPI: 0 plain, 1 + residual, 2 pooled raw map (GSSD_CONV_POOL2)
+// PAIR: the paired form (two output blocks per workgroup, see the top of the file)
+template <int NBT, bool XF, int EPI, bool PSEL, bool F16, bool PAIR = false>      // NB = 16 NBT output channels per workgroup and half; EPI: 0 plain, 1 + residual, 2 pooled raw map (GSSD_CONV_POOL2)
 __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params p) {
+    static_assert(!PAIR || (F16 && EPI == 0 && NBT == 4), "the paired form: two-plane fp16, plain / stats epilogue, 64-channel blocks");
+    constexpr int NH = PAIR ? 2 : 1;                                 // output blocks (halves) of a workgroup
     constexpr int NPX = F16 ? 2 : 3;                                 // operand planes of this instance
     constexpr int NB = 16 * NBT, TILE = NB * 32, STAGE = XG * NPX * TILE, CHUNK = 16 * NPX * TILE;
     constexpr int PWAVE = XG * NPX * 512;                             // u16 elements of one tile group's planes of a block: [xi][plane][lane][8]
@@ -89,14 +108,15 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
     // flat grid: workgroup id = pair + npairs * x.  Ids go round-robin over the 8 XCDs (each with its own L2): the workgroups that stream the
     // U planes of one (group, output block) pair share an XCD (npairs a multiple of 8) or two
     const int pair = blockIdx.x % p.npairs, bx = blockIdx.x / p.npairs;
-    const int g = pair / p.ncb, cb = pair - g * p.ncb;
+    const int ncbp = PAIR ? p.ncb >> 1 : p.ncb;                       // (paired: npairs = groups * ncb / 2, a pair = blocks cb, cb + 1)
+    const int g = pair / ncbp, cb = (pair - g * ncbp) * NH;
     const int n0 = cb * NB;
     const int item_begin = (int)(((long long)bx * nitems) / p.gx);
     const int item_end = (int)(((long long)(bx + 1) * nitems) / p.gx);
     if (item_begin >= item_end) return;
 
     const int cb_ld = p.in_ch_off + g * p.cin_g + kq * 4;            // + chunk * 32 + half * 16
-    const u16* Ug = p.Ux + (size_t)pair * p.nchunks * CHUNK + lane * 8;
+    const u16* Ug = p.Ux + (size_t)(PAIR ? g * p.ncb + cb : pair) * p.nchunks * CHUNK + lane * 8;      // (block cb + 1: nchunks * CHUNK further)
     const int nchunks = p.nchunks;
     const bool tailB = (p.cin_g & 31) != 0;                           // the last chunk has one 16-channel half only
     const int nsteps = (item_end - item_begin) * nchunks;            // a step = one 32-channel chunk of one item = four blocks
@@ -242,6 +262,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
             __builtin_amdgcn_s_barrier();                 // B
             put_planes(P);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (PAIR) __builtin_amdgcn_s_barrier();       // M: the consumers' barrier between the halves of the block that is running
             __builtin_amdgcn_s_barrier();                 // A
         };
         Step cur;
@@ -297,22 +318,32 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
         }
     } else {
         // =============================== consumer: U planes by LDS-DMA, MFMAs, output transform, epilogue =========================================
-        f32x4 Y[2][2][NBT];
+        f32x4 Yh[NH][2][2][NBT];
 #pragma unroll
-        for (int a = 0; a < 2; ++a)
+        for (int h = 0; h < NH; ++h)
 #pragma unroll
-            for (int b = 0; b < 2; ++b)
+            for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int nb = 0; nb < NBT; ++nb) Y[a][b][nb] = zero4;
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int nb = 0; nb < NBT; ++nb) Yh[h][a][b][nb] = zero4;
+        f32x4 (&Y)[2][2][NBT] = Yh[0];
+        // batch sums of this lane's tile.  Paired: of the tile pair r, r ^ 8 -- tile lanes 0-7 keep half 0's, 8-15 half 1's -- and in LDS, a column of
+        // 8 NBT floats per consumer thread behind the planes (value (nb, j): sum at 2 (4 nb + j), sum of squares behind it): touched once per item,
+        // and the 32 registers they would take are the second half's outputs
         f32x4 ssum[NBT], ssq[NBT];
 #pragma unroll
         for (int nb = 0; nb < NBT; ++nb) ssum[nb] = ssq[nb] = zero4;
+        float* const sacc = reinterpret_cast<float*>(Pl + 4 * PWAVE) + (tid - 256);
+        if (PAIR)
+#pragma unroll
+            for (int v = 0; v < 8 * NBT; ++v) sacc[v * 256] = 0.f;
         const bool vec = ((p.out_stride | p.out_ch_off | p.cout_g) & 3) == 0 && p.vec_ok;
         const int fo = r * 32 + ((kq ^ swz64(r)) << 3);          // fragment offset inside a 16-row block of a tile
         // U planes of (chunk c, Winograd row i) -> LDS slot: XG * NPX * TILE / 512 pieces of 1 KB, consumer wave w moves pieces w, w + 4, ..
-        auto stage_U_part = [&](const int c, const int i, const int slot, const int part) {      // part of NBT (-1: all)
+        auto stage_U_part = [&](const int c, const int i, const int slot, const int part, const int half = 0) {      // part of NBT (-1: all)
             if (WX6_KO & 4) return;
-            const u16* src = Ug + (size_t)c * CHUNK + i * STAGE;
+            const u16* src = Ug + (size_t)(PAIR ? half * nchunks + c : c) * CHUNK + i * STAGE;
             u16* dst = smem + slot * STAGE;
             constexpr int PW = STAGE / 512 / 4;       // pieces per consumer wave
 #pragma unroll
@@ -324,27 +355,37 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
         };
         auto stage_U = [&](const int c, const int i, const int slot) { stage_U_part(c, i, slot, -1); };
     auto epilogue = [&](int item) {
-            // lane (r, kq) holds Y[a][b] of channels n0 + nb*16 + 4*kq + j of tile r (conv_wino.hip's epilogue)
+            // lane (r, kq) holds Y[a][b] of channels n0 + nb*16 + 4*kq + j of tile r (conv_wino.hip's epilogue); paired: half 1's 16-channel tiles
+            // follow half 0's (hn = NBT half + nb: channels n0 + hn*16 + ..)
             const int t = (item * 4 + wv) * 16 + r;
-            if (t < p.ntiles) {
+            // (paired: every lane walks the tile, stores and sums predicated -- the sums of tile r and tile r ^ 8 meet by a row rotation below)
+            const bool live = t < p.ntiles;
+            // (paired: no register is left for what the compiler would keep across the blocks for this place -- the reciprocals of the two
+            // divisions, the lane's channel offset: hidden from it here, they are made again per item)
+            int tiles_per_img = p.tiles_y * p.tiles_x, tiles_x = p.tiles_x, kq = lane >> 4;
+            if (PAIR) asm volatile("" : "+s"(tiles_per_img), "+s"(tiles_x), "+v"(kq));
+            if (PAIR || live) {
                 const int b = t / tiles_per_img, rem = t - b * tiles_per_img;
-                const int ty = rem / p.tiles_x, tx = rem - ty * p.tiles_x;
+                const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
                 const int y = 2 * ty, x = 2 * tx;
                 const bool y1 = y + 1 < p.H, x1 = x + 1 < p.W;
                 const int ch0 = g * p.cout_g + n0 + kq * 4;
-                const size_t o00 = EPI == 2 ? ((size_t)(b * p.tiles_y + ty) * p.tiles_x + tx) * p.out_stride + p.out_ch_off + ch0
+                const size_t o00 = EPI == 2 ? ((size_t)(b * p.tiles_y + ty) * tiles_x + tx) * p.out_stride + p.out_ch_off + ch0
                                             : ((size_t)(b * p.H + y) * p.W + x) * p.out_stride + p.out_ch_off + ch0;
 #pragma unroll
-                for (int nb = 0; nb < NBT; ++nb) {
-                    const int nrem = p.cout_g - (n0 + nb * 16 + kq * 4);      // channels of this quad that exist (zero rows of U beyond)
+                for (int hn = 0; hn < NH * NBT; ++hn) {
+                    const int half = hn / NBT, nb = hn % NBT;
+                    f32x4 (&Y)[2][2][NBT] = Yh[half];
+                    const int nrem = p.cout_g - (n0 + hn * 16 + kq * 4);      // channels of this quad that exist (zero rows of U beyond)
                     if (nrem <= 0) continue;
+                    f32x4 ls = zero4, lq = zero4;                         // paired: this item's and half's sums of the lane's tile
                     f32x4 bia = zero4;
                     if (p.bias) {
-                        if (vec && nrem >= 4) bia = *reinterpret_cast<const f32x4*>(p.bias + ch0 + nb * 16);
+                        if (vec && nrem >= 4) bia = *reinterpret_cast<const f32x4*>(p.bias + ch0 + hn * 16);
                         else
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
-                                if (j < nrem) bia[j] = p.bias[ch0 + nb * 16 + j];
+                                if (j < nrem) bia[j] = p.bias[ch0 + hn * 16 + j];
                     }
                     f32x4 v[2][2];
 #pragma unroll
@@ -352,9 +393,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
 #pragma unroll
                         for (int c2 = 0; c2 < 2; ++c2) v[a][c2] = Y[a][c2][nb] + bia;
                     // (GSSD_OUT_HEADS: this quad of channels lies on one side of split_n -- both sides are multiples of four)
-                    const int nq = n0 + nb * 16 + kq * 4;
-                    float* const obase = (p.heads && nq >= p.split_n) ? p.out_b : p.out;
+                    const int nq = n0 + hn * 16 + kq * 4;
+                    float* const obase = (!PAIR && p.heads && nq >= p.split_n) ? p.out_b : p.out;
                     auto put = [&](size_t o, const f32x4& val) {
+                        if (PAIR && !live) return;
                         if (vec && nrem >= 4) *reinterpret_cast<f32x4*>(obase + o) = val;
                         else
 #pragma unroll
@@ -378,23 +420,23 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
                                 }
                             }
                         f32x4 sgn = f32x4{1.f, 1.f, 1.f, 1.f};
-                        if (vec && nrem >= 4) sgn = *reinterpret_cast<const f32x4*>(p.pool_sign + ch0 + nb * 16);
+                        if (vec && nrem >= 4) sgn = *reinterpret_cast<const f32x4*>(p.pool_sign + ch0 + hn * 16);
                         else
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
-                                if (j < nrem) sgn[j] = p.pool_sign[ch0 + nb * 16 + j];
+                                if (j < nrem) sgn[j] = p.pool_sign[ch0 + hn * 16 + j];
                         f32x4 res;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) res[j] = sgn[j] >= 0.f ? mx[j] : mn[j];
-                        put(o00 + nb * 16, res);
+                        put(o00 + hn * 16, res);
                     } else {
 #pragma unroll
                         for (int a = 0; a < 2; ++a)
 #pragma unroll
                             for (int c2 = 0; c2 < 2; ++c2) {
                                 if ((a == 1 && !y1) || (c2 == 1 && !x1)) continue;
-                                size_t o = o00 + nb * 16 + ((size_t)a * p.W + c2) * p.out_stride;
-                                if (p.heads) {
+                                size_t o = o00 + hn * 16 + ((size_t)a * p.W + c2) * p.out_stride;
+                                if (!PAIR && p.heads) {
                                     const size_t pix = (size_t)(y + a) * p.W + x + c2;
                                     o = nq < p.split_n ? (size_t)b * p.out_bs + p.out_off + pix * p.split_n + nq
                                                        : (size_t)b * p.outb_bs + p.outb_off + pix * (p.Cout - p.split_n) + (nq - p.split_n);
@@ -410,19 +452,43 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
                                 put(o, val);
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) {
-                                    ssum[nb][j] += val[j];
-                                    ssq[nb][j] = __builtin_fmaf(val[j], val[j], ssq[nb][j]);
+                                    if constexpr (PAIR) {
+                                        ls[j] += val[j];
+                                        lq[j] = __builtin_fmaf(val[j], val[j], lq[j]);
+                                    } else {
+                                        ssum[nb][j] += val[j];
+                                        ssq[nb][j] = __builtin_fmaf(val[j], val[j], ssq[nb][j]);
+                                    }
                                 }
                             }
+                    }
+                    if constexpr (PAIR) {
+                        // tile r + tile r ^ 8 (same kq: both lanes are here) by a row rotation; the tile-lane half that keeps this output half adds it
+                        const bool mine = (r >> 3) == half;
+                        auto ror8 = [](float x) {
+                            return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false));
+                        };
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float ts = live ? ls[j] : 0.f, tq = live ? lq[j] : 0.f;
+                            const float ps = ts + ror8(ts), pq = tq + ror8(tq);
+                            if (mine) {
+                                sacc[(2 * (4 * nb + j) + 0) * 256] += ps;
+                                sacc[(2 * (4 * nb + j) + 1) * 256] += pq;
+                            }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);      // (one output tile at a time: interleaved, the four overflow the registers)
                     }
                 }
             }
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+            for (int h = 0; h < NH; ++h)
 #pragma unroll
-                for (int b2 = 0; b2 < 2; ++b2)
+                for (int a = 0; a < 2; ++a)
 #pragma unroll
-                    for (int nb = 0; nb < NBT; ++nb) Y[a][b2][nb] = zero4;
+                    for (int b2 = 0; b2 < 2; ++b2)
+#pragma unroll
+                        for (int nb = 0; nb < NBT; ++nb) Yh[h][a][b2][nb] = zero4;
         };
 
         // the four xi of Winograd row I: 24 NBT MFMAs from the row's planes and LDS slot `slot`, folded into the 2 x 2 outputs right away
@@ -509,14 +575,96 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
+        // paired form: Winograd row I of chunk c, the planes once, then half 0 (U stage in slot 0) and half 1 (slot 1).  Weight fragments come one
+        // xi (NPX reads) at a time, two ahead of their MFMAs, through a ring of three: a whole output tile ahead (the unpaired form) costs 64
+        // registers that the second half's outputs need
+        auto run_row_pair = [&](const int I, const int c, const int c_next, const int i_next) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of (block, half 0) have landed
+            __builtin_amdgcn_s_barrier();                 // A
+            bf16x8 Pc[4][NPX];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int q = 0; q < NPX; ++q) Pc[j][q] = *reinterpret_cast<const bf16x8*>(Pr + (j * NPX + q) * 512);
+            constexpr int UR = WX6_UR, UA = UR - 1, NK = NBT * XG;          // k = nb * XG + xl
+            bf16x8 u[UR][NPX];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const u16* ub = smem + h * STAGE + fo;
+                auto frag = [&](const int k) {
+#pragma unroll
+                    for (int q = 0; q < NPX; ++q)
+                        u[k % UR][q] = *reinterpret_cast<const bf16x8*>(ub + ((k % XG) * NPX + q) * TILE + (k / XG) * 16 * 32);
+                };
+                if (h == 1) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of (block, half 1)
+                    __builtin_amdgcn_s_barrier();         // M: everyone's have landed, and slot 0 is free for the next block's half 0
+                }
+#pragma unroll
+                for (int k = 0; k < UA; ++k) frag(k);
+                if (h == 0) {
+                    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(UA * NPX) : "memory");      // (LDS returns in order: the planes are in registers)
+                    __builtin_amdgcn_s_barrier();         // B: the plane buffer is free for the next block
+                }
+#pragma unroll
+                for (int nb = 0; nb < NBT; ++nb) {
+                    if (h == 0) stage_U_part(c, I, 1, nb, 1);
+                    else stage_U_part(c_next, i_next, 0, nb, 0);
+                    // (s0 = m0 + m1 + m2, s1 = m1 - m2 - m3 in the unpaired form's order of additions, each m folded as it arrives)
+                    f32x4 s0v, s1v;
+#pragma unroll
+                    for (int xl = 0; xl < XG; ++xl) {
+                        const int k = nb * XG + xl;
+                        if (k + UA < NK) frag(k + UA);
+                        const bf16x8 (&uc)[NPX] = u[k % UR];
+                        f32x4 s6 = zero4, sx = zero4;             // h h' from zero; h l' + l' h' from zero, entering with 1 / 2048
+                        if (!(WX6_KO & 2)) {
+                            sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[1]), __builtin_bit_cast(f16x8, Pc[xl][0]), sx, 0, 0, 0);
+                            sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][1]), sx, 0, 0, 0);
+                            s6 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][0]), s6, 0, 0, 0);
+                        }
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) s6[e] = __builtin_fmaf(sx[e], 1.f / 2048.f, s6[e]);
+                        if (xl == 0) s0v = s6;
+                        if (xl == 1) s0v += s6, s1v = s6;
+                        if (xl == 2) s0v += s6, s1v -= s6;
+                        if (xl == 3) s1v -= s6;
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float s0 = s0v[e], s1 = s1v[e];
+                        if (I < 3) {
+                            Yh[h][0][0][nb][e] += s0;
+                            Yh[h][0][1][nb][e] += s1;
+                        }
+                        if (I == 1) {
+                            Yh[h][1][0][nb][e] += s0;
+                            Yh[h][1][1][nb][e] += s1;
+                        }
+                        if (I >= 2) {
+                            Yh[h][1][0][nb][e] -= s0;
+                            Yh[h][1][1][nb][e] -= s1;
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        };
         int item = item_begin, c = 0;
         stage_U(0, 0, 0);
         for (int s = 0; s < nsteps; ++s) {
             const int cn = c + 1 == nchunks ? 0 : c + 1;          // the next step's chunk (past the end: harmless)
-            run_row(0, 0, c, 3);
-            run_row(3, 1, c, 1);
-            run_row(1, 0, c, 2);
-            run_row(2, 1, cn, 0);
+            if constexpr (PAIR) {
+                run_row_pair(0, c, c, 3);
+                run_row_pair(3, c, c, 1);
+                run_row_pair(1, c, c, 2);
+                run_row_pair(2, c, cn, 0);
+            } else {
+                run_row(0, 0, c, 3);
+                run_row(3, 1, c, 1);
+                run_row(1, 0, c, 2);
+                run_row(2, 1, cn, 0);
+            }
             if (c == nchunks - 1) {
                 epilogue(item);
                 ++item;
@@ -526,14 +674,34 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the DMA past the end)
         __builtin_amdgcn_s_barrier();                         // A of the block past the end (the producers' last hand-over); they exit behind it
         if (p.stats) {                                        // one flush per workgroup: 16 tile lanes of a kq -> LDS over waves -> fp64 atomics
+            int tid = threadIdx.x;                            // (paired: made again from the thread id, as in the epilogue)
+            if (PAIR) asm volatile("" : "+v"(tid));
+            const int r = tid & 15, kq = (tid >> 4) & 3;
             // (only the four consumer waves are left: the barriers below count the waves that have not ended)
-            float* red = reinterpret_cast<float*>(smem);      // [4 waves][NB][2]
+            float* red = reinterpret_cast<float*>(smem);      // [4 waves][NH * NB][2]
             float fs[4 * NBT], fq[4 * NBT];                   // value index i: channel n0 + 16 * (i >> 2) + 4 * kq + (i & 3)
 #pragma unroll
             for (int i = 0; i < 4 * NBT; ++i) {
-                fs[i] = ssum[i >> 2][i & 3];
-                fq[i] = ssq[i >> 2][i & 3];
+                fs[i] = PAIR ? sacc[(2 * i + 0) * 256] : ssum[i >> 2][i & 3];
+                fq[i] = PAIR ? sacc[(2 * i + 1) * 256] : ssq[i >> 2][i & 3];
             }
+            if constexpr (PAIR) {
+                // tile lanes 0-7 hold half 0's sums, 8-15 half 1's: butterfly over each group of eight, its first lane writes the 4 NBT values
+#pragma unroll
+                for (int w = 4; w >= 1; w >>= 1)
+#pragma unroll
+                    for (int i = 0; i < 4 * NBT; ++i) {
+                        fs[i] += __shfl_xor(fs[i], w, 64);
+                        fq[i] += __shfl_xor(fq[i], w, 64);
+                    }
+                if ((r & 7) == 0)
+#pragma unroll
+                    for (int i = 0; i < 4 * NBT; ++i) {
+                        const int ch = (r >> 3) * NB + (i >> 2) * 16 + kq * 4 + (i & 3);
+                        red[(wv * 2 * NB + ch) * 2 + 0] = fs[i];
+                        red[(wv * 2 * NB + ch) * 2 + 1] = fq[i];
+                    }
+            } else {
             // halving exchange over the 16 tile lanes: lane r ends with value index r & (4 NBT - 1)
 #pragma unroll
             for (int w = 8; w >= 1; w >>= 1) {
@@ -558,15 +726,16 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
                     red[(wv * NB + (vi >> 2) * 16 + kq * 4 + (vi & 3)) * 2 + 1] = fq[0];
                 }
             }
+            }
             __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0)
             __builtin_amdgcn_s_barrier();
             const int ct = tid - 256;
-            if (ct < NB && n0 + ct < p.cout_g) {
+            if (ct < NH * NB && n0 + ct < p.cout_g) {
                 double s = 0.0, q = 0.0;
 #pragma unroll
                 for (int w = 0; w < 4; ++w) {
-                    s += (double)red[(w * NB + ct) * 2 + 0];
-                    q += (double)red[(w * NB + ct) * 2 + 1];
+                    s += (double)red[(w * NH * NB + ct) * 2 + 0];
+                    q += (double)red[(w * NH * NB + ct) * 2 + 1];
                 }
                 const int n = g * p.cout_g + n0 + ct;
                 double* st = gssd_stats_replica(p.stats, p.stats_rep, p.Cout);
@@ -575,6 +744,15 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
             }
         }
     }
+}
+
+// GSSD_WINO_X6_PAIR=0: no launch takes the paired form (A/B, tests); read once
+bool wx6_pair_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("GSSD_WINO_X6_PAIR");
+        return !e || atoi(e) != 0;
+    }();
+    return on;
 }
 
 // output-channel block of a layer
@@ -644,7 +822,8 @@ __global__ void wino_x6_weight_kernel(const float* __restrict__ w, u16* __restri
 template <int NBT, bool XF, int EPI, bool PSEL, bool F16>
 int launch_wino_x6_impl(const gssd_conv_desc& d, const u16* Ux, gssd_conv_ctx& c) {
     constexpr int NB = 16 * NBT, NPX = F16 ? 2 : 3;
-    // (one name per tile, fused input transform and pooled epilogue; the plane format and the padding form are not part of it)
+    // (one name per tile, fused input transform and pooled epilogue; the plane format, the padding form and the paired form are not part of it:
+    // <64> is the column block of a U stage and of one pass of MFMAs, which the paired form runs twice per workgroup)
     if (c.name) return gssd_name_kernel(c, "conv_wino_x6<%d>%s%s", NB, XF ? "" : "/plain", EPI == 2 ? "/pool2" : "");
     WinoX6Params p;
     p.in = d.in;
@@ -685,10 +864,27 @@ int launch_wino_x6_impl(const gssd_conv_desc& d, const u16* Ux, gssd_conv_ctx& c
     if (p.heads) p.vec_ok = p.vec_ok && (((uintptr_t)d.out_b & 15) == 0) && ((d.out_batch_stride | d.outb_batch_stride | d.out_off | d.outb_off | d.split_n | (d.Cout - d.split_n)) & 3) == 0;
     p.pad_off = PSEL ? 0u : wx6_pad_off(d);
     constexpr size_t smem = (2 * (size_t)XG * NPX * NB * 32 + 4 * (size_t)XG * NPX * 512) * sizeof(u16);      // two U stages + the planes of a block
+    const int nitems = (p.ntiles + 63) / 64;
+    if constexpr (NBT == 4 && EPI == 0 && F16) {
+        // the paired form: two adjacent output blocks per workgroup (U of block cb + 1 lies where gssd_wino_x6_pack puts it: behind block cb's)
+        if (wx6_pair_enabled() && p.ncb % 2 == 0 && !p.heads) {
+            p.npairs = p.ncb / 2 * d.groups;
+            auto kern = conv_wino_x6_kernel<NBT, XF, EPI, PSEL, true, true>;
+            constexpr size_t smem_pair = smem + 8 * NBT * 256 * sizeof(float);      // + the consumers' batch sums: 128 KB
+            static unsigned attr_mask = 0;
+            if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem_pair)) return rc;
+            int gx = 256 / p.npairs;                      // one workgroup per CU
+            if (gx < 1) gx = 1;
+            if (gx > nitems) gx = nitems;
+            p.gx = gx;
+            hipLaunchKernelGGL(kern, dim3(gx * p.npairs), dim3(512), smem_pair, c.stream, p);
+            GSSD_CHECK_LAUNCH();
+            return GSSD_OK;
+        }
+    }
     auto kern = conv_wino_x6_kernel<NBT, XF, EPI, PSEL, F16>;
     static unsigned attr_mask = 0;
     if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, smem)) return rc;
-    const int nitems = (p.ntiles + 63) / 64;
     int gx = 256 / p.npairs;                              // one workgroup per CU
     if (gx < 1) gx = 1;
     if (gx > nitems) gx = nitems;

@@ -21,11 +21,6 @@
 
 namespace {
 
-#ifndef X6_SCHED
-#define X6_SCHED 0           // N > 0: N (+1, +2 for the narrower tiles) vector instructions pinned behind every MFMA of the K loop by
-                             // sched_group_barrier; 0: the compiler's own order -- 5-6 % faster with two workgroups per CU (same-box sweep 0 / 1 / 2 / 3:
-                             // conv4_2 367 / 379 / 389 / 387 us, conv6 173 / 186 / 185 / 184), unlike dcn_x6 (one wave per SIMD) where the pinned order is the gain
-#endif
 #ifndef X6_KO
 #define X6_KO 0             // knock-outs (scripts/conv_x6_knockout.sh): 1 no transform / split, 2 no MFMAs, 4 no weight DMA, 8 no activation loads,
 #endif                      // 16 no fragment reads, 32 no LDS writes of the planes
@@ -41,407 +36,22 @@ constexpr int A_STAGE = BM * BKC;                     // u16 elements per plane
 // instructions.  The packed weights hold both forms (the bf16 planes, then the fp16 planes); data gradients keep the bf16 planes.
 // GSSD_X6_F16=0: bf16 everywhere.
 
-#ifndef X6_V2
-#define X6_V2 1             // round 5's K loop for the 64- / 128-column tiles (conv_x6_v2_kernel); 0: round 4's (conv_x6_kernel, also the 256-column sweep instance)
-#endif
-
-template <int BN>
-struct Cfg {
-    static constexpr int NBS = BN >= 128 ? 1 : 2;     // weight stages (one buffer: fragments -> barrier -> next DMA behind the MFMAs)
-    static constexpr int B_STAGE = BN * BKC;
-    static constexpr int LDS_BYTES = (2 * NP * A_STAGE + NBS * NP * B_STAGE) * 2;      // + the scale / shift table [2][cin_g] floats
-    static constexpr int OCC = BN <= 128 ? 2 : 1;
-};
-
-// wp: [3 planes][groups][n_tiles][chunks][BN rows in staging order][32] bf16 (slot-swizzled), chunk = c32 * taps + tap
-template <int BN, bool XF>
-__global__ __launch_bounds__(256, Cfg<BN>::OCC) void conv_x6_kernel(const gssd_conv_desc p, const int M, const int ntn, const int mtiles,
-                                                                   const long long plane_elems) {
-    constexpr int NBS = Cfg<BN>::NBS, B_STAGE = Cfg<BN>::B_STAGE;
-    constexpr int WTM = 64, WTN = BN / 2, MT = WTM / 16, NT = WTN / 16;
-    extern __shared__ __attribute__((aligned(16))) u16 smem_h[];
-    u16* const As = smem_h;                                   // [2][3][BM][32]
-    u16* const Bs = smem_h + 2 * NP * A_STAGE;                // [NBS][3][BN][32]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int r = lane & 15, kq = lane >> 4;
-    // flat XCD-aware grid: the slots of an XCD run through all (group, N tile) pairs of one M tile before the next M tile
-    const int ny = p.groups * ntn;
-    const int slot = blockIdx.x >> 3;
-    const int mt = (slot / ny) * 8 + (blockIdx.x & 7);
-    const int by = slot % ny;
-    if (mt >= mtiles) return;
-    const int g = by / ntn, nt = by - g * ntn;
-    const int cout_g = p.Cout / p.groups;
-    const int n0g = nt * BN;
-    const int m0 = mt * BM;
-    const int HoWo = p.Ho * p.Wo;
-    const int taps = p.KH * p.KW;
-    const int cpc = p.cin_g / BKC;
-    const int nchunks = cpc * taps;
-    const float* __restrict__ in = p.in + p.in_ch_off + g * p.cin_g;
-    const u16* wslab = reinterpret_cast<const u16*>(p.wgt_x6) + (size_t)by * nchunks * B_STAGE;      // plane 0; plane q at + q * plane_elems
-    constexpr bool xf = XF;
-    const float* xsc = xf ? p.in_scale + p.in_ch_off + g * p.cin_g : nullptr;
-    const float* xsh = xf ? p.in_shift + p.in_ch_off + g * p.cin_g : nullptr;
-
-    f32x4 acc[MT][NT];
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = zero4;
-
-    // gather roles: thread -> (pixel row gp + 64 j, 8-channel slot gq)
-    const int gq = tid & 3, gp = tid >> 2;
-    const int a_wr0 = gp * BKC + ((gq ^ swz64(gp)) << 3);
-    const int fo = r * BKC + ((kq ^ swz64(r)) << 3);
-    int g_iy0[2], g_ix0[2], g_off[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int m = m0 + gp + 64 * j;
-        const bool ok = m < M;
-        const int mm = ok ? m : 0;
-        const int b = mm / HoWo, pix = mm - b * HoWo;
-        const int oy = pix / p.Wo, ox = pix - oy * p.Wo;
-        g_iy0[j] = ok ? oy * p.stride - p.pad : -(1 << 20);
-        g_ix0[j] = ox * p.stride - p.pad;
-        g_off[j] = ((b * p.H + oy * p.stride - p.pad) * p.W + g_ix0[j]) * p.in_stride + gq * 8;
-    }
-
-    // ---- the K loop, one instruction stream per chunk ------------------------------------------------------------------------------
-    // chunk ch: fragments of chunk ch -> registers; global loads of chunk ch + 2's activations (registers) and the LDS-DMA of chunk ch + 1's
-    // weights are issued; the MFMAs of chunk ch run INTERLEAVED with the vector work on chunk ch + 1's activations (loaded during chunk
-    // ch - 1: deferred BatchNorm + ReLU, the three-plane split, LDS writes into the other stage).  Everything is unconditional (past the end
-    // the last chunk is loaded again and the writes go to a stage nobody reads), so the chunk is one basic block the scheduler can interleave.
-    int ld_ty = 0, ld_tx = 0, ld_c = 0, ld_tap = 0;          // chunk whose activations are loaded next
-    int fin_c = 0, fin_tap = 0;                             // chunk whose activations are split next (its 32-channel block)
-    f32x4 gvA[2][2], gvB[2][2];
-    bool gokA[2], gokB[2];
-    float* const xtab = reinterpret_cast<float*>(smem_h + 2 * NP * A_STAGE + NBS * NP * B_STAGE);      // [2][cin_g] scale | shift
-    if (xf) {
-        for (int c = tid; c < p.cin_g; c += 256) {
-            xtab[c] = xsc[c];
-            xtab[p.cin_g + c] = xsh[c];
-        }
-    }
-
-    // ASM: the loads are issued from inline assembly, invisible to the compiler's wait-count pass (which otherwise waits for ALL vector
-    // memory operations -- the weight DMA just issued included -- before the first use of the previous chunk's values); the chunk body
-    // waits for them by count itself
-    auto gather_issue = [&](f32x4 (&gv)[2][2], bool (&gok)[2], const bool ASM) {
-        const int dy = ld_ty * p.dil, dx = ld_tx * p.dil;
-        const int toff = (dy * p.W + dx) * p.in_stride + ld_c * BKC;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            gok[j] = (unsigned)(g_iy0[j] + dy) < (unsigned)p.H && (unsigned)(g_ix0[j] + dx) < (unsigned)p.W;
-            const float* src = in + (gok[j] ? g_off[j] + toff : gq * 8);
-            if (X6_KO & 8) continue;
-            if (ASM) {
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(gv[j][0]) : "v"(src) : "memory");
-                asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(gv[j][1]) : "v"(src) : "memory");
-                continue;
-            }
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) gv[j][hh] = *reinterpret_cast<const f32x4*>(src + 4 * hh);
-        }
-    };
-    auto advance_ld = [&]() {
-        ++ld_tap;
-        if (++ld_tx == p.KW) {
-            ld_tx = 0;
-            ++ld_ty;
-        }
-        if (ld_tap == taps) {
-            ld_tap = ld_ty = ld_tx = 0;
-            ++ld_c;
-        }
-    };
-    auto advance_fin = [&]() {
-        if (++fin_tap == taps) {
-            fin_tap = 0;
-            ++fin_c;
-        }
-    };
-    // quarter `part` (pixel j = part >> 1, channel half hh = part & 1) of this thread's 16 values: transform, split into the planes
-    auto finish_part = [&](int part, const f32x4 (&gv)[2][2], const bool (&gok)[2], int buf) {
-        if (X6_KO & 1) return;
-        const int j = part >> 1, hh = part & 1;
-        bf16x4 oh, om_, ol;
-        f32x4 v = gv[j][hh];
-        if (xf) {
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(xtab + fin_c * BKC + gq * 8 + 4 * hh);
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(xtab + p.cin_g + fin_c * BKC + gq * 8 + 4 * hh);
-            // (element by element: packed fp32 instructions do not run beside the MFMAs, scripts/ubench/mfma16_valu_overlap.hip)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e] * sc[e] + sh[e], 0.f);
-        }
-        if (!gok[j]) v = zero4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            __bf16 h, m, l;
-            split3(v[e], h, m, l);
-            oh[e] = h;
-            om_[e] = m;
-            ol[e] = l;
-        }
-        if (X6_KO & 32) return;
-        u16* Ad = As + buf * NP * A_STAGE + a_wr0 + j * 64 * BKC + 4 * hh;
-        *reinterpret_cast<bf16x4*>(Ad) = oh;
-        *reinterpret_cast<bf16x4*>(Ad + A_STAGE) = om_;
-        *reinterpret_cast<bf16x4*>(Ad + 2 * A_STAGE) = ol;
-    };
-    auto b_issue = [&](int chunk, int buf) {
-        if (X6_KO & 4) return;
-        u16* dst = Bs + (NBS == 2 ? buf : 0) * NP * B_STAGE;
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
-            const u16* src = wslab + (size_t)pl * plane_elems + (size_t)chunk * B_STAGE + lane * 8;
-#pragma unroll
-            for (int j = 0; j < B_STAGE / 512 / 4; ++j) {
-                const int piece = j * 4 + wave;                        // 1-KiB pieces of the plane's tile
-                dma16(src + piece * 512, dst + pl * B_STAGE + piece * 512);
-            }
-        }
-    };
-
-    gather_issue(gvA, gokA, false);                // chunk 0
-    b_issue(0, 0);
-    if (nchunks > 1) advance_ld();
-    if (xf) __syncthreads();                       // the scale / shift table
-#pragma unroll
-    for (int part = 0; part < 4; ++part) finish_part(part, gvA, gokA, 0);
-    if (nchunks > 1) advance_fin();
-    gather_issue(gvA, gokA, false);                // chunk 1 (or chunk 0 again)
-    if (nchunks > 2) advance_ld();
-    __syncthreads();
-
-    auto chunk = [&](const int ch, f32x4 (&gv_use)[2][2], const bool (&gok_use)[2], f32x4 (&gv_ld)[2][2], bool (&gok_ld)[2]) {
-        const int buf = ch & 1;
-        const u16* Ab = As + buf * NP * A_STAGE + wm * WTM * BKC + fo;
-        const u16* Bb = Bs + (NBS == 2 ? buf : 0) * NP * B_STAGE + wn * WTN * BKC + fo;
-        bf16x8 afr[2][NP], bf[NP][NT];          // activation fragments row by row (two rows in registers), weight fragments all at once
-        auto a_row = [&](int i) {
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                if (X6_KO & 16) asm volatile("" : "=v"(afr[i & 1][pl]));
-                else afr[i & 1][pl] = *reinterpret_cast<const bf16x8*>(Ab + pl * A_STAGE + i * 16 * BKC);
-            }
-        };
-        a_row(0);
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                if (X6_KO & 16) {
-                    asm volatile("" : "=v"(bf[pl][j]));
-                    continue;
-                }
-                bf[pl][j] = *reinterpret_cast<const bf16x8*>(Bb + pl * B_STAGE + j * 16 * BKC);
-            }
-        }
-        if (NBS == 1) {
-            // one weight buffer: every wave holds its fragments in registers before the next chunk's planes may land
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        b_issue(min(ch + 1, nchunks - 1), buf ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        gather_issue(gv_ld, gok_ld, true);         // chunk ch + 2: the four youngest vector-memory operations of the chunk
-        if (!(X6_KO & 8)) {
-            // chunk ch + 1's values (loaded during the previous chunk): everything older than this chunk's DMA pieces and loads
-            constexpr int YOUNGER = ((X6_KO & 4) ? 0 : NP * (B_STAGE / 512 / 4)) + 4;
-            asm volatile("s_waitcnt vmcnt(%4)" : "+v"(gv_use[0][0]), "+v"(gv_use[0][1]), "+v"(gv_use[1][0]), "+v"(gv_use[1][1]) : "n"(YOUNGER));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // six products per fragment pair, smallest first (a: activation planes, b: weight planes).  The bf16 MFMA's adder truncates: summing
-        // the six products of a chunk from zero and adding the chunk's sum to the running sum with the vector ALU (round to nearest) keeps the
-        // result closer to float64 than the fp32-MFMA kernels (3-4 x closer than accumulating in place: scripts/bench_conv_x6.py)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            if (i + 1 < MT) a_row(i + 1);
-            const bf16x8 (&af)[NP] = afr[i & 1];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                if (X6_KO & 2) continue;
-#if X6_LOCAL_SUM
-                f32x4 c = zero4;
-#else
-                f32x4 c = acc[i][j];
-#endif
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[1][j], af[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[2][j], af[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0][j], af[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[1][j], af[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0][j], af[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0][j], af[0], c, 0, 0, 0);
-#if X6_LOCAL_SUM
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][e] += c[e];
-#else
-                acc[i][j] = c;
-#endif
-            }
-            finish_part(i, gv_use, gok_use, buf ^ 1);
-        }
-#if X6_SCHED
-        // one MFMA, then the vector instructions that fit into its 16 cycles
-#define X6_ROW(DS_READS)                                                                                                   \
-    __builtin_amdgcn_sched_group_barrier(0x100, DS_READS, 0); /* next row's fragments, scale / shift */                    \
-    _Pragma("unroll") for (int k = 0; k < NT * 6; ++k) {                                                                   \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                                 \
-        __builtin_amdgcn_sched_group_barrier(0x002, BN == 64 ? X6_SCHED + 2 : BN == 128 ? X6_SCHED + 1 : X6_SCHED, 0);     \
-    }                                                                                                                      \
-    __builtin_amdgcn_sched_group_barrier(0x200, NP, 0); /* the quarter's planes */
-        static_assert(MT == 4, "the schedule below is written for four fragment rows");
-        X6_ROW(NP + (XF ? 2 : 0))
-        X6_ROW(NP + (XF ? 2 : 0))
-        X6_ROW(NP + (XF ? 2 : 0))
-        X6_ROW((XF ? 2 : 0))
-#undef X6_ROW
-#endif
-        __builtin_amdgcn_sched_barrier(0);
-        if (ch + 2 < nchunks) advance_fin();
-        if (ch + 3 < nchunks) advance_ld();
-        // the next chunk's weights have landed and its planes are written; the activation loads of chunk ch + 2 stay in flight
-        if (X6_KO & 8) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    };
-    // two chunks per trip: the register sets of the activation loads alternate (no copies, no wait for a load before its chunk)
-    for (int ch = 0; ch < nchunks; ch += 2) {
-        chunk(ch, gvA, gokA, gvB, gokB);
-        if (ch + 1 < nchunks) chunk(ch + 1, gvB, gokB, gvA, gokA);
-    }
-    // The last chunk ends with `s_waitcnt vmcnt(4)`: its four look-ahead loads (the last chunk again) are still in flight, and they were
-    // issued from inline assembly, so the compiler's wait-count pass does not know about them.  gvA / gvB are dead from here on and their
-    // registers may be handed to epilogue temporaries: drain the loads before anything else can live there.  gvA / gvB are
-    // never copied between gather_issue() and the counted wait that names them as "+v" operands.
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(gvA[0][0]), "+v"(gvA[0][1]), "+v"(gvA[1][0]), "+v"(gvA[1][1]),
-                                        "+v"(gvB[0][0]), "+v"(gvB[0][1]), "+v"(gvB[1][0]), "+v"(gvB[1][1]) : : "memory");
-    __syncthreads();
-
-    // ---- epilogue: + bias, batch sums of the pre-activation output, ReLU, 16-byte NHWC stores (lane: pixel r, 8 consecutive channels
-    //      per tile pair) ------------------------------------------------------------------------------------------------------------
-    float* red = reinterpret_cast<float*>(smem_h);          // [2 wm][BN][2]
-    const float gate = p.gate ? *p.gate : 0.f;
-    const bool split_t = p.out_mode == GSSD_OUT_SPLIT_T && n0g >= p.split_n;      // workgroup-uniform: split_n is a multiple of the tile
-    const bool gcat = (p.flags & GSSD_CONV_OUT_GROUPCAT) != 0;
-#pragma unroll
-    for (int u = 0; u < NT / 2; ++u) {
-        const int nl = wn * WTN + 32 * u + 8 * kq;            // channel inside the tile
-        const int ng = n0g + nl;                              // ... inside the group
-        const bool n_ok = ng + 8 <= cout_g;
-        const int n = g * cout_g + ng;
-        // GSSD_CONV_OUT_GROUPCAT: channel n lands behind the split_n-channel slabs in front of it once more (the per-group concatenation
-        // slice_and_cat would build); 8-channel vectors never straddle a slab
-        const int ncat = gcat ? (n / p.split_n) * p.split_n : 0;
-        float bv[8], av[8], ssum[8], ssq[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            bv[c] = (p.bias && n_ok) ? p.bias[n + c] : 0.f;
-            av[c] = (p.alpha && n_ok) ? p.alpha[n + c] : 1.f;
-            ssum[c] = ssq[c] = 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int m = m0 + wm * WTM + i * 16 + r;
-            if (m >= M || !n_ok) continue;
-            float v[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                v[c] = acc[i][2 * u + (c >> 2)][c & 3] * av[c] + bv[c];
-                ssum[c] += v[c];
-                ssq[c] += v[c] * v[c];
-            }
-            if (split_t) {
-                // second column range of a merged projection: per image [n - split_n][pixel] (the row tails up to out_b_stride are never
-                // written: the caller zero-fills the buffer once)
-                const int bi = m / HoWo, ml = m - bi * HoWo;
-                float* dst = p.out_b + (size_t)bi * p.outb_batch_stride + (size_t)(n - p.split_n) * p.out_b_stride + ml;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) dst[(size_t)c * p.out_b_stride] = v[c];
-                continue;
-            }
-            // conv_igemm's epilogue order: gate, second output, residual, ReLU
-            const size_t o = (size_t)m * p.out_stride + p.out_ch_off + n + ncat;
-            const size_t ro = gcat ? (size_t)m * p.Cout + n : o;      // (the residual keeps its own dense rows)
-            if (p.gate) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) v[c] *= gate;
-                if (p.out2) {
-                    *reinterpret_cast<f32x4*>(p.out2 + o) = f32x4{v[0], v[1], v[2], v[3]};
-                    *reinterpret_cast<f32x4*>(p.out2 + o + 4) = f32x4{v[4], v[5], v[6], v[7]};
-                }
-            }
-            if (p.resid) {
-                f32x4 r0 = *reinterpret_cast<const f32x4*>(p.resid + ro), r1 = *reinterpret_cast<const f32x4*>(p.resid + ro + 4);
-                if (p.flags & GSSD_CONV_RESID_XF) {
-                    // the residual is its producer's raw map: BatchNorm + ReLU on read, finish_part's expression (bit-identical to the pass)
-                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(p.in_scale + n), s1 = *reinterpret_cast<const f32x4*>(p.in_scale + n + 4);
-                    const f32x4 h0 = *reinterpret_cast<const f32x4*>(p.in_shift + n), h1 = *reinterpret_cast<const f32x4*>(p.in_shift + n + 4);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        r0[c] = fmaxf(r0[c] * s0[c] + h0[c], 0.f);
-                        r1[c] = fmaxf(r1[c] * s1[c] + h1[c], 0.f);
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    v[c] += r0[c];
-                    v[4 + c] += r1[c];
-                }
-            }
-            if (p.relu) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) v[c] = fmaxf(v[c], 0.f);
-            }
-            *reinterpret_cast<f32x4*>(p.out + o) = f32x4{v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(p.out + o + 4) = f32x4{v[4], v[5], v[6], v[7]};
-        }
-        if (p.stats) {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                float s = ssum[c], q = ssq[c];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) {
-                    s += __shfl_xor(s, o, 64);
-                    q += __shfl_xor(q, o, 64);
-                }
-                if (r == 0) {
-                    red[(wm * BN + nl + c) * 2 + 0] = s;
-                    red[(wm * BN + nl + c) * 2 + 1] = q;
-                }
-            }
-        }
-    }
-    if (p.stats) {
-        __syncthreads();
-        if (tid < BN && n0g + tid < cout_g) {
-            const double s = (double)red[tid * 2 + 0] + (double)red[(BN + tid) * 2 + 0];
-            const double q = (double)red[tid * 2 + 1] + (double)red[(BN + tid) * 2 + 1];
-            const int n = g * cout_g + n0g + tid;
-            double* st = gssd_stats_replica(p.stats, p.stats_rep, p.Cout);
-            unsafeAtomicAdd(st + n, s);
-            unsafeAtomicAdd(st + p.Cout + n, q);
-        }
-    }
-}
-
-#if X6_V2
-// ---- round 5: the K loop of dcn_x6.hip's v2 kernel for the plain convolution ---------------------------------------------------------------
-// Round 4's loop read all weight fragments of a chunk (+ the first activation row) in front of a barrier, then issued the weight DMA and the
-// activation loads in a burst; "feeding" and MFMAs added up (profiles/r04_f_conv_x6_knockout.txt).  Here, as in dcn_x6.hip (see there):
+// ---- the kernel: 128 pixels x BN channels per workgroup (BN = 64 / 128), four waves of 64 x BN / 2, two workgroups per CU ------------------------
+// A chunk is 32 input channels of one tap.  The K loop (the one of dcn_x6.hip's kernel, see there) keeps the matrix pipe fed by spreading the
+// memory work of the next chunk over the MFMAs of this one, so that "feeding" hides behind the products instead of adding to them:
 //   * iteration `it` = [part A: the column tiles of the second half of chunk it - 1] [part B: the first half of chunk it];
 //   * ONE activation stage (the four rows' fragments are reloaded in place behind the last column tile's MFMAs), the weight planes in four
 //     half buffers (X: first half of the wave's column tiles, Y: second half; two of each): what an iteration reads was DMA'd during the
-//     previous one -- 24 + 48 KB for 128 columns as before, 24 + 24 KB for 64;
+//     previous one -- 24 KB of activation planes + 48 KB of weights for 128 columns, 24 + 24 KB for 64;
 //   * column tile outer, fragment row inner; the weight fragments of the next tile are prefetched behind the current tile's MFMAs;
-//   * every memory request sits behind its own group of six MFMAs; waits are counted (vmcnt is in issue order);
+//   * every memory request sits behind its own group of six MFMAs; the activation loads are issued from inline assembly (the compiler's
+//     wait-count pass would otherwise wait for the weight DMA issued beside them) and waits are counted (vmcnt is in issue order);
 //   * two barriers per iteration: B1 in front of part A's last column tile (the previous iteration's planes and X pieces are in LDS),
 //     B2 behind part B's first group (every wave holds its fragments, its loads and Y pieces have landed).
+// Packed weights: [3 planes][groups][n_tiles][chunks][BN rows in staging order][32] bf16 (slot-swizzled), chunk = c32 * taps + tap; the three
+// fp16 planes lie behind them in the same layout.
 template <int BN>
-struct Cfg2 {
+struct Cfg {
     static constexpr int WTN = BN / 2, NT = WTN / 16, NTH = NT / 2, MT = 4;
     static constexpr int NG = NTH * MT;                   // groups of six MFMAs per part: 8 / 4
     static constexpr int HB_ROWS = BN / 2, HB_PLANE = HB_ROWS * BKC, HB_ELEMS = NP * HB_PLANE;
@@ -453,9 +63,9 @@ struct Cfg2 {
 };
 
 template <int BN, bool XF, bool F16>
-__global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc p, const int M, const int ntn, const int mtiles,
-                                                           const long long plane_elems) {
-    using K = Cfg2<BN>;
+__global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p, const int M, const int ntn, const int mtiles,
+                                                        const long long plane_elems) {
+    using K = Cfg<BN>;
     // F16: TWO planes travel through LDS and the weight DMA -- h and l6 = (x - h) * 64; h6 = h / 64 is made from h in registers behind the fragment
     // reads (four packed multiplies per fragment).  Why: at three planes a chunk moves 144 KB through the CU's LDS port (fragment reads 96, plane
     // writes 24, DMA 24) = 1 125 cycles at 128 B per cycle against 768 cycles of MFMAs; two planes: 96 KB = 750.  The LDS images keep their
@@ -1007,8 +617,6 @@ __global__ __launch_bounds__(256, 2) void conv_x6_v2_kernel(const gssd_conv_desc
     }
 }
 
-#endif
-
 // packed fp32 rows [Cout][row_stride] (k = tap * cin_g + c) -> three bf16 planes in the kernel's DMA order; rows beyond cout_g zero
 __global__ void conv_x6_pack_kernel(const float* __restrict__ w, u16* __restrict__ wp, int Cout, int groups, int cin_g, int taps, int row_stride,
                                     int BN, long long total) {
@@ -1039,45 +647,32 @@ __global__ void conv_x6_pack_kernel(const float* __restrict__ w, u16* __restrict
     }
 }
 
-template <int BN, bool XF>
-int launch(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
-    if (c.name) return gssd_name_kernel(c, "conv_x6<%d>", BN);
-    static unsigned attr_mask = 0;
-    auto kern = conv_x6_kernel<BN, XF>;
-    if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, Cfg<BN>::LDS_BYTES + 4096)) return rc;
-    const int cout_g = d.Cout / d.groups;
-    const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
-    const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
-    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), Cfg<BN>::LDS_BYTES + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), c.stream, d, M, ntn, mtiles, plane);
-    GSSD_CHECK_LAUNCH();
-    return GSSD_OK;
-}
+// the fused INPUT transform (GSSD_CONV_RESID_XF: in_scale / in_shift belong to the residual, the input is read plain)
+inline bool x6_in_xf(const gssd_conv_desc& d) { return d.in_scale && !(d.flags & GSSD_CONV_RESID_XF); }
 
-#if X6_V2
+// one kernel instance
 template <int BN, bool XF, bool F16>
-int launch2_impl(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
-    if (c.name) return gssd_name_kernel(c, "conv_x6<%d>", BN);
+int launch(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
     static unsigned attr_mask = 0;
-    auto kern = conv_x6_v2_kernel<BN, XF, F16>;
-    constexpr int lds = Cfg2<BN>::LDS_BYTES;
+    auto kern = conv_x6_kernel<BN, XF, F16>;
+    constexpr int lds = Cfg<BN>::LDS_BYTES;
     if (const int rc = gssd_max_dynamic_lds(&attr_mask, kern, lds + 4096)) return rc;
     const int cout_g = d.Cout / d.groups;
     const int ntn = (cout_g + BN - 1) / BN, mtiles = (M + BM - 1) / BM;
     const long long plane = (long long)d.groups * ntn * BN * d.KH * d.KW * d.cin_g;
-    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), lds + ((d.in_scale && !(d.flags & GSSD_CONV_RESID_XF)) ? 8 * d.cin_g : 0), c.stream, d, M, ntn, mtiles, plane);
+    hipLaunchKernelGGL(kern, dim3((mtiles + 7) / 8 * 8 * d.groups * ntn), dim3(256), lds + (x6_in_xf(d) ? 8 * d.cin_g : 0), c.stream, d, M, ntn, mtiles, plane);
     GSSD_CHECK_LAUNCH();
     return GSSD_OK;
 }
-// the three-MFMA fp16 form: only launches the CALLER flags GSSD_CONV_F16_OK (operands inside fp16's range: include/gssd_hip.h) -- never inferred
-template <int BN, bool XF>
-int launch2(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
-    if (gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK)) return launch2_impl<BN, XF, true>(d, M, c);
-    return launch2_impl<BN, XF, false>(d, M, c);
+// the instance of a tile width.  The three-MFMA fp16 form: only launches the CALLER flags GSSD_CONV_F16_OK (operands inside fp16's range:
+// include/gssd_hip.h) -- never inferred
+template <int BN>
+int launch_tile(const gssd_conv_desc& d, int M, gssd_conv_ctx& c) {
+    if (c.name) return gssd_name_kernel(c, "conv_x6<%d>", BN);
+    const bool f16 = gssd_x6_f16_enabled() && (d.flags & GSSD_CONV_F16_OK);
+    if (x6_in_xf(d)) return f16 ? launch<BN, true, true>(d, M, c) : launch<BN, true, false>(d, M, c);
+    return f16 ? launch<BN, false, true>(d, M, c) : launch<BN, false, false>(d, M, c);
 }
-#endif
-
-// the fused INPUT transform (GSSD_CONV_RESID_XF: in_scale / in_shift belong to the residual, the input is read plain)
-inline bool x6_in_xf(const gssd_conv_desc& d) { return d.in_scale && !(d.flags & GSSD_CONV_RESID_XF); }
 
 bool shape_ok(int cin_g, int cout_g, int groups) {
     return cin_g > 0 && cin_g % BKC == 0 && cout_g >= 32 && cout_g % 8 == 0 && groups > 0;
@@ -1088,16 +683,15 @@ bool shape_ok(int cin_g, int cout_g, int groups) {
 // N tile of a (cout_g, groups, M) launch.  GSSD_X6_BN overrides (experiments); the packed weights depend on it, so it is read once.
 extern "C" int gssd_conv_x6_tile(int cout_g, int groups, long long M) {
     static const int forced = getenv("GSSD_X6_BN") ? atoi(getenv("GSSD_X6_BN")) : 0;
-    if (forced == 64 || forced == 128 || forced == 256) return forced;
+    if (forced == 64 || forced == 128) return forced;
     (void)groups;
     (void)M;
-    // measured on the trunk shapes at B = 32 (scripts/bench_conv_x6.py, GSSD_X6_BN sweep): two resident 128-column workgroups beat one
-    // 256-column workgroup everywhere (conv6 174 vs 248 us, fuse_11 166 vs 193); the 256 instance stays for the sweep
+    // the widest tile the group fills more than half of (GSSD_X6_BN=64 against 128 on the trunk shapes: profiles/r06_experiments.txt)
     return cout_g > 64 ? 128 : 64;
 }
 
 extern "C" long long gssd_conv_x6_weight_elems(int Cout, int groups, int cin_g, int taps, int BN) {         // bf16 elements (three planes)
-    if (Cout <= 0 || groups <= 0 || Cout % groups != 0 || taps <= 0 || !(BN == 64 || BN == 128 || BN == 256)) return -1;
+    if (Cout <= 0 || groups <= 0 || Cout % groups != 0 || taps <= 0 || !(BN == 64 || BN == 128)) return -1;
     if (!shape_ok(cin_g, Cout / groups, groups)) return -1;
     const int cout_g = Cout / groups;
     return 6ll * groups * ((cout_g + BN - 1) / BN) * BN * taps * cin_g;      // three bf16 planes, then three fp16 planes
@@ -1132,9 +726,9 @@ extern "C" int gssd_conv_x6_takes(const gssd_conv_desc* dp) {
         const int bn = gssd_conv_x6_tile(d.Cout / d.groups, d.groups, (long long)d.B * d.Ho * d.Wo);
         if (d.groups != 1 || !d.out_b || d.split_n <= 0 || d.split_n % bn != 0 || d.out_b_stride < d.Ho * d.Wo) return 0;
         if (d.flags & GSSD_CONV_OUT_X6PLANES) {
-            // the attention core's planes instead of the fp32 arrays: the v2 kernel's epilogue, whole tiles, dense theta | phi rows, key rows
+            // the attention core's planes instead of the fp32 arrays: whole tiles, dense theta | phi rows, key rows
             // in whole 32-blocks, images of whole 4-pixel groups, no other epilogue work
-            if (!X6_V2 || bn > 128 || d.Cout % bn != 0 || d.out_stride != d.split_n || d.out_ch_off != 0 || d.out_b_stride % 32 != 0 ||
+            if (d.Cout % bn != 0 || d.out_stride != d.split_n || d.out_ch_off != 0 || d.out_b_stride % 32 != 0 ||
                 (d.Ho * d.Wo) % 4 != 0 || d.outb_batch_stride != (long long)(d.Cout - d.split_n) * d.out_b_stride || d.relu || d.stats ||
                 d.gate || d.resid || d.out2 || ((uintptr_t)d.out_b % 16))
                 return 0;
@@ -1167,14 +761,5 @@ int gssd_try_conv_x6(const gssd_conv_desc& d, gssd_conv_ctx& c) {
     if (!gssd_conv_x6_takes(&d)) return 1;
     const long long Mll = (long long)d.B * d.Ho * d.Wo;
     const int M = (int)Mll;
-    switch (gssd_conv_x6_tile(d.Cout / d.groups, d.groups, Mll)) {
-#if X6_V2
-        case 64: return x6_in_xf(d) ? launch2<64, true>(d, M, c) : launch2<64, false>(d, M, c);
-        case 128: return x6_in_xf(d) ? launch2<128, true>(d, M, c) : launch2<128, false>(d, M, c);
-#else
-        case 64: return x6_in_xf(d) ? launch<64, true>(d, M, c) : launch<64, false>(d, M, c);
-        case 128: return x6_in_xf(d) ? launch<128, true>(d, M, c) : launch<128, false>(d, M, c);
-#endif
-        default: return x6_in_xf(d) ? launch<256, true>(d, M, c) : launch<256, false>(d, M, c);
-    }
+    return gssd_conv_x6_tile(d.Cout / d.groups, d.groups, Mll) == 64 ? launch_tile<64>(d, M, c) : launch_tile<128>(d, M, c);
 }

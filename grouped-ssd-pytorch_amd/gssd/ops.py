@@ -219,7 +219,7 @@ def winograd_eligible(k, stride, pad, dil, cin_g, cout_g, groups=4):
 
 
 def x6_tile(cout_g, groups, M):
-    """N tile (64 / 128 / 256) csrc/conv_x6.hip uses for this launch; the packed weights depend on it."""
+    """N tile (64 / 128) csrc/conv_x6.hip uses for this launch; the packed weights depend on it."""
     return int(lib.gssd_conv_x6_tile(cout_g, groups, M))
 
 

@@ -167,7 +167,7 @@ int gssd_conv2d_nhwc_f32(const gssd_conv_desc* d, gssd_stream_t stream);
 
 /* fp32 convolution with fp32-equivalent products on the BF16 matrix cores (csrc/conv_x6.hip; nn.Conv2d of the reference's trunk,
  * models/ssd_multiphase_custom_group.py vgg() / add_extras()): every operand is the exact sum of three bf16 planes, six
- * v_mfma_f32_16x16x32_bf16 per product (all terms above 2^-24), fp32 accumulation.  gssd_conv_x6_tile: the N tile (64 / 128 / 256) the
+ * v_mfma_f32_16x16x32_bf16 per product (all terms above 2^-24), fp32 accumulation.  gssd_conv_x6_tile: the N tile (64 / 128) the
  * launch of a (cout_g, groups, M = B*Ho*Wo) conv uses -- the packed weights depend on it.  gssd_conv_x6_weight_elems: bf16 elements of
  * the packed form (-1: not a shape the kernel takes).  gssd_conv_x6_pack_weight: K-major fp32 rows [Cout][row_stride] (gssd_pack_conv_weight)
  * -> the three planes.  gssd_conv_x6_takes: 1 when gssd_conv2d_nhwc_f32 runs the descriptor on this kernel (wgt_x6 set, NHWC output,

@@ -88,6 +88,7 @@ def test_conv_x6_host_rules():
     assert lib.gssd_conv_x6_weight_elems(216, 1, 512, 9, 128) == 6 * 1 * 2 * 128 * 9 * 512          # 216 -> two 128-column tiles, zero rows
     assert lib.gssd_conv_x6_weight_elems(512, 1, 48, 1, 128) == -1                                    # cin_g % 32 != 0
     assert lib.gssd_conv_x6_weight_elems(512, 1, 64, 1, 96) == -1                                     # not a tile width
+    assert lib.gssd_conv_x6_weight_elems(512, 1, 64, 1, 256) == -1                                    # nor is 256
     assert ops.x6_wanted(1, 512, 512, 1, 46208) and ops.x6_wanted(3, 128, 256, 4, 11552)
     assert not ops.x6_wanted(3, 128, 128, 4, 46208, winograd=True) and not ops.x6_wanted(1, 512, 64, 1, 46208) and not ops.x6_wanted(1, 512, 512, 1, 3200)
     # Winograd shapes: only forward launches on maps too small for conv_wino_x6 (conv5_x at batch 32), and only on the fp16 planes
@@ -273,6 +274,9 @@ def test_conv2d_kernel_name_buffer_and_takes():
     ({'GSSD_NO_SMALL_TILES': '1'}, False, "dict(B=1, H=16, W=32, cin_g=64, in_stride=64, Cout=128, k=3, pad=1)", 'conv_igemm<128x64>'),
     ({'GSSD_CONV21_WINO': '0'}, False, "dict(B=2, H=150, W=150, groups=4, cin_g=16, in_stride=64, Cout=128, k=3, pad=1, wgt_wino=a, wgt_row_stride=144, relu=False, "
                                        "flags=0, out2=a)", 'conv_thin<16,32>'),
+    # conv_x6's forced tile width: 64 or 128, anything else is ignored (the rule gives 512 channels in one group 128 columns)
+    ({'GSSD_X6_BN': '64'}, False, "dict(B=32, H=38, W=38, cin_g=512, in_stride=512, Cout=512, wgt_x6=a)", 'conv_x6<64>'),
+    ({'GSSD_X6_BN': '256'}, False, "dict(B=32, H=38, W=38, cin_g=512, in_stride=512, Cout=512, wgt_x6=a)", 'conv_x6<128>'),
 ])
 def test_conv2d_kernel_name_follows_switches(env, bf16, kw, want):
     import subprocess

@@ -237,7 +237,8 @@ class BackwardOpsMixin:
                                                  pd_.data_ptr(), r.get('stats_rep', 0)))
         pool = r['pool']
         pk, ps, pp = (pool[0], pool[1], pool[2]) if pool else (0, 1, 0)
-        dz = self._buf(B, Ho, Ho, Cout, zero_each_run=bool(pool and ps < pk))
+        zero_dz = ops.routed_grad_needs_zero(Ho, Ho, Hp, Hp, pk, ps, pp)      # overlapping windows accumulate; windows with gaps write only part
+        dz = self._buf(B, Ho, Ho, Cout, zero_each_run=zero_dz)
         sums = self._buf(2 * Cout, dtype=torch.float64, zero_each_run=True)
         # bf16 storage mode: which precision do the consumers of d(pre-activation) read?  (weight gradient: csrc/conv_wgrad_bf16.hip for the
         # grouped 3x3 trunk shapes; data gradient: gssd_conv2d_nhwc_bf16 when the channel counts allow 16-byte rows)
@@ -266,7 +267,7 @@ class BackwardOpsMixin:
             self._need(raw)
         # without pooling the reduce pass only sums (dz = NULL) and the apply pass re-derives dz from d(out): 5 instead of 6 HBM passes
         # mixed + a non-overlapping pool: the routed (un-pooled) gradient travels from the reduce pass to the apply pass as a bf16 map
-        dzp16 = torch.empty(B, Ho, Ho, Cout, device=self.dev, dtype=torch.bfloat16) if (mixed and pool and ps >= pk) else None
+        dzp16 = self._buf(B, Ho, Ho, Cout, dtype=torch.bfloat16, zero_each_run=zero_dz) if (mixed and pool and ps >= pk) else None
         if mixed:
             self._add(lib.gssd_bn_bwd_reduce_mixed,
                       (dout.data_ptr(), int(dout16 is not None), raw16.data_ptr(), sc.data_ptr(), sh.data_ptr(),
@@ -366,7 +367,7 @@ class BackwardOpsMixin:
         B, H, Cc, Hp = self.B, r['H'], r['C'], r['Hp']
         dout = self._grad_of(r['out'])
         existing = self._grad_of(r['x_in'])
-        g = self._buf(B, H, H, Cc, zero_each_run=(r['s'] < r['k']))
+        g = self._buf(B, H, H, Cc, zero_each_run=ops.routed_grad_needs_zero(H, H, Hp, Hp, r['k'], r['s'], r['p']))
         self._add(lib.gssd_bn_bwd_reduce_f32, (dout.data_ptr(), r['x_in'].data_ptr(), 0, 0, g.data_ptr(), 0, B, H, H, Cc, Hp, Hp,
                                                r['k'], r['s'], r['p'], 0))
         if existing is not None:         # (a hoisted branch hanging off the same activation -- L2Norm on conv4_3 -- wrote first)
@@ -393,7 +394,7 @@ class BackwardOpsMixin:
         if dout is None:
             raise _lib.GssdError('no gradient reaches a ReLU / pool pass of the PixelLink++ trunk')
         existing = self._grad_of(r['x_in'])
-        g = self._buf(B, H, H, Cc, zero_each_run=bool(r['k'] and r['s'] < r['k']))
+        g = self._buf(B, H, H, Cc, zero_each_run=ops.routed_grad_needs_zero(H, H, Hp, Hp, r['k'], r['s'], r['p']))
         self._add(lib.gssd_bn_bwd_reduce_f32, (dout.data_ptr(), r['x_in'].data_ptr(), 0, 0, g.data_ptr(), 0, B, H, H, Cc, Hp, Hp,
                                                r['k'], r['s'], r['p'], int(r['relu'])))
         if existing is not None:

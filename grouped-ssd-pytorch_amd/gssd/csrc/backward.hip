@@ -39,8 +39,10 @@ __device__ __forceinline__ void st4_bf16(u16* p, const f32x4 v) {
 // -----------------------------------------------------------------------------------------------------------------
 // Pass 1: window-centric.  One thread per (pooled output position, channel quad).  z = raw*scale + shift, a = relu(z);
 // the window's first maximum of a receives d_out; ReLU's mask (z > 0) is applied; dz is written for every window
-// element (non-overlapping pools) or atomically accumulated (overlapping, dz pre-zeroed).  Per-channel sums
-// s1 = sum dz, s2 = sum dz*raw feed the BatchNorm parameter gradients.
+// element (non-overlapping pools) or atomically accumulated (overlapping, dz pre-zeroed).  Elements in NO window -- a
+// floor-mode pool that ends short of the border, any stride above the kernel size -- are not touched: the caller
+// zeroes dz / dzb then (gssd/ops.py::routed_grad_needs_zero).  Per-channel sums s1 = sum dz, s2 = sum dz*raw feed the
+// BatchNorm parameter gradients.
 // -----------------------------------------------------------------------------------------------------------------
 // POOL = false (pool_k == 0) is its own instantiation: the window code's registers (71) kept the streaming form at ONE 1024-thread
 // workgroup per CU; alone it fits 64 registers = two workgroups (8 waves per SIMD)

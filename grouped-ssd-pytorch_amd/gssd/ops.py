@@ -366,6 +366,21 @@ def pool_out_size(n, k, s, p, ceil):
     return (n + 2 * p - k) // s + 1
 
 
+def pool_leaves_gaps(H, W, Ho, Wo, k, s, p):
+    """True when the Ho x Wo windows of a (k, s, p) max-pool do not cover the H x W map: a floor-mode pool whose last window ends short of
+    the border (2, 2, 0 on an odd extent), or a stride above the kernel size with more than one window.  The pooled reduce pass writes
+    the routed gradient at window elements only, so its buffer has to start as zeros then.  k = 0: no pool."""
+    if not k:
+        return False
+    return (s > k and max(Ho, Wo) > 1) or (Ho - 1) * s - p + k < H or (Wo - 1) * s - p + k < W
+
+
+def routed_grad_needs_zero(H, W, Ho, Wo, k, s, p):
+    """The one rule for the buffer csrc/backward.hip's pooled reduce pass routes d(out) into: overlapping windows accumulate into it with
+    atomics, windows that leave gaps write only part of it.  Every other pool defines all of it with plain stores (no fill launch)."""
+    return bool(k) and (s < k or pool_leaves_gaps(H, W, Ho, Wo, k, s, p))
+
+
 def l2norm(x, weight, eps=1e-10, out=None):
     _need_cuda(x, weight)
     Cc = x.shape[-1]
@@ -618,7 +633,7 @@ def bn_backward(dout, raw, fwd_stats, count, gamma, scale, shift, pool=None, rel
     _, Ho, Wo, _ = dout.shape
     pk, ps, pp = pool if pool else (0, 1, 0)
     dev = raw.device
-    dz = torch.zeros_like(raw) if (pool and ps < pk) else torch.empty_like(raw)
+    dz = torch.zeros_like(raw) if routed_grad_needs_zero(H, W, Ho, Wo, pk, ps, pp) else torch.empty_like(raw)
     sums = torch.zeros(2 * Cc, device=dev, dtype=torch.float64)
     check(lib.gssd_bn_bwd_reduce_f32(_p(dout), _p(raw), _p(scale), _p(shift), _p(dz), _p(sums), B, H, W, Cc, Ho, Wo, pk, ps, pp,
                                      int(relu), _stream()))

@@ -66,7 +66,7 @@ bool gssd_x6_f16_enabled();
 // (workgroup id mod rep), the consumers (gssd_bn_finalize_*, gssd_bn_relu_pool_*, gssd_bn_bwd_finalize_f32) add the replicas up in a
 // fixed order.  Why: device-scope fp64 atomics on one cache line are served one after the other (~8 ns each, measured round 4); the
 // persistent trunk kernels flush all their workgroups' sums at the END of the launch -- 131 k atomics on 16 lines = a 60 us serial
-// tail on a 140 us kernel (profiles/r04_thin_knockout.txt).  16 - 32 replicas make the tail 2 - 4 us.
+// tail on a 140 us kernel (profiles/r04_thin_knockout_before.txt).  16 - 32 replicas make the tail 2 - 4 us.
 __device__ __forceinline__ double* gssd_stats_replica(double* stats, int rep, int cout) {
     return rep > 1 ? stats + (size_t)((blockIdx.x + 7u * blockIdx.y + 13u * blockIdx.z) % (unsigned)rep) * (2 * (size_t)cout) : stats;
 }

@@ -60,12 +60,6 @@ extern "C" int gssd_thin_timing_read(unsigned long long* out8) {
 #else
 #define TSTAMP(k)
 #endif
-// knock-out builds (scripts/thin_knockout.py; `make thin_ko`): which part of the tile loop costs what.  Results are WRONG on purpose.
-//   1 no producer transform   2 no fragment reads   4 no MFMAs   8 trivial epilogue (no bias / batch sums / pooling)   16 no stores   32 no patch DMA
-//   64 linear tile order   128 no unit swizzle on the DMA source   256 no batch-sum atomics   512 no weight prologue
-#ifndef THIN_KO
-#define THIN_KO 0
-#endif
 
 namespace {
 
@@ -117,7 +111,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
     // (dx, channel) run, dx = k' / CIN_G (zero weights where dx > 2).  Round 4: with the contraction ordered this way the B fragments
     // of one input row (its KR shifted reads) serve the THREE output rows that touch it, so a row costs KR LDS reads instead of
     // ceil(9 CIN_G / 32) (2 instead of 5 at 16 channels per group, 3 instead of 9 at 32) and they are issued a row pair ahead of
-    // their MFMAs -- the knock-out builds put 54 of conv1_2's 199 us into fragment reads the MFMAs waited for one by one.
+    // their MFMAs -- round 4's per-phase table put 54 of conv1_2's 199 us into fragment reads the MFMAs waited for one by one.
     bf16x8 wf[3][KR][NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -128,8 +122,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
 #pragma unroll
             for (int kk = 0; kk < KR; ++kk) {
                 const int k = 32 * kk + 8 * kq, dx = k / CIN_G, c = k - dx * CIN_G;
-                wf[dy][kk][j] = (dx < 3 && !(THIN_KO & 512)) ? *reinterpret_cast<const bf16x8*>(wr + (dy * 3 + dx) * CIN_G + c)
-                                                             : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                wf[dy][kk][j] = dx < 3 ? *reinterpret_cast<const bf16x8*>(wr + (dy * 3 + dx) * CIN_G + c) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
     }
     // this lane's output channels (inside the group): cb .. cb + CPL
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
 #ifdef THIN_TIMING
     unsigned long long tacc[7] = {0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
 #endif
-    const int bperm = (gridDim.x & 7) == 0 && !(THIN_KO & 64) ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int bperm = (gridDim.x & 7) == 0 ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     for (int tile = bperm; tile < ntiles; tile += gridDim.x) {
         const int b = tile / tiles_per_img;
         const int trem = tile - b * tiles_per_img;
@@ -185,20 +178,20 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
         for (int i = g; i < NINSTR; i += 4) {
             const int pp = i * PPI + lane / UPR;
             const int py = pp / PW, pxx = pp - py * PW;
-            const int lu = (THIN_KO & 128) ? (lane % UPR) : (lane % UPR) ^ swz_col<UPR>(pxx);
+            const int lu = (lane % UPR) ^ swz_col<UPR>(pxx);
             const int iy = y0 - 1 + py, ix = x0 - 1 + pxx;
             const bool ok = pp < NPATCH && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
             const u16* src = ok ? p.in + ((size_t)(b * p.H + iy) * p.W + ix) * CIN + lu * 8 : g_zero_thin_h;
-            if (!(THIN_KO & 32)) dma16(src, patch + i * PPI * CIN);
+            dma16(src, patch + i * PPI * CIN);
         }
         TSTAMP(0)
         __syncthreads();
         TSTAMP(1)
-        if constexpr (XF && !(THIN_KO & 1)) {
+        if constexpr (XF) {
             // producer BatchNorm + ReLU once per patch element (in-image pixels only: the rest stays 0 = padding after the transform).
             // A thread always transforms the SAME eight channels (unit tid % UPR of every (256 / UPR)-th pixel; the swizzle only
             // moves where that unit sits inside the pixel), so its scale / shift live in 16 registers for the kernel's lifetime.
-            // Round 4 (knock-out builds: this pass cost 30 us of conv1_2's 199): the patch position advances by additions instead of a
+            // Round 4 (per-phase table: this pass cost 30 us of conv1_2's 199): the patch position advances by additions instead of a
             // division per element, tiles whose patch lies inside the image skip the bounds tests (wave-uniform), the arithmetic runs on
             // channel PAIRS (v_pk_fma_f32) and the ReLU on the rounded pairs (v_pk_max_i16 against 0: a negative bf16 is a negative int16;
             // -0 and negatives that round to -0 become +0 exactly like fmaxf(x, 0) followed by the rounding).
@@ -236,11 +229,11 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
         // 2 pr and 2 pr + 1 contract F[0..2] and F[1..3]; the fragments of the next pair's two new rows are read BEFORE this pair's MFMAs
         const int x = x0 + r;
         auto load_row = [&](int row, bf16x8 (&dst)[KR]) {
+            // (`wf` stays this closure's first capture, as it was while a timing arm read it here: without it hipcc emits the same epilogue
+            // with the operands of its commutative adds swapped, and the code object would no longer be the measured one byte for byte)
+            (void)wf;
 #pragma unroll
-            for (int kk = 0; kk < KR; ++kk) {
-                if (THIN_KO & 2) dst[kk] = wf[0][kk][0];
-                else dst[kk] = *reinterpret_cast<const bf16x8*>(patch + foff[kk] + row * PW * CIN);
-            }
+            for (int kk = 0; kk < KR; ++kk) dst[kk] = *reinterpret_cast<const bf16x8*>(patch + foff[kk] + row * PW * CIN);
         };
         bf16x8 F[4][KR], G[2][KR];
 #pragma unroll
@@ -265,10 +258,8 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
 #pragma unroll
                     for (int j = 0; j < NT; ++j)
 #pragma unroll
-                        for (int i = 0; i < RH; ++i) {
-                            if (THIN_KO & 4) acc[i][j][kk & 3] += (float)F[i + dy][kk][j];
-                            else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[dy][kk][j], F[i + dy][kk], acc[i][j], 0, 0, 0);
-                        }
+                        for (int i = 0; i < RH; ++i)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[dy][kk][j], F[i + dy][kk], acc[i][j], 0, 0, 0);
 #pragma unroll
             for (int kk = 0; kk < KR; ++kk) {
                 F[0][kk] = F[2][kk];
@@ -280,28 +271,6 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
             asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[RH - 1][NT - 1][3]));      // the MFMAs have retired
 #endif
             TSTAMP(6)
-            if (THIN_KO & 8) {
-#pragma unroll
-                for (int i = 0; i < RH; ++i) {
-                    const int y = y0 + rb + i;
-                    if (y >= p.H || x >= p.W) continue;
-                    u16* dst = p.out + ((size_t)(b * p.H + y) * p.W + x) * COUT + g * COUT_G + cb;
-                    if (POOL) {
-                        if ((i & 1) || (r & 1)) continue;
-                        dst = p.out + ((size_t)(b * ((p.H + 1) >> 1) + (y >> 1)) * ((p.W + 1) >> 1) + (x >> 1)) * COUT + g * COUT_G + cb;
-                    }
-                    if constexpr (CPL == 4) {
-                        if (!(THIN_KO & 16)) *reinterpret_cast<bf16x4*>(dst) = bf16x4{(__bf16)acc[i][0][0], (__bf16)acc[i][0][1], (__bf16)acc[i][0][2], (__bf16)acc[i][0][3]};
-                    } else {
-                        bf16x8 h;
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) h[c] = (__bf16)acc[i][c >> 2][c & 3];
-                        if (!(THIN_KO & 16)) *reinterpret_cast<bf16x8*>(dst) = h;
-                    }
-                    ssum[0] += acc[i][0][0];
-                }
-                continue;
-            }
             if constexpr (POOL) {
                 // GSSD_CONV_POOL2 (include/gssd_hip.h): rows (i, i + 1) of a lane and columns (r, r ^ 1) of neighbouring lanes form one
                 // pooling window (tile origins are even); batch sums over every pixel as usual, then ONE value per window and channel --
@@ -345,12 +314,12 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
                                 bf16x4 h;
 #pragma unroll
                                 for (int c = 0; c < 4; ++c) h[c] = (__bf16)flip(m[c], smask[c]);
-                                if (!(THIN_KO & 16)) *reinterpret_cast<bf16x4*>(dst) = h;
+                                *reinterpret_cast<bf16x4*>(dst) = h;
                             } else {
                                 bf16x8 h;
 #pragma unroll
                                 for (int c = 0; c < 8; ++c) h[c] = (__bf16)flip(m[c], smask[c]);
-                                if (!(THIN_KO & 16)) *reinterpret_cast<bf16x8*>(dst) = h;
+                                *reinterpret_cast<bf16x8*>(dst) = h;
                             }
                         }
                     }
@@ -397,12 +366,12 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
                             bf16x4 h;
 #pragma unroll
                             for (int c = 0; c < 4; ++c) h[c] = (__bf16)flip(mx[c], smask[c]);
-                            if (!(THIN_KO & 16)) *reinterpret_cast<bf16x4*>(dst) = h;
+                            *reinterpret_cast<bf16x4*>(dst) = h;
                         } else {
                             bf16x8 h;
 #pragma unroll
                             for (int c = 0; c < 8; ++c) h[c] = (__bf16)flip(mx[c], smask[c]);
-                            if (!(THIN_KO & 16)) *reinterpret_cast<bf16x8*>(dst) = h;
+                            *reinterpret_cast<bf16x8*>(dst) = h;
                         }
                     }
                 }
@@ -441,7 +410,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
                     const int y = y0 + rb + i + (kq & 1);
                     if (y < p.H && x < p.W) {
                         u16* dst = p.out + ((size_t)(b * p.H + y) * p.W + x) * COUT + g * COUT_G + 4 * (kq & ~1);
-                        if (!(THIN_KO & 16)) *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
+                        *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
                     }
                 }
             } else {
@@ -460,7 +429,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
                     bf16x8 h;
 #pragma unroll
                     for (int c = 0; c < 8; ++c) h[c] = (__bf16)v[c];
-                    if (!(THIN_KO & 16)) *reinterpret_cast<bf16x8*>(dst) = h;
+                    *reinterpret_cast<bf16x8*>(dst) = h;
                 }
             }
             }
@@ -475,7 +444,7 @@ __global__ __launch_bounds__(256, (COUT_G > 16 ? 2 : 3)) void conv_thin_bf16_ker
         for (int k = 0; k < 7; ++k) atomicAdd(&g_thin_timing[k], tacc[k]);
     if (tid == 0) atomicAdd(&g_thin_timing[7], 1ull);
 #endif
-    if (p.stats && !(THIN_KO & 256)) {
+    if (p.stats) {
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
             double s = (double)ssum[c], q = (double)ssq[c];

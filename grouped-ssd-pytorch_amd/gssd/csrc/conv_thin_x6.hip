@@ -30,13 +30,6 @@
 #include "common.h"
 #include "kernel_util.h"
 
-#ifndef TX6_FENCE
-#define TX6_FENCE 1
-#endif
-#ifndef TX6_KO
-#define TX6_KO 0              // knock-outs (timing only, results wrong): 1 no transform / split, 2 no MFMAs, 4 no fragment reads, 8 no stores, 16 no loads
-#endif
-
 // per-phase stamps (make thin_x6_timing; scripts/bench_thin_x6.py prints them): s_memtime deltas of wave 1 of every workgroup, summed
 #ifdef TX6_TIMING
 __device__ unsigned long long g_tx6_timing[8];
@@ -198,11 +191,6 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
         const int trem = tile - b * tiles_per_img;
         const int tyi = trem / p.tiles_x, txi = trem - tyi * p.tiles_x;
         const int y0 = tyi * TH, x0 = txi * TW;
-        if (TX6_KO & 16) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) pre[it][0] = pre[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            return;
-        }
         const float* const base = p.in + ((size_t)(b * p.H + y0 - 1) * p.W + (x0 - 1)) * CIN + gpi * CW + su * 8;     // (only dereferenced inside the image)
         const bool inside = y0 >= 1 && x0 >= 1 && y0 + TH + 1 <= p.H && x0 + TW + 1 <= p.W;
         if (inside) {
@@ -273,19 +261,14 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = pre[it][e >> 2][e & 3];
             if constexpr (XF) {
-                if (!(TX6_KO & 1)) {
-                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(xtab + su * 8), s1 = *reinterpret_cast<const f32x4*>(xtab + su * 8 + 4);
-                    const f32x4 h0 = *reinterpret_cast<const f32x4*>(xtab + CW + su * 8), h1 = *reinterpret_cast<const f32x4*>(xtab + CW + su * 8 + 4);
+                const f32x4 s0 = *reinterpret_cast<const f32x4*>(xtab + su * 8), s1 = *reinterpret_cast<const f32x4*>(xtab + su * 8 + 4);
+                const f32x4 h0 = *reinterpret_cast<const f32x4*>(xtab + CW + su * 8), h1 = *reinterpret_cast<const f32x4*>(xtab + CW + su * 8 + 4);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e)          // (out-of-image pixels hold in_pad: the transform maps it to 0 = zero padding AFTER BatchNorm + ReLU)
-                        v[e] = fmaxf(__builtin_fmaf(v[e], e < 4 ? s0[e & 3] : s1[e & 3], e < 4 ? h0[e & 3] : h1[e & 3]), 0.f);
-                }
+                for (int e = 0; e < 8; ++e)              // (out-of-image pixels hold in_pad: the transform maps it to 0 = zero padding AFTER BatchNorm + ReLU)
+                    v[e] = fmaxf(__builtin_fmaf(v[e], e < 4 ? s0[e & 3] : s1[e & 3], e < 4 ? h0[e & 3] : h1[e & 3]), 0.f);
             }
             unsigned q[3][4];
-            if (TX6_KO & 1) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) q[0][e] = q[1][e] = q[2][e] = __builtin_bit_cast(unsigned, v[2 * e]);
-            } else if constexpr (F16) {
+            if constexpr (F16) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) split2_pair(v[2 * e], v[2 * e + 1], q[0][e], q[1][e]);
             } else {
@@ -317,19 +300,14 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
-                for (int kk = 0; kk < KR; ++kk) {
-                    if (TX6_KO & 4) F[pl][kk] = wf[pl][0][kk];
-                    else F[pl][kk] = *reinterpret_cast<const bf16x8*>(planes + pl * PLANE + foff[kk] + (row0 + rho) * (PW * CW));
-                }
+                for (int kk = 0; kk < KR; ++kk) F[pl][kk] = *reinterpret_cast<const bf16x8*>(planes + pl * PLANE + foff[kk] + (row0 + rho) * (PW * CW));
             if (rho < RW) {
                 acc[rho & 3] = f32x4{0.f, 0.f, 0.f, 0.f};   // (a bias riding in the accumulator costs accuracy: the MFMA's adder truncates, and
                 accx[rho & 3] = f32x4{0.f, 0.f, 0.f, 0.f};  // the products are small against a bias of the output's size: 7.2e-7 vs 3.1e-7 on conv2_1's shape)
             }
-#if TX6_FENCE
             // keep the row's MFMAs one uninterrupted block: a vector instruction that hipcc moves between two MFMAs of one accumulator chain
             // costs the chain its forwarding path (+43 cycles per intrusion, MI355X_MICROARCH.md) -- the epilogue's instructions stay outside
             __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
                 const int o = rho - dy;
@@ -337,10 +315,6 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
                 f32x4 c = acc[o & 3], cx = accx[o & 3];
 #pragma unroll
                 for (int kk = 0; kk < KR; ++kk) {
-                    if (TX6_KO & 2) {
-                        c[kk & 3] += (float)F[0][kk][0];
-                        continue;
-                    }
                     if constexpr (F16) {
                         // h h' -> main; h l' + l' h' -> the scaled accumulator (first operand: weight planes)
                         cx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[1][dy][kk]), __builtin_bit_cast(f16x8, F[0][kk]), cx, 0, 0, 0);
@@ -359,9 +333,7 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
                 acc[o & 3] = c;
                 accx[o & 3] = cx;
             }
-#if TX6_FENCE
             __builtin_amdgcn_sched_barrier(0);
-#endif
             // output rows complete in order: row rho - 2 after patch row rho; the epilogue takes them in PAIRS (pooling windows)
             if (rho < 3 || ((rho - 2) & 1) == 0) continue;
             const int oa = rho - 3;                     // rows oa, oa + 1 are complete
@@ -398,11 +370,11 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
 #pragma unroll
                     for (int c = 0; c < 4; ++c)          // neighbouring column = neighbouring lane: DPP quad_perm [1, 0, 3, 2]
                         m[c] = fmaxf(m[c], __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, m[c]), 0xB1, 0xF, 0xF, true)));
-                    if (!(r & 1) && !(TX6_KO & 8)) {
+                    if (!(r & 1)) {
                         float* dst = p.out + ((size_t)(b * Hp + (ya >> 1)) * Wp + (x >> 1)) * COUT + co0;
                         *reinterpret_cast<f32x4*>(dst) = f32x4{flip(m[0], smask[0]), flip(m[1], smask[1]), flip(m[2], smask[2]), flip(m[3], smask[3])};
                     }
-                } else if (!(TX6_KO & 8)) {
+                } else {
                     float* dst = p.out + ((size_t)(b * p.H + ya) * p.W + x) * COUT + co0;
                     *reinterpret_cast<f32x4*>(dst) = f32x4{v0[0], v0[1], v0[2], v0[3]};
                     *reinterpret_cast<f32x4*>(dst + (size_t)p.W * COUT) = f32x4{v1[0], v1[1], v1[2], v1[3]};
@@ -428,16 +400,14 @@ __global__ __launch_bounds__(NT_, 2) void conv_thin_x6_kernel(const ThinX6Params
                     const float pm = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, m[c]), 0xB1, 0xF, 0xF, true));
                     if (pok) m[c] = fmaxf(m[c], pm);
                 }
-                if (ok0 && !(r & 1) && !(TX6_KO & 8)) {
+                if (ok0 && !(r & 1)) {
                     float* dst = p.out + ((size_t)(b * Hp + (ya >> 1)) * Wp + (x >> 1)) * COUT + co0;
                     *reinterpret_cast<f32x4*>(dst) = f32x4{flip(m[0], smask[0]), flip(m[1], smask[1]), flip(m[2], smask[2]), flip(m[3], smask[3])};
                 }
             } else {
-                if (!(TX6_KO & 8)) {
-                    float* dst = p.out + ((size_t)(b * p.H + ya) * p.W + x) * COUT + co0;
-                    if (ok0) *reinterpret_cast<f32x4*>(dst) = f32x4{v0[0], v0[1], v0[2], v0[3]};
-                    if (ok1) *reinterpret_cast<f32x4*>(dst + (size_t)p.W * COUT) = f32x4{v1[0], v1[1], v1[2], v1[3]};
-                }
+                float* dst = p.out + ((size_t)(b * p.H + ya) * p.W + x) * COUT + co0;
+                if (ok0) *reinterpret_cast<f32x4*>(dst) = f32x4{v0[0], v0[1], v0[2], v0[3]};
+                if (ok1) *reinterpret_cast<f32x4*>(dst + (size_t)p.W * COUT) = f32x4{v1[0], v1[1], v1[2], v1[3]};
             }
         }
 #pragma unroll

@@ -41,15 +41,9 @@
 #include "kernel_util.h"
 #include <cstdlib>
 
-#ifndef WX6_KO
-#define WX6_KO 0              // knock-outs (scripts/wino_x6_knockout.sh; results wrong by construction): 1 no vector work (transform / split), 2 no MFMAs,
-#endif                        // 4 no U DMA, 8 no patch loads, 16 no fragment reads
 #ifndef WX6_UR
 #define WX6_UR 3              // paired form: ring of weight-fragment sets (one xi each), WX6_UR - 1 ahead of their MFMAs
 #endif
-#ifndef WX6_LOCAL_SUM
-#define WX6_LOCAL_SUM 1       // the six products of a chunk are summed from zero and added to the running sum by the vector ALU (the bf16 MFMA's
-#endif                        // adder truncates: conv_x6.hip)
 
 namespace {
 
@@ -167,7 +161,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
             const int pos = i * 4 + j;
             const unsigned off = (s.valid >> pos) & 1 ? s.pix + (unsigned)(((i * p.W + j) * p.in_stride + ch16 * 16) * 4)
                                                       : (PSEL ? 0u : p.pad_off + (unsigned)((cb_ld + ch16 * 16) * 4));
-            if (WX6_KO & 8) continue;
             row[hf][j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(p.in) + off);
         }
     };
@@ -197,7 +190,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
     };
     // padding + producer BatchNorm + ReLU of a row, in place, once (a row serves two passes): quarter q
     auto activate_row_q = [&](Row& row, const Step& s, const XfTab& xt, const int i, const int q) {
-        if (WX6_KO & 1) return;
         const bool hasB = !(tailB && s.c == nchunks - 1);
         const int hf = q >> 1;
         const float keep = (hf && !hasB) ? 0.f : 1.f;
@@ -220,7 +212,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
     // Winograd row: t = ra + sg * rb, V = t B, three-plane split -> the operand planes of its four xi: quarter q
     // planes of a block as operand dwords: P[xi][plane] = 4 dwords = the lane's 8 k slots (dword 2 * half + e / 2 holds channels e, e + 1)
     auto make_planes_q = [&](const Row& ra, const Row& rb, const float sg, u32x4 (&P)[4][NPX], const int q) {
-        if (WX6_KO & 1) return;
         const int hf = q >> 1, e = 2 * (q & 1);
         float t0[4], t1[4];
 #pragma unroll
@@ -342,7 +333,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
         const int fo = r * 32 + ((kq ^ swz64(r)) << 3);          // fragment offset inside a 16-row block of a tile
         // U planes of (chunk c, Winograd row i) -> LDS slot: XG * NPX * TILE / 512 pieces of 1 KB, consumer wave w moves pieces w, w + 4, ..
         auto stage_U_part = [&](const int c, const int i, const int slot, const int part, const int half = 0) {      // part of NBT (-1: all)
-            if (WX6_KO & 4) return;
             const u16* src = Ug + (size_t)(PAIR ? half * nchunks + c : c) * CHUNK + i * STAGE;
             u16* dst = smem + slot * STAGE;
             constexpr int PW = STAGE / 512 / 4;       // pieces per consumer wave
@@ -514,17 +504,13 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
 #pragma unroll
                 for (int xl = 0; xl < XG; ++xl)
 #pragma unroll
-                    for (int q = 0; q < NPX; ++q) {
-                        if (WX6_KO & 16) asm volatile("" : "=v"(dst[xl][q]));
-                        else dst[xl][q] = *reinterpret_cast<const bf16x8*>(ub + (xl * NPX + q) * TILE + nb * 16 * 32);
-                    }
+                    for (int q = 0; q < NPX; ++q) dst[xl][q] = *reinterpret_cast<const bf16x8*>(ub + (xl * NPX + q) * TILE + nb * 16 * 32);
             };
             // the first tile's weight fragments are requested behind the planes' reads (the block's U planes are in LDS since barrier A): LDS
             // returns in order, so the planes are in registers when at most these XG * NPX reads are outstanding -- barrier B does not wait
             // for them, and their round trip runs beside it instead of behind it
             frags(0, u[0]);
-            if (WX6_KO & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(XG * NPX) : "memory");
+            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(XG * NPX) : "memory");
             __builtin_amdgcn_s_barrier();                 // B: the plane buffer is free for the next block
 #pragma unroll
             for (int nb = 0; nb < NBT; ++nb) {
@@ -534,19 +520,18 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
 #pragma unroll
                 for (int xl = 0; xl < XG; ++xl) {
                     const bf16x8 (&uc)[NPX] = u[nb & 1][xl];
-                    // six products, smallest first (uc: weight planes, Pc: activation planes), summed from zero
+                    // six products, smallest first (uc: weight planes, Pc: activation planes), summed from zero and added to the running sum by
+                    // the vector ALU (the bf16 MFMA's adder truncates: conv_x6.hip)
                     f32x4 s6 = zero4;
                     if constexpr (F16) {
                         // h h' from zero; h l' + l' h' from zero, entering with 1 / 2048
                         f32x4 sx = zero4;
-                        if (!(WX6_KO & 2)) {
-                            sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[1]), __builtin_bit_cast(f16x8, Pc[xl][0]), sx, 0, 0, 0);
-                            sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][1]), sx, 0, 0, 0);
-                            s6 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][0]), s6, 0, 0, 0);
-                        }
+                        sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[1]), __builtin_bit_cast(f16x8, Pc[xl][0]), sx, 0, 0, 0);
+                        sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][1]), sx, 0, 0, 0);
+                        s6 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][0]), s6, 0, 0, 0);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) s6[e] = __builtin_fmaf(sx[e], 1.f / 2048.f, s6[e]);
-                    } else if (!(WX6_KO & 2)) {
+                    } else {
                         s6 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uc[1], Pc[xl][1], s6, 0, 0, 0);
                         s6 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uc[NPX - 1], Pc[xl][0], s6, 0, 0, 0);
                         s6 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uc[0], Pc[xl][NPX - 1], s6, 0, 0, 0);
@@ -618,11 +603,9 @@ __global__ __launch_bounds__(512, 1) void conv_wino_x6_kernel(const WinoX6Params
                         if (k + UA < NK) frag(k + UA);
                         const bf16x8 (&uc)[NPX] = u[k % UR];
                         f32x4 s6 = zero4, sx = zero4;             // h h' from zero; h l' + l' h' from zero, entering with 1 / 2048
-                        if (!(WX6_KO & 2)) {
-                            sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[1]), __builtin_bit_cast(f16x8, Pc[xl][0]), sx, 0, 0, 0);
-                            sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][1]), sx, 0, 0, 0);
-                            s6 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][0]), s6, 0, 0, 0);
-                        }
+                        sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[1]), __builtin_bit_cast(f16x8, Pc[xl][0]), sx, 0, 0, 0);
+                        sx = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][1]), sx, 0, 0, 0);
+                        s6 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, uc[0]), __builtin_bit_cast(f16x8, Pc[xl][0]), s6, 0, 0, 0);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) s6[e] = __builtin_fmaf(sx[e], 1.f / 2048.f, s6[e]);
                         if (xl == 0) s0v = s6;

@@ -21,12 +21,6 @@
 
 namespace {
 
-#ifndef X6_KO
-#define X6_KO 0             // knock-outs (scripts/conv_x6_knockout.sh): 1 no transform / split, 2 no MFMAs, 4 no weight DMA, 8 no activation loads,
-#endif                      // 16 no fragment reads, 32 no LDS writes of the planes
-#ifndef X6_LOCAL_SUM
-#define X6_LOCAL_SUM 1      // the six products of a chunk are summed from zero and added to the running sum by the vector ALU (see the K loop)
-#endif
 constexpr int BM = 128, BKC = 32;
 constexpr int NP = 3;
 constexpr int A_STAGE = BM * BKC;                     // u16 elements per plane
@@ -152,7 +146,6 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
         }
     };
     auto load_req = [&](int q) {                             // request q = (pixel, half): 16 bytes per lane
-        if (X6_KO & 8) return;
         const int j = q >> 1;
         if (q & 1) asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(gv[j][1]) : "v"(src[j]) : "memory");
         else asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(gv[j][0]) : "v"(src[j]) : "memory");
@@ -171,7 +164,6 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
     };
     // quarter `part` (pixel part >> 1, channel half part & 1) of this thread's 16 values: deferred BatchNorm + ReLU, split, 8 bytes per plane
     auto finish_part = [&](int part) {
-        if (X6_KO & 1) return;
         const int j = part >> 1, hh = part & 1;
         f32x4 v = gv[j][hh];
         if (xf) {
@@ -190,7 +182,6 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
             split3_pair(v[0], v[1], h0, m0_, l0);
             split3_pair(v[2], v[3], h1, m1, l1);
         }
-        if (X6_KO & 32) return;
         u16* Ad = As + a_wr0 + j * 64 * BKC + 4 * hh;
         *reinterpret_cast<u32x2*>(Ad) = u32x2{h0, h1};
         if constexpr (F16) {
@@ -204,7 +195,6 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
     // piece q (0 .. DPW - 1) of this wave in an iteration: the first PH pieces of the iteration's list are the Y half of chunk cy, the rest the
     // X half of chunk cx; piece = (plane, wave column, column tile inside the half)
     auto dma_piece = [&](int q, int cy, int cx, int par) {
-        if (X6_KO & 4) return;
         const int idx = q * 4 + wave;
         const bool isx = idx >= PH;
         const int pc = isx ? idx - PH : idx;
@@ -226,55 +216,32 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
     auto a_load_row = [&](int i) {
         const u16* Ab = As + (wm * WTM + i * 16) * BKC + fo;
         if constexpr (F16) {
-            if (X6_KO & 16) {
-                asm volatile("" : "=v"(areg[i][0]));
-                asm volatile("" : "=v"(areg[i][2]));
-            } else {
-                areg[i][0] = *reinterpret_cast<const bf16x8*>(Ab);
-                areg[i][2] = *reinterpret_cast<const bf16x8*>(Ab + A_STAGE);
-                if constexpr (NPL == 3) areg[i][1] = *reinterpret_cast<const bf16x8*>(Ab + 2 * A_STAGE);
-            }
-            if constexpr (NPL == 2) derive(areg[i][1], areg[i][0]);
-            else if (X6_KO & 16) asm volatile("" : "=v"(areg[i][1]));
+            areg[i][0] = *reinterpret_cast<const bf16x8*>(Ab);
+            areg[i][2] = *reinterpret_cast<const bf16x8*>(Ab + A_STAGE);
+            if constexpr (NPL == 3) areg[i][1] = *reinterpret_cast<const bf16x8*>(Ab + 2 * A_STAGE);
+            else derive(areg[i][1], areg[i][0]);
             return;
         }
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
-            if (X6_KO & 16) asm volatile("" : "=v"(areg[i][pl]));
-            else areg[i][pl] = *reinterpret_cast<const bf16x8*>(Ab + pl * A_STAGE);
-        }
+        for (int pl = 0; pl < NP; ++pl) areg[i][pl] = *reinterpret_cast<const bf16x8*>(Ab + pl * A_STAGE);
     };
     auto b_load = [&](int which, int half, int parity, int jj) {
         const u16* Bb = Bh + (half * 2 + parity) * HB_ELEMS + (wn * NTH * 16 + jj * 16) * BKC + fo;
         if constexpr (F16) {
-            if (X6_KO & 16) {
-                asm volatile("" : "=v"(breg[which][0]));
-                asm volatile("" : "=v"(breg[which][2]));
-            } else {
-                breg[which][0] = *reinterpret_cast<const bf16x8*>(Bb);
-                breg[which][2] = *reinterpret_cast<const bf16x8*>(Bb + HB_PLANE);
-                if constexpr (NPL == 3) breg[which][1] = *reinterpret_cast<const bf16x8*>(Bb + 2 * HB_PLANE);
-            }
-            if constexpr (NPL == 2) derive(breg[which][1], breg[which][0]);
-            else if (X6_KO & 16) asm volatile("" : "=v"(breg[which][1]));
+            breg[which][0] = *reinterpret_cast<const bf16x8*>(Bb);
+            breg[which][2] = *reinterpret_cast<const bf16x8*>(Bb + HB_PLANE);
+            if constexpr (NPL == 3) breg[which][1] = *reinterpret_cast<const bf16x8*>(Bb + 2 * HB_PLANE);
+            else derive(breg[which][1], breg[which][0]);
             return;
         }
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
-            if (X6_KO & 16) asm volatile("" : "=v"(breg[which][pl]));
-            else breg[which][pl] = *reinterpret_cast<const bf16x8*>(Bb + pl * HB_PLANE);
-        }
+        for (int pl = 0; pl < NP; ++pl) breg[which][pl] = *reinterpret_cast<const bf16x8*>(Bb + pl * HB_PLANE);
     };
     // six products per fragment pair, smallest first (first operand: weight planes).  The bf16 MFMA's adder truncates: summing the six products
     // of a chunk from zero and adding the chunk's sum to the running sum with the vector ALU (round to nearest) keeps the result closer to
     // float64 than the fp32-MFMA kernels (3-4 x closer than accumulating in place: scripts/bench_conv_x6.py)
     auto mma_row = [&](int i, int j, int which) {
-        if (X6_KO & 2) return;
-#if X6_LOCAL_SUM
         f32x4 c = zero4;
-#else
-        f32x4 c = acc[i][j];
-#endif
         if constexpr (F16) {
             // planes 0: h, 1: h / 64, 2: (x - h) * 64 -- l6 h6', h6 l6', h h'
             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, breg[which][2]), __builtin_bit_cast(f16x8, areg[i][1]), c, 0, 0, 0);
@@ -288,30 +255,20 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(breg[which][0], areg[i][1], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(breg[which][0], areg[i][0], c, 0, 0, 0);
         }
-#if X6_LOCAL_SUM
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[i][j][e] += c[e];
-#else
-        acc[i][j] = c;
-#endif
     };
-    constexpr int NGQ = (X6_KO & 8) ? 0 : 4, NDQ = (X6_KO & 4) ? 0 : DPW, NYQ = (X6_KO & 4) ? 0 : NY;
-    // all four loads have landed; N younger DMA pieces of this wave may still be in flight
-#define X6_LOADS_WAIT(N) \
-    if (!(X6_KO & 8)) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(gv[0][0]), "+v"(gv[0][1]), "+v"(gv[1][0]), "+v"(gv[1][1]) : "n"(N))
 
     // ---- prologue: planes of chunk 0, X half of chunk 0's weights --------------------------------------------------------------------------------
     load_addr();
 #pragma unroll
     for (int q = 0; q < 4; ++q) load_req(q);
     if (xf) __syncthreads();                       // the scale / shift table
-    if (!(X6_KO & 4)) {
-        // X half of chunk 0: PH pieces over four waves (the counts differ by wave when PH = 6: everything is awaited)
-        for (int pc = wave; pc < PH; pc += 4) {
-            const int pl = pc / (2 * NTH), g8 = pc - pl * (2 * NTH);
-            const int G = (g8 / NTH) * NT + (g8 % NTH);
-            dma16(wslab + (size_t)pl * plane_elems + G * 512 + lane * 8, Bh + pl * HB_PLANE + g8 * 512);
-        }
+    // X half of chunk 0: PH pieces over four waves (the counts differ by wave when PH = 6: everything is awaited)
+    for (int pc = wave; pc < PH; pc += 4) {
+        const int pl = pc / (2 * NTH), g8 = pc - pl * (2 * NTH);
+        const int G = (g8 / NTH) * NT + (g8 % NTH);
+        dma16(wslab + (size_t)pl * plane_elems + G * 512 + lane * 8, Bh + pl * HB_PLANE + g8 * 512);
     }
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(gv[0][0]), "+v"(gv[0][1]), "+v"(gv[1][0]), "+v"(gv[1][1]));
 #pragma unroll
@@ -337,9 +294,8 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
             for (int jj = 0; jj < NTH; ++jj) {
                 if (jj + 1 == NTH && !LAST) {
                     // B1: the previous iteration's planes and X pieces are in LDS (every wave waited for its own), its table reads are done
-                    constexpr int K_B1 = NTH == 1 ? 0 : NYQ + NGQ;
-                    if (X6_KO & 64) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(K_B1) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(K_B1) : "memory");
+                    constexpr int K_B1 = NTH == 1 ? 0 : NY + 4;
+                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(K_B1) : "memory");
                 }
                 if (jj + 1 < NTH) b_load((jj + 1) & 1, 1, par ^ 1, jj + 1);
 #pragma unroll
@@ -391,33 +347,24 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
                     if (gidx == 0) {
                         __builtin_amdgcn_sched_barrier(0);
                         // B2: every wave holds chunk it's activation fragments; this wave's loads and Y pieces have landed
-                        constexpr int K_B2 = NDQ - NYQ;
-                        if (X6_KO & 64) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(K_B2) : "memory");
-                        else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(K_B2) : "memory");
-                        X6_LOADS_WAIT(DPW - NY);             // (already true: ties the load registers to the wait for the compiler)
+                        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(DPW - NY) : "memory");
+                        // all four loads have landed, DPW - NY younger DMA pieces of this wave may still be in flight (already true: ties the
+                        // load registers to the wait for the compiler)
+                        asm volatile("s_waitcnt vmcnt(%4)" : "+v"(gv[0][0]), "+v"(gv[0][1]), "+v"(gv[1][0]), "+v"(gv[1][1]) : "n"(DPW - NY));
                     }
-#ifndef X6_FIN
-#define X6_FIN 1        // 1: a quarter rides on TWO groups of MFMAs (scheduling region = groups 2k - 1, 2k); 0: on one
-#endif
                     if (NTH == 2) {
-                        if (X6_FIN) {
-                            if (gidx == 1) finish_part(0);
-                            if (gidx == 3) finish_part(1);
-                            if (gidx == 5) finish_part(2);
-                            if (gidx == 7) finish_part(3);
-                        } else {
-                            if (gidx == 1) finish_part(0);
-                            if (gidx == 2) finish_part(1);
-                            if (gidx == 4) finish_part(2);
-                            if (gidx == 5) finish_part(3);
-                        }
+                        // a quarter rides on TWO groups of MFMAs (scheduling region = groups 2k - 1, 2k)
+                        if (gidx == 1) finish_part(0);
+                        if (gidx == 3) finish_part(1);
+                        if (gidx == 5) finish_part(2);
+                        if (gidx == 7) finish_part(3);
                     } else {
                         if (gidx == 1) finish_part(0), finish_part(1);
                         if (gidx == 2) finish_part(2);
                         if (gidx == 3) finish_part(3);
                     }
                     if (gidx == NG - 1) b_load(0, 1, par, 0);   // Y of chunk it for the next iteration's first column tile
-                    if (!(X6_FIN && NTH == 2) || (gidx & 1) == 0 || gidx == NG - 1) __builtin_amdgcn_sched_barrier(0);
+                    if (NTH != 2 || (gidx & 1) == 0 || gidx == NG - 1) __builtin_amdgcn_sched_barrier(0);
                 }
             }
             if (it + 2 < nchunks) advance_ld();
@@ -431,7 +378,6 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const gssd_conv_desc p,
     iteration(nchunks, std::false_type{}, std::true_type{});
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(gv[0][0]), "+v"(gv[0][1]), "+v"(gv[1][0]), "+v"(gv[1][1]) : : "memory");
     __syncthreads();
-#undef X6_LOADS_WAIT
 
     if (p.flags & GSSD_CONV_OUT_X6PLANES) {
         // ---- merged Self_Attn projection, GSSD_CONV_OUT_X6PLANES: the epilogue stores the three bf16 planes the attention core reads

@@ -8,10 +8,6 @@
 #include "common.h"
 #include "kernel_util.h"
 
-#ifndef COL2IM_KO
-#define COL2IM_KO 0      // scripts/col2im_knockout.sh
-#endif
-
 namespace {
 
 // element type of the sampled map / of the column matrix: fp32, or bf16 for the training step of the bf16 storage mode (the forward
@@ -244,9 +240,9 @@ __global__ __launch_bounds__(192) void dcn_col2im_kernel(const float* __restrict
     }
     __syncthreads();                                                  // (drains the DMA: window, chunk 0) + table visible
 
-    for (int c = 0; c < ((COL2IM_KO & 4) ? 0 : NCH); ++c) {
+    for (int c = 0; c < NCH; ++c) {
         const float* gbuf = gb[c & 1];
-        if (wave == 0 && c + 1 < NCH && !(COL2IM_KO & 32)) stage_chunk(c + 1, gb[(c + 1) & 1]);
+        if (wave == 0 && c + 1 < NCH) stage_chunk(c + 1, gb[(c + 1) & 1]);
         // the chunk's geometry: lane q holds unit q's table row; a unit's (wave-uniform) values then come out of the registers by
         // v_readlane with a constant lane instead of one dependent LDS round trip per unit
         const int gl = lane < DC_CH ? lane : 0;
@@ -259,7 +255,6 @@ __global__ __launch_bounds__(192) void dcn_col2im_kernel(const float* __restrict
             m = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v_m), q));
         };
         if (wave < 2) {
-            if (!(COL2IM_KO & 16))
             // reduce waves: units q = wave, wave + 2, ...; three units per trip, branch free (a unit that does not contribute reads
             // window pixel 0 and multiplies by 0), so the nine wave sums and the LDS reads of a trip interleave
 #pragma unroll
@@ -297,7 +292,7 @@ __global__ __launch_bounds__(192) void dcn_col2im_kernel(const float* __restrict
                     }
                 }
             }
-        } else if (!(COL2IM_KO & 8)) {
+        } else {
             // scatter wave: read-modify-write of the accumulator window; consecutive units may hit the same pixel, so they stay in
             // order.  Branch free (a unit that does not contribute adds 0 to window pixel 0): the d(cols) reads of the whole chunk
             // hoist above the chain
@@ -320,16 +315,11 @@ __global__ __launch_bounds__(192) void dcn_col2im_kernel(const float* __restrict
         __syncthreads();                                              // chunk c consumed by all waves, chunk c + 1 landed
     }
     // ---- flush: d(x) window (one atomic per element: neighbouring tiles' windows overlap) and the three d(om) scalars per unit ----
-    // (knock-out builds for scripts/col2im_knockout.sh: 1 no d(x) flush, 2 plain stores instead of atomics, 4 no chunk loop, 8 no scatter wave,
-    // 16 no reduce waves, 32 no d(cols) DMA -- results wrong on purpose)
-    if (!(COL2IM_KO & 1))
     for (int i = wave; i < WPX; i += 3) {
         const int y = wy0 + i / WW, xx = wx0 + i % WW;
         if ((unsigned)y >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
         const float v = dw[i * 64 + lane];
-        if (COL2IM_KO & 2) {
-            if (v != 0.f) dxb[(size_t)(y * W + xx) * C] = v;
-        } else if (v != 0.f) unsafeAtomicAdd(dxb + (size_t)(y * W + xx) * C, v);
+        if (v != 0.f) unsafeAtomicAdd(dxb + (size_t)(y * W + xx) * C, v);
     }
     for (int u = tid; u < NU; u += 192) {
         if ((geo_i[u] & 48) != 48) continue;

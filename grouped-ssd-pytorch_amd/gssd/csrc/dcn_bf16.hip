@@ -12,10 +12,6 @@
 #include "common.h"
 #include "kernel_util.h"
 
-#ifndef X6_KO
-#define X6_KO 0        // knock-outs of the round-5 kernel (as csrc/dcn_x6.hip): 1 no blend, 2 no MFMAs, 4 no weight DMA, 8 no x loads, 16 no fragment reads, 32 no barrier
-#endif
-
 namespace {
 
 constexpr int BM = 128, BN = 256, BKC = 32;          // tile; channels (bf16) per K chunk: 64 B per row
@@ -250,9 +246,7 @@ __device__ unsigned long long g_dcnb_timing[8];
 #else
 #define X6_T(k)
 #endif
-#define X6_BARRIER(VM, LGKM)                                                                                   \
-    if (X6_KO & 32) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)" ::"n"(VM), "n"(LGKM) : "memory");           \
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)\n\ts_barrier" ::"n"(VM), "n"(LGKM) : "memory")
+#define X6_BARRIER(VM, LGKM) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)\n\ts_barrier" ::"n"(VM), "n"(LGKM) : "memory")
 
 __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __restrict__ x, const float* __restrict__ om,
                                                           const u16* __restrict__ wp, const float* __restrict__ bias,
@@ -377,8 +371,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
             const int cb = ld_d * cpg + ld_cc * BKC + gq * 8;
 #pragma unroll
             for (int j = 0; j < NC; ++j) {
-                int pos = pos_next[j];
-                if (X6_KO & 128) pos = (pos & 0xC0000000) | (gp + CSTEP * j);       // experiment: every tile reads the same 128 pixels (cache hits)
+                const int pos = pos_next[j];
                 const unsigned i00 = (unsigned)(pos & 0x3FFFFFFF);
                 const unsigned dxb = ((unsigned)pos >> 30) & 1u, dyb = (unsigned)pos >> 31;
                 const unsigned i10 = i00 + dyb * (unsigned)W;
@@ -389,7 +382,6 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
             }
         };
         auto corner_reqs = [&](int q0, int q1) {             // requests q0 .. q1 - 1 of the 4 NC: (cell, corner), 16 bytes = 8 channels per lane
-            if (X6_KO & 8) return;
 #pragma unroll
             for (int q = q0; q < q1; ++q) {
                 const int j = q >> 2, k = q & 3;
@@ -402,7 +394,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
         };
         // all 16 requests of this wave have landed; N younger DMA pieces may still be in flight
 #define X6_CORNERS_WAIT(N)                                                                                                            \
-    if (!(X6_KO & 8)) {                                                                                                               \
+    {                                                                                                                                 \
         if (NC == 2)                                                                                                                  \
             asm volatile("s_waitcnt vmcnt(%8)"                                                                                        \
                          : "+v"(gv[0][0]), "+v"(gv[0][1]), "+v"(gv[0][2]), "+v"(gv[0][3]), "+v"(gv[1][0]), "+v"(gv[1][1]),             \
@@ -423,7 +415,6 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
         // blend of the thread's 16 column values (fp32, the products and their order as in round 4's kernel), rounded to bf16 once
         bf16x8 pln[2];
         auto blend_all = [&]() {
-            if (X6_KO & 1) return;
 #pragma unroll
             for (int j = 0; j < NC; ++j)
 #pragma unroll
@@ -432,13 +423,11 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
                                          (float)gv[j][3][e] * gw[j][3]);
         };
         auto write_planes = [&]() {
-            if (X6_KO & 1) return;
 #pragma unroll
             for (int j = 0; j < NC; ++j) *reinterpret_cast<bf16x8*>(As + a_wr0 + j * CSTEP * BKC) = pln[j];
         };
         // weights of (chunk, half) -> half buffer (half, parity): 8 1-KiB pieces (wave column, j & 1), two per loader wave
         auto dma_half = [&](int chunk, int half, int parity) {
-            if (X6_KO & 4) return;
             u16* dst = Bh + (half * 2 + parity) * HB_ELEMS;
             const u16* src = wslab + (size_t)chunk * B_STAGE + lane * 8;
 #pragma unroll
@@ -448,7 +437,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
                 dma16(src + G * 512, dst + g8 * 512);
             }
         };
-        constexpr int ND = (X6_KO & 4) ? 0 : DPH, NL = (X6_KO & 8) ? 0 : 4 * NC;
+        constexpr int ND = DPH, NL = 4 * NC;                 // a wave's DMA pieces per half, its corner requests per chunk
 
         // prologue: table of group 0; corners of chunk 0 -> planes -> stage; X half of chunk 0; corners of chunk 1 requested
         tab_load(0);
@@ -476,7 +465,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
 #ifndef X6_GPRE
 #define X6_GPRE (2 * NC)  // corner requests of chunk it + 2 issued in front of M(it), the rest behind it (same-box sweep 0 / 4 / 8 / 12 / 16: 1.92 / 1.90 / 1.98 / 1.98 / 2.06 ms)
 #endif
-        constexpr int GPRE = X6_GPRE, NPRE = (X6_KO & 8) ? 0 : GPRE;
+        constexpr int GPRE = X6_GPRE;
         for (int it = 0; it < nchunks; ++it) {
             const int par = it & 1;
             const bool make_tab = it + 2 == tb_next && it + 2 < nchunks;      // chunk it + 2 opens a group: its table is made in front of M(it)
@@ -502,7 +491,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
                 corner_addr();                               // chunk it + 2 (past the end: the last chunk again, never used)
                 corner_reqs(0, GPRE);
                 X6_T(0)
-                X6_BARRIER(ND + NPRE, 0);                    // M(it)
+                X6_BARRIER(ND + GPRE, 0);                   // M(it)
                 X6_T(1)
                 write_planes();
                 corner_reqs(GPRE, 4 * NC);
@@ -528,21 +517,14 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
         auto a_load_row = [&](int i) {
             const u16* Ab = As + (wm * WTM + i * 16) * BKC + fo;
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                if (X6_KO & 16) asm volatile("" : "=v"(areg[i][pl]));
-                else areg[i][pl] = *reinterpret_cast<const bf16x8*>(Ab + pl * A_STAGE);
-            }
+            for (int pl = 0; pl < NP; ++pl) areg[i][pl] = *reinterpret_cast<const bf16x8*>(Ab + pl * A_STAGE);
         };
         auto b_load = [&](int which, int half, int parity, int jj) {
             const u16* Bb = Bh + (half * 2 + parity) * HB_ELEMS + (wn * NTH * 16 + jj * 16) * BKC + fo;
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                if (X6_KO & 16) asm volatile("" : "=v"(breg[which][pl]));
-                else breg[which][pl] = *reinterpret_cast<const bf16x8*>(Bb + pl * HB_PLANE);
-            }
+            for (int pl = 0; pl < NP; ++pl) breg[which][pl] = *reinterpret_cast<const bf16x8*>(Bb + pl * HB_PLANE);
         };
         auto mma_row = [&](int i, int j, int which) {
-            if (X6_KO & 2) return;
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(breg[which][0], areg[i][0], acc[i][j], 0, 0, 0);
         };
         X6_BARRIER(0, 0);                                    // P1
@@ -589,8 +571,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_bf16_v3_kernel(const u16* __re
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 X6_T(2)
-                if (X6_KO & 32) asm volatile("" ::: "memory");
-                else asm volatile("s_barrier" ::: "memory"); // E(it)
+                asm volatile("s_barrier" ::: "memory");      // E(it)
                 X6_T(3)
             }
         };

@@ -34,9 +34,6 @@
 #include "common.h"
 #include "kernel_util.h"
 
-#ifndef DCN_B_DMA
-#define DCN_B_DMA 1
-#endif
 #ifndef LD_EVERY
 #define LD_EVERY 4
 #endif
@@ -203,12 +200,11 @@ __global__ __launch_bounds__(256, 1) void dcn_fused_kernel(const float* __restri
     // One chunk = 256 MFMAs per wave (8192 matrix-pipe cycles).  Slot k = MFMA k followed by at most a few staging instructions of
     // chunk ch+1 that issue in that MFMA's 32-cycle shadow; a scheduling fence after every slot keeps hipcc from regrouping them:
     //   0..11   the second half (k 16..31) of this chunk's fragment reads         12..15 sampling-table reads of the 4 cells
-    //   16..31  16 gather loads (4 corners x 4 cells, one per slot)               32..39 8 x 16-byte loads of the next weight tile
-    //   120..127 its 8 LDS writes      160..191 blend of the 4 cells (>= 4000 cycles after their loads) + the 4 LDS writes of the next
+    //   16..31  16 gather loads (4 corners x 4 cells, one per slot)               112..143 the next weight tile: 8 LDS-DMA pieces, one per four slots
+    //   160..191 blend of the 4 cells (>= 4000 cycles after their loads) + the 4 LDS writes of the next
     //   activation tile      192 the chunk's barrier      194..205 the first half (k 0..15) of the NEXT chunk's fragment reads
-    f32x4 af[2][MT], bf[2][NT], bstage[8];
+    f32x4 af[2][MT], bf[2][NT];
     const float* stage_src = nullptr;
-    float* stage_dst = nullptr;
     float* stage_dst_w = nullptr;
     float* a_dst = nullptr;
     auto slot = [&](auto kc, auto stage_c, const float* Ab, const float* Bb, const float* Abn, const float* Bbn) {
@@ -228,12 +224,7 @@ __global__ __launch_bounds__(256, 1) void dcn_fused_kernel(const float* __restri
                 constexpr int n = (K - 16) / LD_EVERY, c = n >> 2, k = n & 3;
                 gv[c][k] = *reinterpret_cast<const f32x4*>(xbytes + (go[c][k] + cb));
             }
-#if DCN_B_DMA
             if constexpr (K >= 112 && K < 144 && (K & 3) == 0) dma16(stage_src + ((K - 112) >> 2) * 1024, stage_dst_w + ((K - 112) >> 2) * 1024);
-#else
-            if constexpr (K >= 32 && K < 40) bstage[K - 32] = *reinterpret_cast<const f32x4*>(stage_src + (K - 32) * 1024);
-            if constexpr (K >= 120 && K < 128) *reinterpret_cast<f32x4*>(stage_dst + (K - 120) * 1024) = bstage[K - 120];
-#endif
             if constexpr (K >= 160 && K < 192) {
                 constexpr int c = (K - 160) >> 3, ph = (K - 160) & 7;
                 // scalar FMAs on purpose (compiled with -fno-slp-vectorize): a packed-f32 VALU op beside an MFMA costs ~25 cycles
@@ -333,7 +324,6 @@ __global__ __launch_bounds__(256, 1) void dcn_fused_kernel(const float* __restri
             }
             cb = (unsigned)(ch_d * cpg + ch_c * BKC + gq * 4) * 4u;
             stage_src = wslab + (size_t)(ch + 1) * B_STAGE + wave * 256 + lane * 4;
-            stage_dst = Bs + (buf ^ 1) * B_STAGE + wave * 256 + lane * 4;
             stage_dst_w = Bs + (buf ^ 1) * B_STAGE + wave * 256;
             a_dst = As + (buf ^ 1) * A_STAGE + a_wr0;
             const float* Ab = As + buf * A_STAGE + wm * WTM * BKC;

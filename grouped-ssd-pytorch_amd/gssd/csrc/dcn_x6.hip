@@ -9,7 +9,7 @@
 //
 // Round 5's kernel (round 4's: one workgroup of four waves, weight planes in ONE LDS buffer, every chunk = [27 fragment reads, barrier]
 // [12 DMA pieces + 16 corner requests in a row] [192 MFMAs, the next chunk's blend behind the last two fragment rows]: 2.12 ms.  The steps
-// from there, with same-box knock-outs and per-phase timings, are in profiles/r05_dcn_x6_v2_knockout.txt and DESIGN.md section 9):
+// from there, with same-box per-phase tables and timings, are in profiles/r05_dcn_x6_v2_knockout.txt and DESIGN.md section 9):
 //   * 128 x 256 tile, K chunk = 32 channels of one tap, tap fastest (a pixel's 128-byte line is revisited by the next tap while it is in L2);
 //   * LDS: ONE activation stage (3 planes x 128 rows x 64 B = 24 KB) + the weight planes in four half buffers (X: the wave's column tiles
 //     0, 1; Y: 2, 3; two of each: 96 KB) + the sampling table of a deformable group (9 taps x 128 rows x 20 B = 23 KB) = 143 KB;
@@ -27,14 +27,10 @@
 //   * two barriers per iteration: M behind the matrix waves' first group of part B (they hold chunk it's fragments -> the stage may be
 //     overwritten; the loaders' Y pieces have landed -> the Y half may be read), E at the end.
 // 1.76 ms per launch at the GSSD++ shape (2.12 in round 4); what bounds it now: memory side alone 1.33 ms, MFMAs alone 1.08 ms, together
-// 1.76 (the two sides share LDS and the issue ports; scripts/dcn_x6_knockout.sh, scripts/dcn_x6_timing.sh).
+// 1.76 (the two sides share LDS and the issue ports; profiles/r05_dcn_x6_v2_knockout.txt, scripts/dcn_x6_timing.sh).
 #include "common.h"
 #include "kernel_util.h"
 #include <type_traits>
-
-#ifndef X6_KO
-#define X6_KO 0        // knock-outs (scripts/dcn_x6_knockout.sh): 1 no blend / split VALU, 2 no MFMAs, 4 no weight DMA, 8 no x loads, 16 no fragment reads,
-#endif                 // 32 no barrier, 128 every tile's corners from the same 128 pixels (cache hits)
 
 namespace {
 
@@ -43,19 +39,13 @@ constexpr int WTM = 64, MT = WTM / 16;
 constexpr int NP = 3;                                 // planes of the split
 constexpr int A_STAGE = BM * BKC, B_STAGE = BN * BKC;            // u16 elements per plane
 
-#ifndef X6_DMA_AUX
-#define X6_DMA_AUX 0       // cache policy bits of the weight DMA (experiments: 2 = nt)
-#endif
-
 // Operand planes (kernel_util.h): three bf16 planes (split3_pair, six MFMAs per product) or, round 6, the three-fp16-plane form (split3h_pair,
 // three MFMAs into ONE accumulator: this kernel's accumulator count leaves no room for the second set the two-plane form needs).  Same planes,
 // same LDS images, same DMA pieces in both forms.  GSSD_X6_F16=0: the bf16 planes.
 
 // wp: [3 planes][n_tiles][chunks][BN rows in staging order][32] bf16 (slot-swizzled), chunk = (d * cpg / 32 + c32) * 9 + tap
-#ifndef X6_MW
-#define X6_MW 8          // matrix waves: 8 = 2 (rows) x 4 (columns) of 64 x 64; 4 = 2 x 2 of 64 x 128 (experiment)
-#endif
-constexpr int MW = X6_MW, LW = 4, THREADS = 64 * (MW + LW), LTHREADS = 64 * LW;
+constexpr int MW = 8;    // matrix waves: 2 (rows) x 4 (columns) of 64 x 64 (2 x 2 of 64 x 128 measured the same: profiles/r06_experiments.txt)
+constexpr int LW = 4, THREADS = 64 * (MW + LW), LTHREADS = 64 * LW;
 constexpr int WCOLS = MW / 2, WTN = BN / WCOLS, NT = WTN / 16;
 constexpr int HB_ROWS = BN / 2, HB_PLANE = HB_ROWS * BKC, HB_ELEMS = NP * HB_PLANE;
 constexpr int NTH = NT / 2, NG = NTH * MT;
@@ -63,7 +53,7 @@ constexpr int TAB_N = 9 * BM;
 constexpr int LDS_BYTES = (NP * A_STAGE + 4 * HB_ELEMS) * 2 + TAB_N * 16 + TAB_N * 4;
 constexpr int TPT = (TAB_N + LTHREADS - 1) / LTHREADS;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-static_assert(MT == 4 && (NT == 4 || NT == 8) && BN == 256, "written for 128 x 256 tiles, eight or four matrix waves");
+static_assert(MT == 4 && NT == 4 && BN == 256, "written for 128 x 256 tiles, eight matrix waves");
 #ifdef X6_TIMING
 __device__ unsigned long long g_x6_timing[8];
 #ifndef X6_TWAVE
@@ -78,9 +68,7 @@ __device__ unsigned long long g_x6_timing[8];
 #else
 #define X6_T(k)
 #endif
-#define X6_BARRIER(VM, LGKM)                                                                                   \
-    if (X6_KO & 32) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)" ::"n"(VM), "n"(LGKM) : "memory");           \
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)\n\ts_barrier" ::"n"(VM), "n"(LGKM) : "memory")
+#define X6_BARRIER(VM, LGKM) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)\n\ts_barrier" ::"n"(VM), "n"(LGKM) : "memory")
 
 template <bool F16, int KSPLIT>
 __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restrict__ x, const float* __restrict__ om,
@@ -103,21 +91,11 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         const int xcd = blockIdx.x & 7;
         const int slot = (int)(blockIdx.x >> 3) / ksplit;
         kz = (int)(blockIdx.x >> 3) % ksplit;
-#ifndef X6_MAP
-#define X6_MAP 1         // 1: the column tiles of a row tile on the SAME XCD (consecutive slots: its x lines come out of one L2; same-box A/B
-                         // 1.856 vs 1.882 - 1.894 ms); 0: on neighbouring XCDs (each XCD streams one column tile's weight planes)
-#endif
-        if (X6_MAP) {                                        // (a contiguous range of row tiles per XCD -- neighbours share halo rows -- measured the same)
-            nt = slot % ntn;
-            mt = (slot / ntn) * 8 + xcd;
-        } else if (8 % ntn == 0) {
-            nt = xcd % ntn;
-            mt = slot * (8 / ntn) + xcd / ntn;
-        } else {
-            const int id = slot * 8 + xcd;
-            nt = id % ntn;
-            mt = id / ntn;
-        }
+        // the column tiles of a row tile on the SAME XCD (consecutive slots: its x lines come out of one L2; same-box A/B 1.856 vs 1.882 - 1.894 ms
+        // for neighbouring XCDs, where each XCD streams one column tile's weight planes; a contiguous range of row tiles per XCD -- neighbours
+        // share halo rows -- measured the same)
+        nt = slot % ntn;
+        mt = (slot / ntn) * 8 + xcd;
     }
     if (mt >= mtiles) return;
     const int m0 = mt * BM;
@@ -220,8 +198,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
             const int cb = ld_d * cpg + ld_cc * BKC + gq * 8;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                int pos = pos_next[j];
-                if (X6_KO & 128) pos = (pos & 0xC0000000) | (gp + 64 * j);       // experiment: every tile reads the same 128 pixels (cache hits)
+                const int pos = pos_next[j];
                 const unsigned i00 = (unsigned)(pos & 0x3FFFFFFF);
                 const unsigned dxb = ((unsigned)pos >> 30) & 1u, dyb = (unsigned)pos >> 31;
                 const unsigned i10 = i00 + dyb * (unsigned)W;
@@ -232,7 +209,6 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
             }
         };
         auto corner_reqs = [&](int q0, int q1) {             // requests q0 .. q1 - 1 of the 16: (cell, corner, half)
-            if (X6_KO & 8) return;
 #pragma unroll
             for (int q = q0; q < q1; ++q) {
                 const int j = q >> 3, k = (q >> 1) & 3;
@@ -246,7 +222,6 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         };
         // all 16 requests of this wave have landed; N younger DMA pieces may still be in flight
 #define X6_CORNERS_WAIT(N)                                                                                                              \
-    if (!(X6_KO & 8))                                                                                                                   \
     asm volatile("s_waitcnt vmcnt(%16)"                                                                                                 \
                  : "+v"(gv[0][0][0]), "+v"(gv[0][0][1]), "+v"(gv[0][1][0]), "+v"(gv[0][1][1]), "+v"(gv[0][2][0]), "+v"(gv[0][2][1]),    \
                    "+v"(gv[0][3][0]), "+v"(gv[0][3][1]), "+v"(gv[1][0][0]), "+v"(gv[1][0][1]), "+v"(gv[1][1][0]), "+v"(gv[1][1][1]),    \
@@ -267,7 +242,6 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         constexpr int NPL = F16 ? 2 : NP;                    // planes in LDS / in the packed weights
         u32x2 pln[2][2][NP];                                 // [cell][channel half][plane]
         auto blend_all = [&]() {
-            if (X6_KO & 1) return;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -291,7 +265,6 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
                 }
         };
         auto write_planes = [&]() {
-            if (X6_KO & 1) return;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -303,7 +276,6 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         // weight planes of (chunk, half) -> half buffer (half, parity): 24 (F16: 16) 1-KiB pieces (plane, wave column, j & 1), six (four) per loader wave
         constexpr int DPH = 8 * NPL / LW;
         auto dma_half = [&](int chunk, int half, int parity) {
-            if (X6_KO & 4) return;
             u16* dst = Bh + (half * 2 + parity) * HB_ELEMS;
             const u16* src = wslab + (size_t)chunk * B_STAGE + lane * 8;
 #pragma unroll
@@ -311,10 +283,10 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
                 const int p = q * LW + lwave;                // piece 0..23
                 const int pl = p >> 3, g8 = p & 7;
                 const int G = (g8 / NTH) * NT + half * NTH + (g8 % NTH);   // 16-row group of the plane's [BN][32] tile
-                dma16<X6_DMA_AUX>(src + (size_t)pl * plane_elems + G * 512, dst + pl * HB_PLANE + g8 * 512);
+                dma16(src + (size_t)pl * plane_elems + G * 512, dst + pl * HB_PLANE + g8 * 512);
             }
         };
-        constexpr int ND = (X6_KO & 4) ? 0 : DPH, NL = (X6_KO & 8) ? 0 : 16;
+        constexpr int ND = DPH, NL = 16;                     // a wave's DMA pieces per half, its corner requests per chunk
 
         // prologue: table of group 0; corners of chunk 0 -> planes -> stage; X half of chunk 0; corners of chunk 1 requested
         tab_load(d0);
@@ -342,7 +314,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
 #ifndef X6_GPRE
 #define X6_GPRE 4        // corner requests of chunk it + 2 issued in front of M(it), the rest behind it (same-box sweep 0 / 4 / 8 / 12 / 16: 1.92 / 1.90 / 1.98 / 1.98 / 2.06 ms)
 #endif
-        constexpr int GPRE = X6_GPRE, NPRE = (X6_KO & 8) ? 0 : GPRE;
+        constexpr int GPRE = X6_GPRE;
         for (int it = 0; it < nchunks; ++it) {
             const int par = it & 1;
             const bool make_tab = it + 2 == tb_next && it + 2 < nchunks;      // chunk it + 2 opens a group: its table is made in front of M(it)
@@ -368,7 +340,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
                 corner_addr();                               // chunk it + 2 (past the end: the last chunk again, never used)
                 corner_reqs(0, GPRE);
                 X6_T(0)
-                X6_BARRIER(ND + NPRE, 0);                    // M(it)
+                X6_BARRIER(ND + GPRE, 0);                    // M(it)
                 X6_T(1)
                 write_planes();
                 corner_reqs(GPRE, 16);
@@ -401,44 +373,27 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
         auto a_load_row = [&](int i) {
             const u16* Ab = As + (wm * WTM + i * 16) * BKC + fo;
             if constexpr (F16) {
-                if (X6_KO & 16) {
-                    asm volatile("" : "=v"(areg[i][0]));
-                    asm volatile("" : "=v"(areg[i][2]));
-                } else {
-                    areg[i][0] = *reinterpret_cast<const bf16x8*>(Ab);
-                    areg[i][2] = *reinterpret_cast<const bf16x8*>(Ab + A_STAGE);
-                }
+                areg[i][0] = *reinterpret_cast<const bf16x8*>(Ab);
+                areg[i][2] = *reinterpret_cast<const bf16x8*>(Ab + A_STAGE);
                 derive(areg[i][1], areg[i][0]);
                 return;
             }
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                if (X6_KO & 16) asm volatile("" : "=v"(areg[i][pl]));
-                else areg[i][pl] = *reinterpret_cast<const bf16x8*>(Ab + pl * A_STAGE);
-            }
+            for (int pl = 0; pl < NP; ++pl) areg[i][pl] = *reinterpret_cast<const bf16x8*>(Ab + pl * A_STAGE);
         };
         auto b_load = [&](int which, int half, int parity, int jj) {
             const u16* Bb = Bh + (half * 2 + parity) * HB_ELEMS + (wn * NTH * 16 + jj * 16) * BKC + fo;
             if constexpr (F16) {
-                if (X6_KO & 16) {
-                    asm volatile("" : "=v"(breg[which][0]));
-                    asm volatile("" : "=v"(breg[which][2]));
-                } else {
-                    breg[which][0] = *reinterpret_cast<const bf16x8*>(Bb);
-                    breg[which][2] = *reinterpret_cast<const bf16x8*>(Bb + HB_PLANE);
-                }
+                breg[which][0] = *reinterpret_cast<const bf16x8*>(Bb);
+                breg[which][2] = *reinterpret_cast<const bf16x8*>(Bb + HB_PLANE);
                 derive(breg[which][1], breg[which][0]);
                 return;
             }
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                if (X6_KO & 16) asm volatile("" : "=v"(breg[which][pl]));
-                else breg[which][pl] = *reinterpret_cast<const bf16x8*>(Bb + pl * HB_PLANE);
-            }
+            for (int pl = 0; pl < NP; ++pl) breg[which][pl] = *reinterpret_cast<const bf16x8*>(Bb + pl * HB_PLANE);
         };
         // the six products of one fragment pair, smallest first (first operand: weight planes, second: column planes)
         auto mma_row = [&](int i, int j, int which) {
-            if (X6_KO & 2) return;
             f32x4 c = acc[i][j];
             if constexpr (F16) {
                 // planes 0: h, 1: h / 64, 2: (x - h) * 64 -- l6 h6', h6 l6', h h'
@@ -499,8 +454,7 @@ __global__ __launch_bounds__(THREADS, 1) void dcn_x6_kernel(const float* __restr
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 X6_T(2)
-                if (X6_KO & 32) asm volatile("" ::: "memory");
-                else asm volatile("s_barrier" ::: "memory"); // E(it)
+                asm volatile("s_barrier" ::: "memory");      // E(it)
                 X6_T(3)
             }
         };
@@ -619,7 +573,7 @@ extern "C" int gssd_dcn_forward_x6_ex(const float* x, const float* om, const voi
     // the launch is bound by the request rate of the shared vector-memory / L2 path, not by the CUs of the half-empty second round.
     static const bool no_split = gssd_env_off("GSSD_DCN_X6_SPLITK");
     int ksplit = 1;
-    if (!no_split && X6_MAP) {
+    if (!no_split) {
         int dev = 0, ncu = 256;
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
@@ -632,15 +586,7 @@ extern "C" int gssd_dcn_forward_x6_ex(const float* x, const float* om, const voi
     const auto kernel = ksplit == 2 ? (f16 ? dcn_x6_kernel<true, 2> : dcn_x6_kernel<false, 2>) : (f16 ? dcn_x6_kernel<true, 1> : dcn_x6_kernel<false, 1>);
     const int ai = (f16 ? 1 : 0) + 2 * (ksplit - 1);
     if (const int rc = gssd_max_dynamic_lds(&attr_mask[ai], kernel, LDS_BYTES)) return rc;
-    int blocks;
-    if (X6_MAP) {
-        blocks = (mtiles + 7) / 8 * 8 * ntn * ksplit;
-    } else if (8 % ntn == 0) {
-        const int per = 8 / ntn;
-        blocks = ((mtiles + per - 1) / per) * 8;
-    } else {
-        blocks = ((mtiles * ntn + 7) / 8) * 8;
-    }
+    const int blocks = (mtiles + 7) / 8 * 8 * ntn * ksplit;       // the kernel's mapping: slot -> (row tile group of eight XCDs, column tile, part)
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(NTHREADS), LDS_BYTES, as_stream(stream), x, om, reinterpret_cast<const u16*>(w_packed), bias,
                        out, M, H, W, C, dg, om_stride, Cout, ntn, mtiles, gssd_dcn_packed_weight_elems_x6(Cout, C) / 5);
     GSSD_CHECK_LAUNCH();

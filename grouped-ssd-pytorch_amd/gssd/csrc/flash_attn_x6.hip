@@ -140,15 +140,11 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_x6_kernel(const u16* __
 #pragma unroll
         for (int j = 0; j < KW + VW; ++j) stage_piece(t, buf, j);
     };
-#ifndef FX6_SPREAD
-#define FX6_SPREAD 1         // 1: the next tile's pieces between the MFMA groups of this tile; 0: all of them at the tile's top
-#endif
-    stage(0, 0);
+    stage(0, 0);                                                  // (tile 0 at once; the next tile's pieces go out between the MFMA groups of this tile)
     for (int t = 0; t < ntiles; ++t) {
         const int key0 = t * BKV, buf = t & 1;
         __syncthreads();                                          // (vmcnt(0) + barrier) tile t has landed; everyone is done with tile t - 1
         const int tn = t + 1 < ntiles ? t + 1 : t;             // past the end: the last tile again, into the stage nobody reads any more
-        if (!FX6_SPREAD && t + 1 < ntiles) stage(t + 1, buf ^ 1);
         const u16* const Ks = smem + buf * STAGE;
         const u16* const Vs = Ks + NPX * K_PLANE;
 
@@ -183,14 +179,13 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_x6_kernel(const u16* __
             }
             s[kt] = acc;
             // K pieces of the next tile behind the logits of this one
-            if (FX6_SPREAD)
 #pragma unroll
-                for (int j = 0; j < KW; ++j)
-                    if (j * KT / KW == kt) {
-                        __builtin_amdgcn_sched_barrier(0);       // (keeps the piece's address arithmetic here: hoisted, it costs registers the 12-wave form does not have)
-                        stage_piece(tn, buf ^ 1, j);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+            for (int j = 0; j < KW; ++j)
+                if (j * KT / KW == kt) {
+                    __builtin_amdgcn_sched_barrier(0);           // (keeps the piece's address arithmetic here: hoisted, it costs registers the 12-wave form does not have)
+                    stage_piece(tn, buf ^ 1, j);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
         }
         // ---- online softmax over the keys of this tile (fp32, as flash_attn.hip) ----------------------------------------------------
         float mx = -INFINITY;
@@ -275,14 +270,13 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_x6_kernel(const u16* __
             for (int e = 0; e < 4; ++e) o[c][e] += F16 ? __builtin_fmaf(accx[e], 1.f / 2048.f, acc[e]) : acc[e];
             if (F16 && (c & 1)) __builtin_amdgcn_sched_barrier(0);      // (keeps hipcc from hoisting the value fragments of many tiles: the twelve-wave form has 168 registers)
             // V pieces of the next tile: VW of them dealt out over the first three quarters of the value tiles
-            if (FX6_SPREAD)
 #pragma unroll
-                for (int j = 0; j < VW; ++j)
-                    if (j * (3 * CT / 4) / VW == c) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        stage_piece(tn, buf ^ 1, KW + j);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+            for (int j = 0; j < VW; ++j)
+                if (j * (3 * CT / 4) / VW == c) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    stage_piece(tn, buf ^ 1, KW + j);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
         }
     }
     l_run += __shfl_xor(l_run, 16, 64);

@@ -31,11 +31,10 @@ __device__ __forceinline__ void static_for(F&& f) {
 // ---- memory ----
 
 // LDS-DMA (global_load_lds_dwordx4): every lane fetches 16 bytes from its own `src`; the wave's 64 pieces land contiguously (1 KiB, lane
-// order) at `lds_wave_base`, which is wave-uniform.  Counted by vmcnt.  AUX: cache policy bits of the load (experiments: 2 = nt).
-template <int AUX = 0>
+// order) at `lds_wave_base`, which is wave-uniform.  Counted by vmcnt.
 __device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, AUX);
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
 // wait until at most N of this wave's vector-memory operations (LDS-DMA pieces) are outstanding and this wave's fragment reads have

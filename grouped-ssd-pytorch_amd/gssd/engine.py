@@ -324,7 +324,7 @@ class _Plan(_PlanBase):
         self.P, self.nc = 8732, net.num_classes
         # The trunk's batch sums are kept in R replicas (include/gssd_hip.h: gssd_conv_desc::stats_rep): device-scope fp64 atomics on one
         # cache line are served serially, and the persistent trunk kernels flush every workgroup's sums at the END of the launch (conv2_1
-        # in bf16: 131 k atomics on 16 lines = 60 of its 140 us, profiles/r04_thin_knockout.txt).  R * C <= 2048 (at most 32): every
+        # in bf16: 131 k atomics on 16 lines = 60 of its 140 us, profiles/r04_thin_knockout_before.txt).  R * C <= 2048 (at most 32): every
         # trunk layer spreads its sums over 256 lines; the consumers add the replicas up in a fixed order.
         # bf16 storage mode only: the fp32 trunk kernels are compute-bound, their workgroups finish spread out and the tail is not
         # there to remove (scripts/thin_f32_probe.py: conv1_1 248 us with one array, 260 with 32 replicas, 224 without batch sums)

@@ -1,5 +1,5 @@
 """flash_attn_x6 (the fp32 mode's attention core on the bf16 matrix cores) at the GSSD++ shape: B = 32, N = 38 x 38, D = 64, C2 = 256; us per call
-incl. the split passes.  A/B builds through GSSD_LIB_PATH (scripts/flash_x6_ab.sh)."""
+incl. the split passes.  Another build of the library through GSSD_LIB_PATH."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'grouped-ssd-pytorch_amd'))
 import torch

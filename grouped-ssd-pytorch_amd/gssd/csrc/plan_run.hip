@@ -163,6 +163,7 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_pixellink_final_bwd_f32),
     GSSD_PLAN_FN(gssd_pixellink_loss_bwd_f32),
     GSSD_PLAN_FN(gssd_pixellink_decode_f32),
+    GSSD_PLAN_FN(gssd_pixellink_boxes_f32),
     GSSD_PLAN_FN(gssd_pixellink_final5_f32),
     GSSD_PLAN_FN(gssd_pixellink_final5_bwd_f32),
     GSSD_PLAN_FN(gssd_self_attn_flash_bwd_f32),

@@ -841,6 +841,28 @@ int gssd_pixellink_loss_bwd_f32(const float* out1, const float* out2, const long
 int gssd_pixellink_decode_f32(const float* out1, const float* out2, int* labels, float* comps, int* ncomp, int B, int H, int W,
                               float pixel_thr, float link_thr, int max_comp, gssd_stream_t stream);
 
+/* The box tail of mask_to_box (pixel_link/postprocess.py:124-160) exactly as pixel_link/box_geometry.py component_boxes defines it, per image:
+ * nearest up-scaling of the label map [h][w] to [Hd][Wd] (destination (Y, X) reads source (min(int(Y * (h / Hd)), h - 1), min(int(X * (w / Wd)),
+ * w - 1)), float64), per component the convex hull of its destination pixels (integer arithmetic, convex_hull's vertex order), rotating
+ * calipers in float64 (edge length = sqrt of the exact integer, the definition's sequential choice among edges), the strict filters
+ * min(size) < min_height and area < min_area, corners trunc(rint(c * 1e6) / 1e6) clamped to [0, Wd - 1] x [0, Hd - 1]; the score is the mean
+ * over the component's destination pixels (float64 sum, rounded once to fp32) of upscale_bilinear (fp32, half-pixel centres, replicated
+ * border) of the positive-class probability float32(1 / (1 + exp(float64(l0 - l1)))).  (The one place where this is not numpy's own
+ * arithmetic: component_boxes takes `.mean()` of a float32 array, which numpy sums pairwise in float32; the float64 sum here is the more
+ * accurate of the two, and the two scores agree to a few fp32 ulps, not bit for bit.)
+ * labels int32 [B][h][w] as gssd_pixellink_decode_f32 writes them (0 = background, 1 .. n connected components); out1 fp32 [B][2][h][w];
+ * ncomp int32 [B] = n per image, or NULL: the largest label of the map.  det: max_det rows (score, min x, min y, max x, max y) per image at
+ * det + b * det_stride floats (det_stride >= 5 * max_det: e.g. the class-1 plane of a [B][2][max_det][5] tensor for gssd_eval_match);
+ * the kept components in label order (by_score = 0: component_boxes' order) or in descending score order, equal scores in label order
+ * (by_score != 0: what gssd_eval_match expects of an image's rows); rows ndet[b] .. max_det - 1 zero; ndet int32 [B].  Labels above
+ * min(n, max_det) are ignored.
+ * GSSD_EINVAL, nothing launched or written: a non-positive size; h * w > 26624 (the decode's limit); Hd or Wd > 65536; Hd * Wd > 2^22
+ * (every thread walks Hd * Wd / 1024 destination pixels: 2048 x 2048 is some milliseconds; the drivers use 300 x 300); max_det outside
+ * 1 .. 1024 (the decode's statistics table); det_stride < 5 * max_det; tables beyond the 160 KB of LDS (4 h w + 2 (Hd + Wd) + 8 (h + w)
+ * bytes + 44 KB; hull stacks of 128 * min(2 h, Hd) bytes share the first term's space). */
+int gssd_pixellink_boxes_f32(const int* labels, const float* out1, const int* ncomp, float* det, long long det_stride, int* ndet, int B, int h,
+                             int w, int Hd, int Wd, double min_height, double min_area, int max_det, int by_score, gssd_stream_t stream);
+
 /* Version "2s" (pixel_link/model.py:153-155,306-356): final_1 / final_2 over nf <= 5 cascade features, the contract of
  * gssd_pixellink_final_f32 / gssd_pixellink_final_bwd_f32 with a fifth map (w1 [2][2*nf], w2 [16][16*nf]; dw1 fp64 [2*2*nf + 2],
  * dw2 fp64 [16*16*nf + 16]).  For nf <= 4 the forward and d(features) equal the four-map entry points' bit for bit. */

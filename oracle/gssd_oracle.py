@@ -227,7 +227,9 @@ def multibox_loss(loc_data, conf_data, priors, targets, threshold=0.5, negpos_ra
     loc_t = np.zeros((num, P, 4), dtype=f32)
     conf_t = np.zeros((num, P), dtype=np.int64)
     for idx in range(num):                                               # :67-72
-        t = np.asarray(targets[idx], dtype=f32)
+        t = np.asarray(targets[idx], dtype=f32).reshape(-1, 5)
+        if t.shape[0] == 0:                                              # an image without boxes (the reference cannot run one): all
+            continue                                                     # background, no positives; loc_t is not defined there
         loc_t[idx], conf_t[idx], _ = match(threshold, t[:, :-1], priors, variance, t[:, -1])
     pos = conf_t > 0                                                     # :80
     d = (loc_data[pos] - loc_t[pos]).astype(f32)                         # smooth-L1, sum (:85-88)

@@ -12,35 +12,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gpu_common import *                      # noqa: E402,F401,F403  (fixtures dev / ops)
-from gpu_common import O, ROOT                # noqa: E402
+from gpu_common import O, ROOT                # noqa: E402,F401
+from index_kernel_cases import FAR, prior_box_as_target, priors, rand_boxes      # noqa: E402  (shared with the edge registry)
 
 pytestmark = pytest.mark.gpu
-
-PRIORS = {}
-
-
-def priors(P):
-    """The first P rows of the SSD300 prior boxes (computed once)."""
-    if 'all' not in PRIORS:
-        PRIORS['all'] = O.prior_box().astype(np.float32)
-    return PRIORS['all'][:P]
-
-
-def rand_boxes(rng, n, C):
-    c = rng.uniform(0.2, 0.8, size=(n, 2))
-    wh = rng.uniform(0.05, 0.4, size=(n, 2))
-    lab = rng.integers(0, C - 1, size=(n, 1)).astype(np.float64)
-    return np.concatenate([c - wh / 2, c + wh / 2, lab], 1).astype(np.float32)
-
-
-def prior_box_as_target(pri, k, label=0.):
-    """Prior k in corner form, rounded as the kernel rounds it: its IoU with prior k is exactly 1."""
-    cx, cy, w, h = (np.float32(v) for v in pri[k])
-    hx, hy = w / np.float32(2), h / np.float32(2)
-    return np.array([[cx - hx, cy - hy, cx + hx, cy + hy, label]], np.float32)
-
-
-FAR = np.array([[5., 5., 6., 6., 0.]], np.float32)        # overlaps no prior (they lie in [0, 1]): every IoU is 0, the best prior is 0
 
 
 def scenario(name, P, B, C, seed):

@@ -9,41 +9,14 @@
 // elements, so its alignment is that of the tensors' base pointers.
 //
 // p and buf are read and written through the same pointer: none of the pointers below is __restrict__.
-#include "common.h"
-#include "kernel_util.h"
+#include "optim_util.h"
 
 namespace {
-
-constexpr int CHUNK = 4096;            // elements per chunk: 4 x 16 bytes per thread and array
-constexpr int THREADS = 256;
-constexpr int SUMSQ_MAX_BLOCKS = 1024; // partial sums every update workgroup re-reads (8 KiB, L2 resident)
-constexpr int HYPER_CAP = 8;           // param groups per launch of the step kernel (by-value kernel argument)
 
 struct HyperArgs {
     gssd_sgd_hyper h[HYPER_CAP];
     int g0, ng;                        // this launch updates the groups [g0, g0 + ng)
 };
-
-// The tensors' pointers come out of the table, where the compiler cannot see their address space: saying "global" here turns the
-// flat_load / flat_store it would emit (counted by vmcnt AND lgkmcnt) into global_load / global_store.
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) f32x4 gfloat4;
-__device__ __forceinline__ gfloat* as_global(const float* p) { return (gfloat*)p; }
-
-__device__ __forceinline__ bool aligned16(const gfloat* p) { return ((uintptr_t)p & 15) == 0; }
-
-// sum over the workgroup, the same value (to the bit) in every thread: xor-butterfly inside the waves, then the four waves in order
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__device__ __forceinline__ int chunk_len(const gssd_sgd_item& it, const gssd_sgd_chunk& ch) {
-    const int64_t left = it.n - ch.off;
-    return left < CHUNK ? (int)left : CHUNK;
-}
 
 __global__ __launch_bounds__(THREADS) void grad_sumsq_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks,
                                                              double* partials) {
@@ -69,16 +42,6 @@ __global__ __launch_bounds__(THREADS) void grad_sumsq_kernel(const gssd_sgd_item
     }
     const double s = block_sum(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// torch.nn.utils.clip_grad_norm_: total = ||g||_2, coefficient = clamp(max_norm / (total + 1e-6), max = 1) -- a NaN stays a NaN
-__device__ __forceinline__ float clip_coef(const double* partials, int n_partials, float max_norm, double* red, float& total) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n_partials; i += THREADS) s += partials[i];
-    s = block_sum(s, red);
-    total = (float)sqrt(s);
-    const float coef = max_norm / (total + 1e-6f);
-    return coef > 1.f ? 1.f : coef;
 }
 
 struct Hyper {
@@ -183,8 +146,6 @@ __global__ __launch_bounds__(THREADS) void grad_scale_clip_kernel(const gssd_sgd
     }
     for (int i = done + threadIdx.x; i < len; i += THREADS) g[i] = g[i] * c;
 }
-
-int sumsq_blocks(int n_chunks) { return n_chunks < SUMSQ_MAX_BLOCKS ? n_chunks : SUMSQ_MAX_BLOCKS; }
 
 }  // namespace
 

@@ -1,5 +1,6 @@
 """The optimizer step on the device: ``SGD`` (torch.optim.SGD's update rule and state layout, optionally with the gradient-norm clip
-fused in) and a stand-alone ``clip_grad_norm_``, each two launches of csrc/optim.hip over a device table of tensors.
+fused in) and a stand-alone ``clip_grad_norm_``, each two launches of csrc/optim.hip over a device table of tensors; ``Adam`` and
+``AdamW`` (torch's rule, state names and checkpoints, the same optional clip) on the same tables and csrc/optim_adam.hip.
 
 The reference driver's step (train_lesion_multiphase_v2.py:242-253) then runs on this library's kernels alone:
 
@@ -22,6 +23,8 @@ CHUNK = lib.gssd_optim_chunk_elems()      # elements per chunk (csrc/optim.hip)
 
 _ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('buf', np.uint64), ('n', np.int64), ('group', np.int32), ('flags', np.int32)])
 _CHUNK = np.dtype([('off', np.int64), ('item', np.int32), ('reserved', np.int32)])
+_ADAM_ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('vmax', np.uint64), ('n', np.int64),
+                       ('group', np.int32), ('flags', np.int32), ('t0', np.int64)])
 FIRST_STEP = 1
 
 
@@ -40,14 +43,14 @@ def build_chunks(numels, chunk=None):
 
 
 class _Table:
-    """Device copies of gssd_sgd_item[n] / gssd_sgd_chunk[m] and the partial-sum workspace that goes with them."""
+    """Device copies of gssd_sgd_item[n] (or gssd_adam_item[n]) / gssd_sgd_chunk[m] and the partial-sum workspace that goes with them."""
 
-    def __init__(self, rows, device):
-        # rows: (p ptr, g ptr, buf ptr, numel, group, flags), numel > 0
-        items = np.zeros(len(rows), _ITEM)
+    def __init__(self, rows, device, dtype=_ITEM):
+        # rows: (p ptr, g ptr, buf ptr, numel, group, flags), numel > 0 -- or the fields of ``dtype``, in order
+        items = np.zeros(len(rows), dtype)
         for i, r in enumerate(rows):
             items[i] = r
-        ci, co = build_chunks([r[3] for r in rows])
+        ci, co = build_chunks(items['n'])
         chunks = np.zeros(len(ci), _CHUNK)
         chunks['item'], chunks['off'] = ci, co
         self.n_chunks = len(ci)
@@ -214,6 +217,192 @@ class SGD(torch.optim.Optimizer):
         if first:
             self._table = None       # the table carries first-step flags: the next step builds one without them
         return loss
+
+
+_ADAM_OFF = ('maximize', 'foreach', 'capturable', 'differentiable', 'fused')
+_ADAM_STATE = ('exp_avg', 'exp_avg_sq', 'max_exp_avg_sq')
+
+
+class Adam(torch.optim.Optimizer):
+    """torch.optim.Adam's constructor, update rule (amsgrad and ``decoupled_weight_decay`` included), ``param_groups`` and state
+    ``step`` / ``exp_avg`` / ``exp_avg_sq`` / ``max_exp_avg_sq`` -- checkpoints go either way -- with the whole step in ONE launch of
+    csrc/optim_adam.hip for all parameters of all groups (one per eight groups beyond eight).
+
+    ``max_grad_norm`` (extra keyword) is SGD's: when set, step() is ``clip_grad_norm_(all params, max_grad_norm)`` + the update in two
+    launches, the coefficient is applied inside the update, ``p.grad`` is left UNSCALED and the total norm of the step is left in
+    ``self.grad_norm``, a 0-dim device tensor that the next step overwrites (None without max_grad_norm).
+
+    ``state[p]['step']`` is torch's default, a 0-dim float32 CPU tensor, counted on the host (the counts of one table are views of one
+    host tensor, so a step is one add_ for all of them); the kernel gets the step of every parameter from one launch argument, the
+    number of launches so far, and an offset in the table (a parameter whose gradient appears later starts at step 1, one whose gradient
+    goes away stands still).  The moments are created on a parameter's first step as 16-byte aligned slices of flat ZERO tensors (zeros
+    give torch's first step); after ``load_state_dict`` they are whatever torch put there.  A ``step`` that arrives as a DEVICE tensor
+    (a checkpoint of torch's fused or capturable form) is read back ONCE, when the table is built, and lives on the host from then on.
+    A group that turns ``amsgrad`` on later gets a zero ``max_exp_avg_sq``.
+
+    ``maximize``, ``foreach``, ``capturable``, ``differentiable`` and ``fused`` are accepted for signature compatibility and must keep
+    their defaults; ``lr`` and ``betas`` must be Python numbers.  Hyperparameters are read from ``param_groups`` at every step.
+    Parameters whose ``grad`` is None are skipped, as in torch.  After the launch every updated parameter's version counter is bumped:
+    GssdEngine re-packs its weights on that signal."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None, maximize=False,
+                 capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, max_grad_norm=None):
+        name = type(self).__name__
+        if isinstance(lr, torch.Tensor) or any(isinstance(b, torch.Tensor) for b in betas):
+            raise NotImplementedError(f'gssd.optim.{name}: lr and betas must be Python numbers (a tensor would need a host read per step)')
+        if not 0.0 <= lr:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if not 0.0 <= eps:
+            raise ValueError(f'Invalid epsilon value: {eps}')
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f'Invalid beta parameter at index 0: {betas[0]}')
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f'Invalid beta parameter at index 1: {betas[1]}')
+        if not 0.0 <= weight_decay:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        if not (isinstance(betas[0], float) and isinstance(betas[1], float)):
+            raise ValueError('betas must be either both floats or both Tensors')
+        for what, v in (('maximize', maximize), ('foreach', foreach), ('capturable', capturable), ('differentiable', differentiable),
+                        ('fused', fused)):
+            if v:
+                raise NotImplementedError(f'gssd.optim.{name}: {what}={v!r} is not implemented')
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f'Invalid max_grad_norm: {max_grad_norm}')
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=False, foreach=None,
+                        capturable=False, differentiable=False, fused=None, decoupled_weight_decay=decoupled_weight_decay)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None
+        self._launches = 0         # steps that reached the device: the kernel's `t`
+        self._table = None         # (key, _Table, its gradients' _Table for the norm or None, params, their step counts, device)
+        super().__init__(params, defaults)
+
+    # ------------------------------------------------------------------------------------------
+    def _table_key(self):
+        """Everything the device table depends on: whether the step clips, per group whether it runs AMSGrad, per parameter the storage
+        pointers of the parameter, its gradient and its three moment tensors (0: none), the identity of its step tensor, and the gradient's
+        dtype and size (a new gradient that the allocator put at the old address must be validated again)."""
+        key, state = [self.max_grad_norm is not None], self.state.get       # (.get: asking creates no state entry)
+        for g in self.param_groups:
+            key.append(bool(g['amsgrad']))
+            for p in g['params']:
+                s, grad = state(p), p.grad
+                if s:
+                    m, v, x = s.get('exp_avg'), s.get('exp_avg_sq'), s.get('max_exp_avg_sq')
+                    s = (m is not None and m.data_ptr(), v is not None and v.data_ptr(), x is not None and x.data_ptr(), id(s.get('step')))
+                else:
+                    s = None
+                if grad is None:
+                    key.append((p.data_ptr(), s))
+                else:
+                    key.append((p.data_ptr(), s, grad.data_ptr(), grad.dtype, grad.numel()))
+        return tuple(key)
+
+    def _hyper(self):
+        name = type(self).__name__
+        arr = (_lib.AdamHyper * len(self.param_groups))()
+        for gi, (h, g) in enumerate(zip(arr, self.param_groups)):
+            for what in _ADAM_OFF:
+                if g.get(what):
+                    raise NotImplementedError(f'gssd.optim.{name}: param_groups[{gi}][{what!r}]={g[what]!r} is not implemented')
+            b1, b2 = g['betas']
+            for what, v in (('lr', g['lr']), ('betas', b1), ('betas', b2), ('eps', g['eps']), ('weight_decay', g['weight_decay'])):
+                if isinstance(v, torch.Tensor):
+                    raise NotImplementedError(f'gssd.optim.{name}: {what} must be a Python number')
+            h.lr, h.beta1, h.beta2 = g['lr'], b1, b2
+            h.one_minus_beta1, h.one_minus_beta2 = 1.0 - b1, 1.0 - b2            # formed in double, rounded once
+            h.eps, h.weight_decay = g['eps'], g['weight_decay']
+            h.amsgrad, h.decoupled = bool(g['amsgrad']), bool(g.get('decoupled_weight_decay', False))
+        return arr
+
+    def _build(self):
+        todo, device = [], None
+        for gi, g in enumerate(self.param_groups):
+            for pi, p in enumerate(g['params']):
+                if p.grad is None:
+                    continue
+                what = f'param_groups[{gi}]["params"][{pi}] (shape {tuple(p.shape)})'
+                _check_tensor(p.detach(), what, device)
+                device = p.device
+                _check_tensor(p.grad, 'the gradient of ' + what, device)
+                if p.grad.shape != p.shape:
+                    raise GssdError(f'gssd.optim: the gradient of {what} has shape {tuple(p.grad.shape)}')
+                if p.numel() == 0:
+                    continue
+                s = self.state.get(p) or {}
+                for k in _ADAM_STATE:
+                    if k in s:
+                        _check_tensor(s[k], f'{k} of ' + what, device)
+                        if s[k].numel() != p.numel():
+                            raise GssdError(f'gssd.optim: {k} of {what} has {s[k].numel()} elements')
+                if s and not ('step' in s and 'exp_avg' in s and 'exp_avg_sq' in s):
+                    raise GssdError(f'gssd.optim: the state of {what} holds {sorted(s)}, not step, exp_avg and exp_avg_sq')
+                todo.append((gi, p, bool(g['amsgrad'])))
+        # new moments: 16-byte aligned slices of one flat ZERO tensor per kind (the views keep it alive).  All of them on the first step; a
+        # gradient or group that appears later gets flat tensors of its own
+        pad = lambda p: -(-p.numel() // 4) * 4                                   # noqa: E731
+        fresh = {k: [p for _, p, ams in todo if k not in (self.state.get(p) or {}) and (ams or k != 'max_exp_avg_sq')] for k in _ADAM_STATE}
+        # the step counts of the table's parameters move into ONE host tensor, state[p]['step'] becoming a 0-dim view of it, so that a
+        # step counts them all with one add_ (253 host tensors incremented one by one cost more than the launch).  A count that arrives
+        # as a device tensor is read back here, once
+        counts = torch.tensor([float(self.state[p]['step']) if self.state.get(p) else 0.0 for _, p, _ in todo], dtype=torch.float32)
+        for i, (_, p, _) in enumerate(todo):
+            self.state[p]['step'] = counts[i]
+        for k in _ADAM_STATE:                                                     # (torch's key order: step, exp_avg, exp_avg_sq, max_...)
+            if fresh[k]:
+                flat = torch.zeros(sum(pad(p) for p in fresh[k]), device=device, dtype=torch.float32)
+                o = 0
+                for p in fresh[k]:
+                    self.state[p][k] = flat[o:o + p.numel()].view(p.shape)
+                    o += pad(p)
+        rows, params = [], []
+        for i, (gi, p, ams) in enumerate(todo):
+            s = self.state[p]
+            rows.append((p.data_ptr(), p.grad.data_ptr(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr(),
+                         s['max_exp_avg_sq'].data_ptr() if ams else 0, p.numel(), gi, 0, self._launches - int(counts[i])))
+            params.append(p)
+        if not rows:
+            return None, None, params, counts, device
+        table, norm = _Table(rows, device, _ADAM_ITEM), None
+        if self.max_grad_norm is not None:
+            norm = _Table([(0, p.grad.data_ptr(), 0, p.numel(), 0, 0) for p in params], device)
+            if self.grad_norm is None:
+                self.grad_norm = torch.zeros((), device=device, dtype=torch.float32)
+        return table, norm, params, counts, device
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        hyper = self._hyper()
+        if self._table is None or self._table[0] != self._table_key():
+            built = self._build()
+            self._table = (self._table_key(),) + built
+        _, table, norm, params, steps, device = self._table
+        if table is None:
+            return loss
+        clip = norm is not None
+        with torch.cuda.device(device):
+            stream = _stream(device)
+            if clip:
+                norm.sumsq(stream)
+            check(lib.gssd_adam_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, hyper, len(hyper),
+                                         self._launches + 1, norm.partials.data_ptr() if clip else None, norm.n_partials if clip else 0,
+                                         self.max_grad_norm if clip else -1.0, self.grad_norm.data_ptr() if clip else None, stream))
+        self._launches += 1
+        steps.add_(1.0)
+        torch.autograd.graph.increment_version(params)
+        return loss
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: ``Adam`` with ``decoupled_weight_decay=True`` and weight_decay 1e-2 by default."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None, max_grad_norm=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True, max_grad_norm=max_grad_norm)
 
 
 # (device, ((grad ptr, numel), ...)) -> _Table, the few most recent: building a table costs a host-to-device copy, and a training loop

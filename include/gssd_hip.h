@@ -992,6 +992,43 @@ int gssd_sgd_step_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, 
 int gssd_grad_scale_clip_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const double* partials,
                              int n_partials, float max_norm, float* norm_out, gssd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Adam / AdamW step (csrc/optim_adam.hip): torch.optim.Adam's single-tensor rule, the gradient-norm clip fused in
+ * ------------------------------------------------------------------------------------------
+ * The same scheme: a device table of items, the same chunk list (gssd_sgd_chunk), one workgroup per chunk, 16-byte vectors where p, g, m,
+ * v (and vmax) are all 16-byte aligned at the chunk's offset.  p, m, v and vmax are updated in place; m, v and vmax start as ZEROS, which
+ * gives torch's first step exactly, so there is no first-step flag.
+ * Step counts are per item and cost neither a table upload nor a device read: the caller counts its launches, passes the count `t`
+ * (1 at its first launch) by value, and item i is at step t - items[i].t0 (>= 1), the exponent of its bias corrections. */
+typedef struct gssd_adam_item {
+    float* p;       /* parameter, n floats */
+    const float* g; /* its gradient */
+    float* m;       /* exp_avg */
+    float* v;       /* exp_avg_sq */
+    float* vmax;    /* max_exp_avg_sq; NULL: the group does not run AMSGrad */
+    int64_t n;
+    int32_t group;
+    int32_t flags;  /* reserved, 0 */
+    int64_t t0;     /* launch count of the caller when this item was at step 0 (negative after a loaded checkpoint) */
+} gssd_adam_item;
+/* One param group, a HOST-side argument read during the call.  lr and the betas are doubles because the bias corrections are formed
+ * from them in fp64 (1 - fp32(0.999) is 4.7e-5 off 1 - 0.999); one_minus_beta* are 1 - beta* formed in double by the caller and then
+ * rounded, the weights of g and g^2 in the moments.  decoupled: 0 = Adam (weight decay joins the gradient), 1 = AdamW. */
+typedef struct gssd_adam_hyper {
+    double lr, beta1, beta2;
+    float one_minus_beta1, one_minus_beta2, eps, weight_decay;
+    int32_t amsgrad, decoupled;
+} gssd_adam_hyper;
+/* The clip coefficient c as in gssd_sgd_step_f32 (max_norm < 0: c = 1, partials and norm_out are not touched; the partial sums come
+ * from gssd_grad_sumsq_f32 over a gssd_sgd_item table of the same gradients).  Per workgroup, in fp64 and rounded to fp32 once:
+ * bc1 = 1 - beta1^step, step_size = lr / bc1, sqrt(bc2) = sqrt(1 - beta2^step), decay = 1 - lr weight_decay.  Then per element, in fp32:
+ *   g' = c g (+ weight_decay p: Adam);   p *= decay (AdamW);   m = beta1 m + (1 - beta1) g';   v = beta2 v + (1 - beta2) g' g'
+ *   vh = v, or vmax = max(vmax, v) with amsgrad;   p -= step_size m / (sqrt(vh) / sqrt(bc2) + eps)
+ * The gradients are left as they are; a NaN gradient or norm propagates.  More than 8 groups take several launches; only the first
+ * writes norm_out. */
+int gssd_adam_step_f32(const gssd_adam_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const gssd_adam_hyper* hyper, int n_groups,
+                       int64_t t, const double* partials, int n_partials, float max_norm, float* norm_out, gssd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

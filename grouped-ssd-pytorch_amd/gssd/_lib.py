@@ -236,6 +236,7 @@ SIGNATURES = {
     'gssd_sgd_step_f32': (c_i, [c_fp, c_fp, c_i, C.POINTER(SgdHyper), c_i, c_fp, c_i, c_f, c_fp, c_fp]),
     'gssd_grad_scale_clip_f32': (c_i, [c_fp, c_fp, c_i, c_fp, c_i, c_f, c_fp, c_fp]),
     'gssd_adam_step_f32': (c_i, [c_fp, c_fp, c_i, C.POINTER(AdamHyper), c_i, c_i64, c_fp, c_i, c_f, c_fp, c_fp]),
+    'gssd_avg_update_f32': (c_i, [c_fp, c_fp, c_i, c_f, c_fp, c_fp, c_fp]),
 }
 
 

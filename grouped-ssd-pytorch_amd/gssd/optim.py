@@ -1,6 +1,9 @@
 """The optimizer step on the device: ``SGD`` (torch.optim.SGD's update rule and state layout, optionally with the gradient-norm clip
 fused in) and a stand-alone ``clip_grad_norm_``, each two launches of csrc/optim.hip over a device table of tensors; ``Adam`` and
-``AdamW`` (torch's rule, state names and checkpoints, the same optional clip) on the same tables and csrc/optim_adam.hip.
+``AdamW`` (torch's rule, state names and checkpoints, the same optional clip) on the same tables and csrc/optim_adam.hip; and what a
+training loop keeps next to its optimizer, ``AveragedModel`` (torch.optim.swa_utils.AveragedModel's layout and checkpoints: an EMA or
+the equal SWA average of the weights, every tensor in ONE launch of csrc/optim_avg.hip, the update count on the device) with an
+``update_bn`` that works on this engine (torch's sets ``momentum = None``, which the launch plans cannot take).
 
 The reference driver's step (train_lesion_multiphase_v2.py:242-253) then runs on this library's kernels alone:
 
@@ -11,7 +14,9 @@ The reference driver's step (train_lesion_multiphase_v2.py:242-253) then runs on
 Nothing here reads back to the host.  There is no CPU fallback: a parameter or gradient that is not a contiguous fp32 device tensor
 raises GssdError.
 """
+import copy
 import ctypes as C
+import itertools
 
 import numpy as np
 import torch
@@ -25,7 +30,9 @@ _ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('buf', np.uint64), ('n', 
 _CHUNK = np.dtype([('off', np.int64), ('item', np.int32), ('reserved', np.int32)])
 _ADAM_ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('vmax', np.uint64), ('n', np.int64),
                        ('group', np.int32), ('flags', np.int32), ('t0', np.int64)])
+_AVG_ITEM = np.dtype([('dst', np.uint64), ('src', np.uint64), ('n', np.int64), ('kind', np.int32), ('reserved', np.int32)])
 FIRST_STEP = 1
+AVG_LERP, AVG_COPY32, AVG_COPY64 = 0, 1, 2     # gssd_avg_item.kind
 
 
 def build_chunks(numels, chunk=None):
@@ -64,10 +71,11 @@ class _Table:
         check(lib.gssd_grad_sumsq_f32(self.items.data_ptr(), self.chunks.data_ptr(), self.n_chunks, partials.data_ptr(), stream))
 
 
-def _check_tensor(t, what, device=None):
-    if not isinstance(t, torch.Tensor) or t.layout != torch.strided or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+def _check_tensor(t, what, device=None, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or t.layout != torch.strided or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         d = f'{t.layout}, {t.device}, {t.dtype}, shape {tuple(t.shape)}, strides {t.stride() if t.layout == torch.strided else None}'
-        raise GssdError(f'gssd.optim: {what} must be a contiguous fp32 tensor on the MI355X (got {d}); there is no CPU fallback')
+        name = 'fp32' if dtype == torch.float32 else str(dtype).replace('torch.', '')
+        raise GssdError(f'gssd.optim: {what} must be a contiguous {name} tensor on the MI355X (got {d}); there is no CPU fallback')
     if device is not None and t.device != device:
         raise GssdError(f'gssd.optim: {what} is on {t.device}, the other tensors on {device}')
 
@@ -450,3 +458,205 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
                                            table.n_partials, float(max_norm), norm.data_ptr(), stream))
     torch.autograd.graph.increment_version(grads)
     return norm
+
+
+# ----------------------------------------------------------------------------------------------
+# averaged weights
+# ----------------------------------------------------------------------------------------------
+def _avg_kind(a, lerp):
+    if a.dtype == torch.float32:
+        return AVG_LERP if lerp else AVG_COPY32
+    return AVG_COPY64           # (anything that is not fp32 or int64 is refused by _AvgTable)
+
+
+def _model_tensors(model):
+    """list(model.parameters()), list(model.buffers()) -- the same tensors in the same order, duplicates removed by identity -- in ONE
+    walk of the module tree: the two generator walks cost more host time on this network than everything else in an update."""
+    ps, bs, seen = [], [], set()
+    for m in model.modules():
+        for t in m._parameters.values():
+            if t is not None and id(t) not in seen:
+                seen.add(id(t))
+                ps.append(t)
+        for t in m._buffers.values():
+            if t is not None and id(t) not in seen:
+                seen.add(id(t))
+                bs.append(t)
+    return ps, bs
+
+
+def _avg_key(pairs):
+    """Everything a table of (kind, dst, src, what) pairs depends on: kinds, storage pointers, sizes and dtypes (a new tensor that the
+    allocator put at the old address must be validated again)."""
+    return tuple((k, a.data_ptr(), b.data_ptr(), a.numel(), b.numel(), a.dtype, b.dtype) for k, a, b, _ in pairs)
+
+
+class _AvgTable:
+    """Device copies of gssd_avg_item[n] / gssd_sgd_chunk[m] for (kind, dst, src, what) pairs, the ticket word that goes with them, and the
+    tensors one launch writes.  Every pair is validated before anything is built: nothing is written when one is refused."""
+
+    def __init__(self, pairs, count):
+        rows, self.written, device = [], [], None
+        for i, (kind, a, b, what) in enumerate(pairs):
+            what = f'{what} (pair {i} of the launch, shape {tuple(a.shape)})'
+            dtype = torch.int64 if kind == AVG_COPY64 else torch.float32
+            _check_tensor(a, 'the averaged ' + what, device, dtype)
+            device = a.device
+            _check_tensor(b, 'the source ' + what, device, dtype)
+            if a.shape != b.shape:
+                raise GssdError(f'gssd.optim: the averaged {what} has shape {tuple(a.shape)}, the source {tuple(b.shape)}')
+            if a.numel():
+                rows.append((a.data_ptr(), b.data_ptr(), a.numel(), kind, 0))
+                self.written.append(a)
+        _check_tensor(count, 'n_averaged', device, torch.int64)
+        self.written.append(count)
+        self.count, self.device = count, count.device
+        self.table = _Table(rows, self.device, _AVG_ITEM) if rows else None
+        self.ticket = torch.zeros(1, device=self.device, dtype=torch.int32)
+
+    def launch(self, w):
+        """One update with weight ``w`` of the source (negative: 1 / (count + 1)); without items only the count moves."""
+        if self.table is None:
+            self.count.add_(1)
+            return
+        t = self.table
+        with torch.cuda.device(self.device):
+            check(lib.gssd_avg_update_f32(t.items.data_ptr(), t.chunks.data_ptr(), t.n_chunks, w, self.count.data_ptr(),
+                                          self.ticket.data_ptr(), _stream(self.device)))
+        torch.autograd.graph.increment_version(self.written)
+
+
+class AveragedModel(torch.nn.Module):
+    """torch.optim.swa_utils.AveragedModel's layout -- ``module`` (a deep copy of the model), the 0-dim int64 buffer ``n_averaged``,
+    ``forward`` delegating to ``module``, the same ``state_dict()`` keys, so checkpoints go either way -- with ``update_parameters`` as
+    ONE launch of csrc/optim_avg.hip over all parameters and buffers.
+
+    ``ema_decay`` (extra keyword): None gives torch's default, the equal (SWA) average ``a += (b - a) / (n_averaged + 1)``; a Python
+    number in [0, 1] gives the EMA ``a = lerp(a, b, 1 - ema_decay)`` of ``get_ema_multi_avg_fn(ema_decay)``.  It is a plain attribute read
+    at every update, so a warm-up schedule sets it per call; a tensor raises NotImplementedError (it would need a host read).  ``avg_fn``
+    and ``multi_avg_fn`` must stay None: an arbitrary Python function cannot run inside the kernel -- use ``ema_decay``.  ``device`` must
+    be None or the model's device; ``n_averaged`` lives on the model's device (torch leaves it on the CPU unless told otherwise).
+
+    The first update (``n_averaged == 0``) copies the source, later ones average: parameters always, float buffers too with
+    ``use_buffers=True``; with ``use_buffers=False`` every buffer is copied from the source (torch's rule).  The count is read and
+    incremented ON THE DEVICE by the same launch and never read by the host: ``n_averaged.zero_()`` makes the next update a first one.
+    Parameters are paired positionally and buffers positionally, duplicates removed by identity as ``parameters()`` / ``buffers()`` do;
+    empty tensors are skipped.
+
+    One deviation from torch: integer buffers (``num_batches_tracked``) are COPIED from the source in every mode.  torch passes them
+    through the averaging function with ``use_buffers=True``, in float arithmetic truncated back to int64, which leaves a counter that
+    counts nothing.
+
+    Every tensor must be a contiguous fp32 (int64 for the copied counters) device tensor of the source's shape on one device: GssdError
+    otherwise, before anything is written.  After the launch every written tensor's version counter is bumped: GssdEngine re-packs its
+    weights on that signal."""
+
+    def __init__(self, model, device=None, avg_fn=None, multi_avg_fn=None, use_buffers=False, *, ema_decay=None):
+        super().__init__()
+        if avg_fn is not None or multi_avg_fn is not None:
+            raise NotImplementedError('gssd.optim.AveragedModel: avg_fn / multi_avg_fn cannot run inside the kernel; ema_decay=d gives '
+                                      'get_ema_multi_avg_fn(d), ema_decay=None the equal SWA average')
+        first = next(itertools.chain(model.parameters(), model.buffers()), None)
+        model_device = torch.device('cpu') if first is None else first.device
+        if device is not None:
+            d = torch.device(device)
+            if d.type != model_device.type or (d.index is not None and d.index != model_device.index):
+                raise ValueError(f'gssd.optim.AveragedModel: device={device!r}, but the model is on {model_device} (move the model first)')
+        self.module = copy.deepcopy(model)
+        self.register_buffer('n_averaged', torch.tensor(0, dtype=torch.long, device=model_device))
+        self.avg_fn = None
+        self.multi_avg_fn = None
+        self.use_buffers = use_buffers
+        self.ema_decay = ema_decay
+        self._weight()
+        self._table = None         # (key, _AvgTable)
+
+    def forward(self, *args, **kwargs):
+        return self.module(*args, **kwargs)
+
+    def _weight(self):
+        """The kernel's ``w``: 1 - ema_decay formed in double (the binding rounds it once), or -1 for the SWA rule."""
+        d = self.ema_decay
+        if d is None:
+            return -1.0
+        if isinstance(d, torch.Tensor):
+            raise NotImplementedError('gssd.optim.AveragedModel: ema_decay must be a Python number (a tensor would need a host read)')
+        if not 0.0 <= d <= 1.0:
+            raise ValueError(f'Invalid decay value {d} provided. Please provide a value in [0,1] range.')
+        return 1.0 - d
+
+    def _pairs(self, model):
+        """(kind, averaged tensor, source tensor, what it is) in launch order: parameters, then buffers."""
+        (pa, ba), (pb, bb) = _model_tensors(self.module), _model_tensors(model)
+        if len(pa) != len(pb) or len(ba) != len(bb):
+            raise GssdError(f'gssd.optim.AveragedModel: the source model has {len(pb)} parameters and {len(bb)} buffers, the averaged '
+                            f'one {len(pa)} and {len(ba)}')
+        lerp = self.use_buffers
+        return [(AVG_LERP, a, b, 'parameter') for a, b in zip(pa, pb)] + [(_avg_kind(a, lerp), a, b, 'buffer') for a, b in zip(ba, bb)]
+
+    def _table_key(self, model):
+        return (self.n_averaged.data_ptr(),) + _avg_key(self._pairs(model))
+
+    @torch.no_grad()
+    def update_parameters(self, model):
+        w = self._weight()
+        pairs = self._pairs(model)
+        key = (self.n_averaged.data_ptr(),) + _avg_key(pairs)
+        if self._table is None or self._table[0] != key:
+            self._table = (key, _AvgTable(pairs, self.n_averaged))
+        self._table[1].launch(w)
+
+
+@torch.no_grad()
+def update_bn(loader, model, device=None):
+    """torch.optim.swa_utils.update_bn: one pass over ``loader`` that leaves in every BatchNorm of ``model`` the equal average of the
+    batches' statistics (``momentum = None`` in torch's words) and ``num_batches_tracked`` at the number of batches.
+
+    torch's own function sets ``momentum = None``, which the launch plans cannot take, and a different constant momentum per batch would
+    build and keep a plan per value.  Here every momentum is the constant 1.0 during the pass, so that each train-mode forward leaves
+    exactly ITS batch's statistics in ``running_mean`` / ``running_var``; one launch of csrc/optim_avg.hip per batch then folds them into
+    fp32 accumulators by the SWA rule, acc += (stat - acc) / k with the count k on the device -- term for term torch's cumulative
+    average -- and after the last batch one more launch copies the accumulators back.  Momenta and the training flag are restored on the
+    way out, also when a forward raises.  Momentum 1.0 is one more plan key: the pass builds one extra train-mode plan per batch size,
+    once; a second pass reuses it."""
+    bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    if not bns:
+        return
+    momenta = [m.momentum for m in bns]
+    was_training = model.training
+    for m in bns:
+        m.reset_running_stats()
+    stats = [t for m in bns for t in (m.running_mean, m.running_var) if t is not None]
+    try:
+        for m in bns:
+            m.momentum = 1.0
+        model.train()
+        fold = unfold = None
+        for input in loader:
+            if isinstance(input, (list, tuple)):
+                input = input[0]
+            if device is not None:
+                input = input.to(device)
+            model(input)
+            if not stats:
+                continue
+            key = _avg_key([(AVG_LERP, t, t, '') for t in stats])
+            if fold is None or fold[0] != key:
+                # the accumulators: 16-byte aligned slices of one flat tensor; a statistic whose storage moved keeps its accumulator
+                if fold is None:
+                    pad = lambda t: -(-t.numel() // 4) * 4                      # noqa: E731
+                    flat = torch.zeros(sum(pad(t) for t in stats), device=stats[0].device, dtype=torch.float32)
+                    count = torch.zeros((), device=stats[0].device, dtype=torch.int64)
+                    accs, o = [], 0
+                    for t in stats:
+                        accs.append(flat[o:o + t.numel()].view(t.shape))
+                        o += pad(t)
+                fold = (key, _AvgTable([(AVG_LERP, a, t, 'running statistic') for a, t in zip(accs, stats)], count))
+                unfold = _AvgTable([(AVG_COPY32, t, a, 'running statistic') for a, t in zip(accs, stats)], torch.zeros_like(count))
+            fold[1].launch(-1.0)
+        if unfold is not None:
+            unfold.launch(-1.0)
+    finally:
+        for m, mom in zip(bns, momenta):
+            m.momentum = mom
+        model.train(was_training)

@@ -1029,6 +1029,31 @@ typedef struct gssd_adam_hyper {
 int gssd_adam_step_f32(const gssd_adam_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const gssd_adam_hyper* hyper, int n_groups,
                        int64_t t, const double* partials, int n_partials, float max_norm, float* norm_out, gssd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Averaged weights (csrc/optim_avg.hip): torch.optim.swa_utils.AveragedModel's update, EMA or the equal SWA average, in one launch
+ * ------------------------------------------------------------------------------------------
+ * The same scheme: a device table of items, the same chunk list (gssd_sgd_chunk; `off` counts elements of the item's kind), one
+ * workgroup per chunk, 16-byte vectors where dst and src are both 16-byte aligned at the chunk's offset, element by element otherwise.
+ * dst is updated in place; src is only read. */
+#define GSSD_AVG_LERP 0   /* fp32: dst = lerp(dst, src, w) as torch writes it: w < 0.5 ? dst + w (src - dst) : src - (src - dst) (1 - w) */
+#define GSSD_AVG_COPY32 1 /* dst = src, n 4-byte elements (a buffer kept in sync) */
+#define GSSD_AVG_COPY64 2 /* dst = src, n 8-byte elements (num_batches_tracked) */
+typedef struct gssd_avg_item {
+    void* dst;       /* the averaged tensor, n elements */
+    const void* src; /* the source model's tensor */
+    int64_t n;
+    int32_t kind;    /* GSSD_AVG_* */
+    int32_t reserved;
+} gssd_avg_item;
+/* n = *n_averaged is read on the device by every workgroup before it writes anything.  n == 0: every LERP item is a copy (torch's first
+ * update), whatever w is.  Otherwise 0 <= w <= 1: EMA, w = 1 - decay formed in double by the caller and rounded once; w < 0: SWA, the
+ * device forms w = 1 / (n + 1) in fp32.  w > 1 (or a NaN) is refused.  The same launch leaves *n_averaged = n + 1, stored by the
+ * workgroup that finishes last: `ticket` is one 32-bit word that belongs to the table, zero before the first launch and zero again after
+ * every launch, on which the workgroups count themselves off.  The host never reads the count, and a count the caller sets to zero
+ * makes the next launch a first update.  Launches that share a ticket word or a count must follow each other on one stream. */
+int gssd_avg_update_f32(const gssd_avg_item* items, const gssd_sgd_chunk* chunks, int n_chunks, float w, int64_t* n_averaged,
+                        uint32_t* ticket, gssd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@ fused in) and a stand-alone ``clip_grad_norm_``, each two launches of csrc/optim
 ``AdamW`` (torch's rule, state names and checkpoints, the same optional clip) on the same tables and csrc/optim_adam.hip; and what a
 training loop keeps next to its optimizer, ``AveragedModel`` (torch.optim.swa_utils.AveragedModel's layout and checkpoints: an EMA or
 the equal SWA average of the weights, every tensor in ONE launch of csrc/optim_avg.hip, the update count on the device) with an
-``update_bn`` that works on this engine (torch's sets ``momentum = None``, which the launch plans cannot take).
+``update_bn`` that works on this engine (torch's sets ``momentum = None``, which the launch plans cannot take); and ``grad_stats`` /
+``GradMonitor`` (gssd/grad_stats.py, re-exported here): per-parameter norms, maxima and non-finite counts in two launches.
 
 The reference driver's step (train_lesion_multiphase_v2.py:242-253) then runs on this library's kernels alone:
 
@@ -660,3 +661,8 @@ def update_bn(loader, model, device=None):
         for m, mom in zip(bns, momenta):
             m.momentum = mom
         model.train(was_training)
+
+
+# per-parameter gradient / weight statistics on the same tables (gssd/grad_stats.py, csrc/optim_stats.hip), re-exported here: they sit
+# in the training loop between backward() and step() like everything above
+from .grad_stats import GradMonitor, GradStats, grad_stats      # noqa: E402,F401

@@ -1054,6 +1054,27 @@ typedef struct gssd_avg_item {
 int gssd_avg_update_f32(const gssd_avg_item* items, const gssd_sgd_chunk* chunks, int n_chunks, float w, int64_t* n_averaged,
                         uint32_t* ticket, gssd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-tensor statistics (csrc/optim_stats.hip): the norms check_grad_norm() reads tensor by tensor, and where the non-finite values are
+ * ------------------------------------------------------------------------------------------
+ * The same scheme: a device table of gssd_sgd_item -- only p, g and n are read; p or g may be NULL, n may be 0 -- and the chunk list that
+ * goes with it, one workgroup per chunk, 16-byte vectors where the chunk of an array is 16-byte aligned, element by element otherwise.
+ * Nothing is written but the workspace and `out`.  Two launches, no atomics, no host read; every sum runs in a fixed order, so the
+ * table is the same to the bit from run to run.
+ *   launch 1 leaves in `workspace` one 32-byte record per chunk {double sumsq_g, sumsq_p; float amax_g, amax_p; uint32 nf_g, nf_p}:
+ *     sumsq  the sum of x * x with the square formed in fp64 (exact for every fp32 x, subnormals and 1e30 alike), IEEE semantics:
+ *            an inf makes it inf, a NaN makes it NaN;
+ *     amax   the largest |x| over the FINITE elements (0: there is none);   nf  the number of non-finite elements;
+ *   launch 2 folds the records of item i, the chunks item_chunk0[i] .. item_chunk0[i + 1] (a DEVICE prefix of n_items + 1 ints, the
+ *     last one n_chunks), into row i of out, a [n_items + 1][8] fp64 matrix with the columns
+ *       0 g_sumsq   1 g_norm = sqrt(col 0)   2 g_absmax   3 g_nonfinite   4 p_sumsq   5 p_norm   6 p_absmax   7 p_nonfinite
+ *     (counts and maxima are exact in fp64), and ALL records into row n_items, the totals: sum / sqrt / max / sum.
+ * An item without chunks (n = 0) or with a NULL pointer gets zeros in the columns concerned.  n_chunks = 0 is valid: only the fold
+ * runs and writes zeros (chunks and workspace may then be NULL). */
+long long gssd_tensor_stats_workspace_bytes(int n_chunks); /* 32 * n_chunks */
+int gssd_tensor_stats_f32(const gssd_sgd_item* items, int n_items, const gssd_sgd_chunk* chunks, int n_chunks, const int* item_chunk0,
+                          void* workspace, double* out, gssd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,18 @@ class AdamHyper(C.Structure):
                 ('weight_decay', c_f), ('amsgrad', C.c_int32), ('decoupled', C.c_int32)]
 
 
+class LarsHyper(C.Structure):
+    """struct gssd_lars_hyper: one param group's hyperparameters, a host-side argument of gssd_lars_step_f32."""
+    _fields_ = [('lr', c_d), ('weight_decay', c_d), ('trust_coefficient', c_d), ('eps', c_d), ('momentum', c_f), ('dampening', c_f),
+                ('nesterov', C.c_int32), ('adapt', C.c_int32)]
+
+
+class LambHyper(C.Structure):
+    """struct gssd_lamb_hyper: one param group's hyperparameters, a host-side argument of gssd_lamb_step_f32."""
+    _fields_ = [('lr', c_d), ('beta1', c_d), ('beta2', c_d), ('one_minus_beta1', c_f), ('one_minus_beta2', c_f), ('eps', c_f),
+                ('weight_decay', c_f), ('bias_correction', C.c_int32), ('adapt', C.c_int32)]
+
+
 OUT_NHWC, OUT_TRANSPOSED, OUT_HEADS, OUT_SPLIT_T = 0, 1, 2, 3
 CONV_OUT_F32, CONV_OUTB_BF16_PERM32, CONV_HEADS_SLICES, CONV_POOL2, CONV_RESID_F32, CONV_F16_OK = 1, 2, 4, 8, 16, 32
 CONV_IN_NCHW3, CONV_OUT_GROUPCAT, CONV_OUT_X6PLANES, CONV_RESID_XF = 64, 128, 256, 512
@@ -239,6 +251,9 @@ SIGNATURES = {
     'gssd_avg_update_f32': (c_i, [c_fp, c_fp, c_i, c_f, c_fp, c_fp, c_fp]),
     'gssd_tensor_stats_workspace_bytes': (C.c_longlong, [c_i]),
     'gssd_tensor_stats_f32': (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp]),
+    'gssd_lars_workspace_bytes': (C.c_longlong, [c_i]),
+    'gssd_lars_step_f32': (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, C.POINTER(LarsHyper), c_i, c_fp, c_fp, c_i, c_f, c_fp, c_fp, c_fp]),
+    'gssd_lamb_step_f32': (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, C.POINTER(LambHyper), c_i, c_i64, c_fp, c_fp, c_i, c_f, c_fp, c_fp, c_fp]),
 }
 
 

@@ -1,6 +1,6 @@
-// What the optimizer kernels (optim.hip: clip + SGD; optim_adam.hip: Adam / AdamW) share: the chunk scheme, the global-address-space
-// casts, the bit-identical workgroup sum and the clip coefficient that every workgroup derives from the same partial sums.
-// Everything has internal linkage: each of the two files carries its own copy.
+// What the optimizer kernels (optim.hip: clip + SGD; optim_adam.hip: Adam / AdamW; optim_lars.hip: LARS / LAMB) share: the chunk scheme,
+// the global-address-space casts, the bit-identical workgroup sum and the clip coefficient that every workgroup derives from the same
+// partial sums.  Everything has internal linkage: each of the files carries its own copy.
 #pragma once
 #include "common.h"
 #include "kernel_util.h"
@@ -26,6 +26,16 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// block_sum for two sums behind one barrier (optim_lars.hip): red is [2][4]
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[4]) {
+    a = wave_sum(a);
+    b = wave_sum(b);
+    if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = a, red[1][threadIdx.x >> 6] = b;
+    __syncthreads();
+    a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
 }
 
 // elements of chunk `ch` of table item `it` (gssd_sgd_item / gssd_adam_item): CHUNK, or what is left of the tensor

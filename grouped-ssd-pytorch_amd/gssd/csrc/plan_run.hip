@@ -173,6 +173,8 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_adam_step_f32),
     GSSD_PLAN_FN(gssd_avg_update_f32),
     GSSD_PLAN_FN(gssd_tensor_stats_f32),
+    GSSD_PLAN_FN(gssd_lars_step_f32),
+    GSSD_PLAN_FN(gssd_lamb_step_f32),
     GSSD_PLAN_FN(gssd_self_attn_core_any_f32),
     GSSD_PLAN_FN(gssd_self_attn_flash_bwd_any_f32),
 };

@@ -1,6 +1,7 @@
 """The optimizer step on the device: ``SGD`` (torch.optim.SGD's update rule and state layout, optionally with the gradient-norm clip
 fused in) and a stand-alone ``clip_grad_norm_``, each two launches of csrc/optim.hip over a device table of tensors; ``Adam`` and
-``AdamW`` (torch's rule, state names and checkpoints, the same optional clip) on the same tables and csrc/optim_adam.hip; and what a
+``AdamW`` (torch's rule, state names and checkpoints, the same optional clip) on the same tables and csrc/optim_adam.hip; ``LARS`` and
+``LAMB`` (csrc/optim_lars.hip), the two with a per-tensor trust ratio that is formed and consumed on the device; and what a
 training loop keeps next to its optimizer, ``AveragedModel`` (torch.optim.swa_utils.AveragedModel's layout and checkpoints: an EMA or
 the equal SWA average of the weights, every tensor in ONE launch of csrc/optim_avg.hip, the update count on the device) with an
 ``update_bn`` that works on this engine (torch's sets ``momentum = None``, which the launch plans cannot take); and ``grad_stats`` /
@@ -412,6 +413,223 @@ class AdamW(Adam):
                  capturable=False, differentiable=False, fused=None, max_grad_norm=None):
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
                          differentiable=differentiable, fused=fused, decoupled_weight_decay=True, max_grad_norm=max_grad_norm)
+
+
+# ----------------------------------------------------------------------------------------------
+# layer-wise adaptive rates
+# ----------------------------------------------------------------------------------------------
+def step_launches(n_groups, cap=8):
+    """Update launches of a step over ``n_groups`` param groups: one per ``cap`` groups (the hyperparameters travel by value)."""
+    return max(1, -(-n_groups // cap))
+
+
+class _Ratios:
+    """What a trust-ratio step needs next to its item / chunk table: the items' chunk prefix, their slots in ``trust_ratio`` (the index
+    of the parameter in ``param_groups`` order) and the per-chunk norm records -- all owned by the table they were built for."""
+
+    def __init__(self, table, params, slot_of, device):
+        from .grad_stats import item_chunk_prefix
+        self.chunk0 = torch.from_numpy(item_chunk_prefix([p.numel() for p in params])).to(device)
+        self.slot = torch.tensor([slot_of[id(p)] for p in params], dtype=torch.int32).to(device)
+        self.workspace = torch.empty(lib.gssd_lars_workspace_bytes(table.n_chunks) // 8, device=device, dtype=torch.float64)
+
+
+class _TrustRatio:
+    """Shared by LARS and LAMB: the extra group keys (filled from the defaults in new groups and in loaded checkpoints that lack them)
+    and ``trust_ratio``."""
+    _EXTRA = ()
+
+    def add_param_group(self, param_group):
+        self.defaults.update(self._extra_defaults)          # (torch fills a new group from self.defaults)
+        super().add_param_group(param_group)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for g in self.param_groups:                         # a checkpoint of SGD / Adam has none of the extra keys
+            for k, v in self._extra_defaults.items():
+                g.setdefault(k, v)
+        self._table = None
+
+    def _check_extra(self, gi, g):
+        name = type(self).__name__
+        for k in self._EXTRA:
+            if isinstance(g[k], torch.Tensor):
+                raise NotImplementedError(f'gssd.optim.{name}: {k} must be a Python number')
+            if not g[k] >= 0.0:
+                raise ValueError(f'gssd.optim.{name}: param_groups[{gi}][{k!r}]={g[k]!r} is negative')
+
+    def _ratios(self, table, params, device):
+        """The _Ratios of a freshly built table, and ``trust_ratio`` zeroed (entries of parameters that left the table read 0)."""
+        if table is None:
+            return None
+        order = [p for g in self.param_groups for p in g['params']]
+        if self.trust_ratio is None or self.trust_ratio.numel() != len(order) or self.trust_ratio.device != device:
+            self.trust_ratio = torch.zeros(len(order), device=device, dtype=torch.float32)
+        else:
+            self.trust_ratio.zero_()
+        return _Ratios(table, params, {id(p): i for i, p in enumerate(order)}, device)
+
+
+class LARS(_TrustRatio, SGD):
+    """Layer-wise adaptive rate scaling (You et al. 2017) on ``SGD``'s state and checkpoint format: torch.optim.SGD's rule with the
+    decayed gradient of every parameter TENSOR scaled by its trust ratio, the learning rate outside the momentum buffer --
+
+        r    = layer_adaptation and ||w|| != 0 and ||g'|| != 0 ? trust_coefficient ||w|| / (||g'|| + weight_decay ||w|| + eps) : 1
+        d    = r (g' + weight_decay w);   buf = first ? d : momentum buf + (1 - dampening) d
+        step = nesterov ? d + momentum buf : buf   (momentum 0: step = d);   w -= lr step
+
+    with g' = c g, c the clip coefficient of ``max_grad_norm`` (1 without), ||.|| the 2-norm over one tensor and ||w|| the norm BEFORE
+    the update -- in TWO launches of csrc/optim_lars.hip for all parameters of all groups, clip or no clip (one more per eight groups
+    beyond eight; ``self.launches`` holds the count of the last step).  Norms are summed in fp64 in a fixed order: a step is bitwise
+    reproducible.  A norm that is exactly zero gives r = 1; a NaN or inf norm gives a NaN ratio, which propagates into that tensor as a
+    NaN gradient does in SGD (there is no skip-on-non-finite step).
+
+    Per-group keys next to SGD's: ``trust_coefficient`` (1e-3), ``eps`` (1e-8) and ``layer_adaptation`` (True; the usual recipe puts
+    biases and BatchNorm weights in a group with False, which then takes SGD's step exactly).  They travel in ``param_groups``; a
+    checkpoint of ``gssd.optim.SGD`` / ``torch.optim.SGD`` loads with them filled from the defaults, and a LARS checkpoint loads into
+    those.
+
+    ``self.trust_ratio``: an fp32 device vector with one entry per parameter in ``param_groups`` order, written by the step (None before
+    the first): r for every updated parameter, 1 in a group without adaptation, 0 for a parameter the step did not touch.  The host
+    never reads it; it stands until the next step overwrites it.  ``max_grad_norm`` / ``self.grad_norm`` and everything else are SGD's."""
+    _EXTRA = ('trust_coefficient', 'eps')
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, trust_coefficient=1e-3, eps=1e-8,
+                 layer_adaptation=True, maximize=False, foreach=None, differentiable=False, fused=None, max_grad_norm=None):
+        for k, v in (('trust_coefficient', trust_coefficient), ('eps', eps)):
+            if isinstance(v, torch.Tensor):
+                raise NotImplementedError(f'gssd.optim.LARS: {k} must be a Python number')
+            if not v >= 0.0:
+                raise ValueError(f'Invalid {k} value: {v}')
+        self._extra_defaults = dict(trust_coefficient=trust_coefficient, eps=eps, layer_adaptation=bool(layer_adaptation))
+        self.trust_ratio = None
+        self.launches = 0
+        self._ratio = None         # the _Ratios of self._table
+        super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, maximize=maximize, foreach=foreach,
+                         differentiable=differentiable, fused=fused, max_grad_norm=max_grad_norm)
+
+    def _hyper(self):
+        arr = (_lib.LarsHyper * len(self.param_groups))()
+        for gi, (h, g) in enumerate(zip(arr, self.param_groups)):
+            for name in ('lr', 'weight_decay', 'momentum', 'dampening'):
+                if isinstance(g[name], torch.Tensor):
+                    raise NotImplementedError(f'gssd.optim.LARS: {name} must be a Python number')
+            self._check_extra(gi, g)
+            h.lr, h.weight_decay, h.momentum, h.dampening, h.nesterov = g['lr'], g['weight_decay'], g['momentum'], g['dampening'], \
+                bool(g['nesterov'])
+            h.trust_coefficient, h.eps, h.adapt = g['trust_coefficient'], g['eps'], bool(g['layer_adaptation'])
+        return arr
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        hyper = self._hyper()
+        key = self._table_key() if self._table is not None else None
+        if self._table is None or self._table[1] != key:
+            table, params, first, device = self._build()
+            self._ratio = self._ratios(table, params, device)
+            self._table = (table, self._table_key(), params, first, device)
+        table, _, params, first, device = self._table
+        if table is None:
+            return loss
+        rt = self._ratio
+        clip = self.max_grad_norm is not None
+        with torch.cuda.device(device):
+            check(lib.gssd_lars_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, rt.chunk0.data_ptr(),
+                                         rt.slot.data_ptr(), hyper, len(hyper), rt.workspace.data_ptr(), table.partials.data_ptr(),
+                                         table.n_partials, self.max_grad_norm if clip else -1.0,
+                                         self.grad_norm.data_ptr() if clip else None, self.trust_ratio.data_ptr(), _stream(device)))
+        self.launches = 1 + step_launches(len(hyper))
+        torch.autograd.graph.increment_version(params)
+        if first:
+            self._table = None       # the table carries first-step flags: the next step builds one without them
+        return loss
+
+
+class LAMB(_TrustRatio, Adam):
+    """LAMB (You et al. 2020) on ``Adam``'s state and checkpoint format (``step`` / ``exp_avg`` / ``exp_avg_sq``; there is no amsgrad):
+    Adam's moments with a per-tensor trust ratio on the full update --
+
+        m = b1 m + (1 - b1) g';   v = b2 v + (1 - b2) g'^2
+        u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + weight_decay w        bc1 = 1 - b1^t, bc2 = 1 - b2^t (1 with bias_correction=False)
+        r = layer_adaptation and ||w|| != 0 and ||u|| != 0 ? ||w|| / ||u|| : 1;   w -= lr r u
+
+    with g' = c g, c the clip coefficient of ``max_grad_norm`` (1 without), ||.|| the 2-norm over one tensor and ||w|| the norm BEFORE
+    the update -- in TWO launches of csrc/optim_lars.hip for all parameters of all groups, three with the clip (one more per eight
+    groups beyond eight; ``self.launches`` holds the count of the last step).  The second launch forms u again from the stored moments
+    instead of reading a stored copy: the same traffic, no fourth state tensor.  Norms are summed in fp64 in a fixed order: a step is
+    bitwise reproducible.  A norm that is exactly zero gives r = 1; a NaN or inf norm gives a NaN ratio, which propagates into that tensor
+    as a NaN gradient does in Adam.
+
+    Defaults: lr 1e-3, betas (0.9, 0.999), eps 1e-6, weight_decay 0.01.  Per-group keys next to Adam's: ``bias_correction`` (True) and
+    ``layer_adaptation`` (True; False for biases and BatchNorm weights).  They travel in ``param_groups``; a checkpoint of
+    ``gssd.optim.Adam`` / ``torch.optim.Adam`` loads with them filled from the defaults, and a LAMB checkpoint loads into those (the
+    groups carry Adam's keys, ``amsgrad`` and ``decoupled_weight_decay`` False).
+
+    ``self.trust_ratio`` is LARS's: one fp32 device entry per parameter in ``param_groups`` order, r for every updated parameter, 1 in
+    a group without adaptation, 0 for a parameter the step did not touch, never read by the host.  Step counts, ``max_grad_norm`` /
+    ``self.grad_norm`` and everything else are Adam's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, *, bias_correction=True, layer_adaptation=True,
+                 amsgrad=False, foreach=None, maximize=False, capturable=False, differentiable=False, fused=None, max_grad_norm=None):
+        if amsgrad:
+            raise NotImplementedError('gssd.optim.LAMB: there is no amsgrad')
+        self._extra_defaults = dict(bias_correction=bool(bias_correction), layer_adaptation=bool(layer_adaptation))
+        self.trust_ratio = None
+        self.launches = 0
+        self._ratio = None         # the _Ratios of self._table
+        super().__init__(params, lr, betas, eps, weight_decay, False, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, max_grad_norm=max_grad_norm)
+
+    def _hyper(self):
+        arr = (_lib.LambHyper * len(self.param_groups))()
+        for gi, (h, g) in enumerate(zip(arr, self.param_groups)):
+            for what in _ADAM_OFF + ('amsgrad', 'decoupled_weight_decay'):
+                if g.get(what):
+                    raise NotImplementedError(f'gssd.optim.LAMB: param_groups[{gi}][{what!r}]={g[what]!r} is not implemented')
+            b1, b2 = g['betas']
+            for what, v in (('lr', g['lr']), ('betas', b1), ('betas', b2), ('eps', g['eps']), ('weight_decay', g['weight_decay'])):
+                if isinstance(v, torch.Tensor):
+                    raise NotImplementedError(f'gssd.optim.LAMB: {what} must be a Python number')
+            h.lr, h.beta1, h.beta2 = g['lr'], b1, b2
+            h.one_minus_beta1, h.one_minus_beta2 = 1.0 - b1, 1.0 - b2            # formed in double, rounded once
+            h.eps, h.weight_decay = g['eps'], g['weight_decay']
+            h.bias_correction, h.adapt = bool(g['bias_correction']), bool(g['layer_adaptation'])
+        return arr
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        hyper = self._hyper()
+        if self._table is None or self._table[0] != self._table_key():
+            built = self._build()
+            self._ratio = self._ratios(built[0], built[2], built[4])
+            self._table = (self._table_key(),) + built
+        _, table, norm, params, steps, device = self._table
+        if table is None:
+            return loss
+        rt = self._ratio
+        clip = norm is not None
+        with torch.cuda.device(device):
+            stream = _stream(device)
+            if clip:
+                norm.sumsq(stream)
+            check(lib.gssd_lamb_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, rt.chunk0.data_ptr(),
+                                         rt.slot.data_ptr(), hyper, len(hyper), self._launches + 1, rt.workspace.data_ptr(),
+                                         norm.partials.data_ptr() if clip else None, norm.n_partials if clip else 0,
+                                         self.max_grad_norm if clip else -1.0, self.grad_norm.data_ptr() if clip else None,
+                                         self.trust_ratio.data_ptr(), stream))
+        self.launches = int(clip) + 1 + step_launches(len(hyper))
+        self._launches += 1
+        steps.add_(1.0)
+        torch.autograd.graph.increment_version(params)
+        return loss
 
 
 # (device, ((grad ptr, numel), ...)) -> _Table, the few most recent: building a table costs a host-to-device copy, and a training loop

@@ -1075,6 +1075,57 @@ long long gssd_tensor_stats_workspace_bytes(int n_chunks); /* 32 * n_chunks */
 int gssd_tensor_stats_f32(const gssd_sgd_item* items, int n_items, const gssd_sgd_chunk* chunks, int n_chunks, const int* item_chunk0,
                           void* workspace, double* out, gssd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LARS and LAMB (csrc/optim_lars.hip): layer-wise adaptive rates, the per-tensor trust ratio formed and consumed on the device
+ * ------------------------------------------------------------------------------------------
+ * The same scheme: LARS walks a gssd_sgd_item table, LAMB a gssd_adam_item table (vmax NULL: there is no AMSGrad), both with the chunk
+ * list (gssd_sgd_chunk), one workgroup per chunk in the update launches, 16-byte vectors where every array of the chunk is 16-byte
+ * aligned.  Both need ||.||_2 over ONE tensor before any of its elements moves: a first launch leaves one 16-byte record of two fp64
+ * sums of squares per chunk in `workspace` (gssd_lars_workspace_bytes(n_chunks) bytes, 8-byte aligned, owned by the table), and every
+ * workgroup of the second re-adds the records of ITS item, the chunks item_chunk0[i] .. item_chunk0[i + 1] (a DEVICE prefix of
+ * n_items + 1 ints, as in gssd_tensor_stats_f32), in one fixed order: all chunks of a tensor hold the same ratio r to the bit, two runs
+ * give the same bits, and there is no atomic and no host read.  Squares are formed in fp64; r is formed in fp64 and rounded to fp32 once.
+ * ||w|| is the norm BEFORE the update.  A norm that is exactly 0 gives r = 1; a NaN or inf norm gives a NaN r, which propagates into the
+ * tensor as a NaN gradient does.  The workgroup of an item's first chunk writes r to ratio_out[item_slot[i]] (item_slot: a DEVICE array
+ * of n_items ints; NULL: ratio_out[i]); a group with adapt = 0 writes 1.  c is the clip coefficient of gssd_sgd_step_f32, g' = c g; the
+ * gradients are left as they are.  `hyper` is a HOST array of n_groups entries read during the call; groups beyond 8 take one more
+ * launch per 8; only the first launch writes norm_out. */
+typedef struct gssd_lars_hyper {
+    double lr, weight_decay, trust_coefficient, eps; /* doubles: r is formed from them in fp64; per element lr and weight_decay act rounded */
+    float momentum, dampening;
+    int32_t nesterov;
+    int32_t adapt;  /* 0: r = 1, torch.optim.SGD's rule exactly (biases, BatchNorm weights) */
+} gssd_lars_hyper;
+/* lr / betas are doubles and one_minus_beta* come rounded from the caller's doubles, as in gssd_adam_hyper */
+typedef struct gssd_lamb_hyper {
+    double lr, beta1, beta2;
+    float one_minus_beta1, one_minus_beta2, eps, weight_decay;
+    int32_t bias_correction; /* 0: bc1 = bc2 = 1 */
+    int32_t adapt;           /* 0: r = 1 */
+} gssd_lamb_hyper;
+long long gssd_lars_workspace_bytes(int n_chunks); /* 16 * n_chunks */
+/* LARS, 2 launches with or without the clip.  Launch 1 reads p and g and leaves {sum g^2, sum p^2} per chunk; with max_norm >= 0 it also
+ * leaves in partials[0 .. n_partials) (n_partials = gssd_optim_sumsq_blocks(n_chunks)) the partial sums of g^2 that the clip coefficient
+ * is formed from, so the global norm costs no launch.  max_norm < 0: c = 1, partials and norm_out are not touched.  Launch 2, per item:
+ *   r = adapt && ||w|| != 0 && ||g'|| != 0 ? trust_coefficient ||w|| / (||g'|| + weight_decay ||w|| + eps) : 1       (||g'|| = c ||g||)
+ * and per element, with its group's hyperparameters:
+ *   d = r (c g + weight_decay p);  buf = first ? d : momentum buf + (1 - dampening) d;  step = nesterov ? d + momentum buf : buf
+ *   (buf NULL: step = d);  p -= lr step.      With adapt = 0 this is gssd_sgd_step_f32 bit for bit. */
+int gssd_lars_step_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const int* item_chunk0,
+                       const int* item_slot, const gssd_lars_hyper* hyper, int n_groups, void* workspace, double* partials, int n_partials,
+                       float max_norm, float* norm_out, float* ratio_out, gssd_stream_t stream);
+/* LAMB, 2 launches (the clip's partial sums come from gssd_grad_sumsq_f32, a launch before, as for gssd_adam_step_f32).  Step counts as
+ * there: t by value, item i at step t - items[i].t0; bc1 = 1 - beta1^step and bc2 = 1 - beta2^step are formed per workgroup in fp64.
+ * Launch 1, per element, in fp32:
+ *   m = beta1 m + (1 - beta1) g';   v = beta2 v + (1 - beta2) g' g';   u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + weight_decay p
+ * with u formed from the m, v it stores, and {sum u^2, sum p^2} per chunk.  Launch 2, per item: r = adapt && ||w|| != 0 && ||u|| != 0 ?
+ * ||w|| / ||u|| : 1, and per element p -= (lr r) u, u formed again from the stored m, v and the unchanged p: bit for bit the u whose
+ * norm was taken (u is not stored: that would cost the same traffic and a fourth state-sized array).  With more than 8 groups launch k
+ * runs launch 1's part for the groups [8k, 8k + 8) and launch 2's part for [8k - 8, 8k). */
+int gssd_lamb_step_f32(const gssd_adam_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const int* item_chunk0,
+                       const int* item_slot, const gssd_lamb_hyper* hyper, int n_groups, int64_t t, void* workspace, const double* partials,
+                       int n_partials, float max_norm, float* norm_out, float* ratio_out, gssd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -777,7 +777,10 @@ def test_dcn_col2im_backward(dev, ops):
     assert rel(nchw(dom), om.grad) < TOL
 
 
-@pytest.mark.parametrize('N,D,C2', [(1444, 64, 256), (1100, 64, 256), (300, 64, 256)])
+# (the short maps: one key tile of 32 and its two-stage prologue -- 1, 31, 32 --, just beyond it -- 33, 65 --, the boundary between the
+# 4-wave and the 12-wave instance -- 1024 / 1025 --, a multiple of the 12-wave instance's 192 queries and one beyond -- 1152 / 1153)
+@pytest.mark.parametrize('N,D,C2', [(1444, 64, 256), (1100, 64, 256), (300, 64, 256)]
+                         + [(n, 64, 256) for n in (1, 31, 32, 33, 65, 1024, 1025, 1152, 1153)])
 def test_self_attn_core_x6(dev, N, D, C2):
     """csrc/flash_attn_x6.hip (the fp32 mode's attention core on the bf16 matrix cores, three-plane operands) against float64
     softmax(theta phi^T) g (layers/self_attn.py:68-80) and against the fp32-MFMA core on the same inputs: fp32-equivalent means it

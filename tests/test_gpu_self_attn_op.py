@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attn_core_cases import SENT, core_buffers, core_case     # float64 cases of the cores, shared with tests/test_gpu_attn_cores.py
 from gpu_common import TOL, dev, rel              # noqa: F401  (dev: fixture)
 from gssd import _lib
 from gssd.modules import Self_Attn
@@ -304,37 +305,6 @@ def test_memory_stays_below_one_map(dev):
 # --------------------------------------------------------------------------------------------------
 WIDTHS = [(4, 4), (4, 16), (20, 68), (36, 132), (68, 260), (256, 1024)]
 TOKENS = [(25, 25), (81, 16), (169, 169), (25, 1)]
-SENT = 777.0
-
-
-@functools.lru_cache(maxsize=None)
-def core_case(D, C2, N, Nk, B=2):
-    """float64 inputs (fp32-representable) and references of the attention core and its backward."""
-    g = torch.Generator().manual_seed(D * 7919 + C2 * 31 + N * 3 + Nk)
-    f = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64).float().double()      # noqa: E731
-    th, ks = f(B, N, D) * D ** -0.25 * 1.5, f(B, Nk, D) * D ** -0.25 * 1.5
-    v, dag = f(B, Nk, C2), f(B, N, C2)
-    S = th @ ks.transpose(1, 2)
-    lse = torch.logsumexp(S, dim=-1)
-    P = torch.exp(S - lse.unsqueeze(-1))
-    out = P @ v
-    dvec = (dag * out).sum(-1)
-    dP = dag @ v.transpose(1, 2)
-    dS = P * (dP - dvec.unsqueeze(-1))
-    return dict(th=th, ks=ks, v=v, dag=dag, lse=lse, out=out, dvec=dvec, dq=dS @ ks, dk=dS.transpose(1, 2) @ th, dv=P.transpose(1, 2) @ dag)
-
-
-def core_buffers(c, D, C2, N, Nk, device, B=2):
-    """Device operands with strides wider than the widths: tp rows of 2 D (theta | noise), keys rows of D + 4, gT [B][C2][Nkp]."""
-    Nkp = (Nk + 3) // 4 * 4
-    krow = D + 4
-    tp = torch.randn(B, N, 2 * D)
-    tp[..., :D] = c['th'].float()
-    keys = torch.randn(B, Nk, krow)
-    keys[..., :D] = c['ks'].float()
-    gT = torch.zeros(B, C2, Nkp)
-    gT[..., :Nk] = c['v'].float().transpose(1, 2)
-    return tp.to(device), keys.to(device), krow, gT.to(device), Nkp
 
 
 @pytest.mark.parametrize('N,Nk', TOKENS)

@@ -906,7 +906,8 @@ def test_self_attn_flash_bwd(dev, B, N, D, C2):
     """gssd_self_attn_flash_bwd_bf16 (csrc/sa_flash_bwd.hip) against the float64 backward of attn_g = softmax(theta phi^T) g over the same
     operands: fp32 theta / phi, bf16-rounded g and d(attn_g); lse and D_i = <d(attn_g)_i, attn_g_i> are inputs, as the plan hands them
     over.  Inside, P and dS are rounded to bf16 before they are contracted (relative 2^-9 per element, uncorrelated): 5e-3 of the
-    tensors' scale in L2.  Ragged N exercises the masked last blocks of both the owned and the streamed side."""
+    tensors' scale in L2.  Ragged N exercises the masked last blocks of both the owned and the streamed side.
+    These are the workload sizes; every instance at its tile and block edges, per token: tests/test_gpu_attn_bwd.py::test_flash_bwd_bf16."""
     from gssd import _lib
     rng = np.random.default_rng(N + D)
     th = torch.from_numpy(rng.normal(0, 0.6, size=(B, N, D)).astype(np.float32))

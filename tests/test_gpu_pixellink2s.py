@@ -293,7 +293,8 @@ def test_flash_backward_kernel_vs_float64(dev, B, H, P):
     """gssd_self_attn_flash_bwd_f32 alone against float64: 150 x 150 unpooled (N = Nk = 22 500), pooled P = 75, and ragged token counts
     (N = 1369, Nk = 144: neither a multiple of the 64-token tiles).  Measured on the MI355X: at most 1.5e-6 L2-relative (d theta, 150 x 150
     unpooled), 5.0e-7 on the ragged maps.  The bound 2e-5 keeps a factor of ten over that for fp32 sums of up to 22 500 terms of mixed
-    sign in another order; the test prints the errors of every run."""
+    sign in another order; the test prints the errors of every run.
+    These are the workload sizes; the 64-token tiles' edges and the idle-wave cases: tests/test_gpu_attn_bwd.py::test_flash_bwd_f32."""
     got, want = _flash_case(dev, B, H, P, seed=H * 1000 + P)
     errs = [l2rel(g_, w_) for g_, w_ in zip(got, want)]
     print(f'flash bwd B={B} N={H * H} Nk={P * P}: dq {errs[0]:.2e} dk {errs[1]:.2e} dv {errs[2]:.2e}')

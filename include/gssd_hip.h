@@ -811,7 +811,10 @@ int gssd_pixellink_final_f32(const float* f0, const float* f1, const float* f2, 
  * means of the first four columns.  neg_weight_out (optional) [B][H][W] = the mined-negative mask (criterion.py:47-48).
  * H*W <= 2^20: up to 8192 pixels the threshold comes from a bitonic sort in LDS, above that (the 150 x 150 maps of version "2s") from a
  * radix select over the same keys -- the same threshold, the same mined set.  An image without a negative candidate is an IndexError in the
- * reference; here its pixel_neg term is 0. */
+ * reference; here its pixel_neg term is 0.
+ * Contract at the edges: only neg_pixel_mask == 1 is a candidate (ncand of them); neg_area = min(area * ratio, or 10000 when area == 0, ncand);
+ * ncand == 0: neg_area = 0, neg_weight_out all zero, the denominator is area alone; area + neg_area == 0: pixel_pos and pixel_neg are NaN
+ * (0 / 0, as the reference's division gives), the link terms stay defined. */
 int gssd_pixellink_loss_f32(const float* out1, const float* out2, const long long* pixel_target, const unsigned char* neg_pixel_mask,
                             const float* pixel_pos_weight, const long long* link_target, double* per_image, float* neg_weight_out,
                             int B, int H, int W, int neg_pos_ratio, gssd_stream_t stream);
@@ -823,7 +826,8 @@ int gssd_pixellink_loss_f32(const float* out1, const float* out2, const long lon
  * gssd_pixellink_final_bwd_f32: g[k] (= or += per bit k of accumulate_mask) the gradient of feature k; dw1 fp64 [2*2*nf + 2] = final_1's
  * weight rows then its bias, dw2 fp64 [16*16*nf + 16] likewise (accumulated with atomics: zero them first).
  * gssd_pixellink_loss_bwd_f32: d(out1), d(out2) of sum_k upstream4[k] * loss_k for the four means gssd_pixellink_loss_f32 defines; neg_weight
- * and per_image are that launch's outputs (the mined-negative mask, areas and link weight sums are constants under autograd). */
+ * and per_image are that launch's outputs (the mined-negative mask, areas and link weight sums are constants under autograd).
+ * An image with area + neg_area == 0 (NaN pixel terms in per_image) gets finite zeros in d(out1), never NaN; 1 / B is still applied per image. */
 int gssd_interp_add_bwd_f32(const float* d_out, const float* d_out2, float* d_src, float* d_addend, int B, int Hs, int Ws, int Hd, int Wd,
                             int C, int ld, gssd_stream_t stream);
 int gssd_pixellink_final_bwd_f32(const float* d_out1, const float* d_out2, const float* f0, const float* f1, const float* f2,
@@ -837,7 +841,8 @@ int gssd_pixellink_loss_bwd_f32(const float* out1, const float* out2, const long
  * 1 + rank of the pixel's connected component by its first pixel in raster order (the reference's root_map numbering; the reference
  * stores it as uint8 and wraps beyond 255 components, this does not).  comps [B][max_comp][6] = {pixel count, min x, min y, max x,
  * max y, sum of the positive-class probability} for the first min(max_comp, 1024) components (the rest: count 0); ncomp [B].
- * H*W <= 26624 (150 x 150 = 22500 in version "2s"): the label map lives in LDS, in dynamic LDS above 8192 pixels. */
+ * H*W <= 26624 (150 x 150 = 22500 in version "2s"): the label map lives in LDS, in dynamic LDS above 8192 pixels; beyond that GSSD_EINVAL,
+ * nothing launched.  Both thresholds are strict: a pixel is positive / a link lit when its fp32 probability is > the threshold, not >=. */
 int gssd_pixellink_decode_f32(const float* out1, const float* out2, int* labels, float* comps, int* ncomp, int B, int H, int W,
                               float pixel_thr, float link_thr, int max_comp, gssd_stream_t stream);
 

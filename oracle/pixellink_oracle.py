@@ -133,6 +133,8 @@ def pixel_link_loss(out_1, out_2, pixel_masks, neg_pixel_masks, pixel_pos_weight
             r = 10000
         k = min(r, cand.numel())
         neg_area[i] = k
+        if k == 0:                                                         # no candidate: the reference's topk[-1] raises; nothing is mined
+            continue
         thr = torch.sort(cand).values[k - 1]                               # = -topk(-cand, k)[-1]
         neg_w[i] = (p0[i] <= thr) & (neg_pixel_masks[i] == 1)
     den = area.double() + neg_area.double()

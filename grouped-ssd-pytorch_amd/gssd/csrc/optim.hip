@@ -13,11 +13,6 @@
 
 namespace {
 
-struct HyperArgs {
-    gssd_sgd_hyper h[HYPER_CAP];
-    int g0, ng;                        // this launch updates the groups [g0, g0 + ng)
-};
-
 __global__ __launch_bounds__(THREADS) void grad_sumsq_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks,
                                                              double* partials) {
     __shared__ double red[4];
@@ -44,94 +39,22 @@ __global__ __launch_bounds__(THREADS) void grad_sumsq_kernel(const gssd_sgd_item
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-struct Hyper {
-    float lr, wd, mom, omd;            // omd = 1 - dampening
-    bool nesterov, has_buf, first;
-};
-
-__device__ __forceinline__ void sgd_update(float& p, const float g, float& b, const float c, const Hyper& h) {
-    const float cg = c * g;
-    const float d = h.wd != 0.f ? fmaf(h.wd, p, cg) : cg;
-    float step = d;
-    if (h.has_buf) {
-        b = h.first ? d : fmaf(h.mom, b, h.omd * d);
-        step = h.nesterov ? fmaf(h.mom, b, d) : b;
-    }
-    p = fmaf(-h.lr, step, p);
-}
-
-// NV: 16-byte vectors per thread, known at compile time for a full chunk (all loads of a thread issue before the first use)
-template <int NV>
-__device__ __forceinline__ void sgd_vec(gfloat4* p4, const gfloat4* g4, gfloat4* b4, int nv, const float c, const Hyper& h) {
-    const bool rd_b = h.has_buf && !h.first;
-    f32x4 pv[NV], gv[NV], bv[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = threadIdx.x + k * THREADS;
-        if (i < nv) {
-            pv[k] = p4[i];
-            gv[k] = g4[i];
-            bv[k] = rd_b ? b4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = threadIdx.x + k * THREADS;
-        if (i < nv) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float pe = pv[k][e], be = bv[k][e];
-                sgd_update(pe, gv[k][e], be, c, h);
-                pv[k][e] = pe, bv[k][e] = be;
-            }
-            p4[i] = pv[k];
-            if (h.has_buf) b4[i] = bv[k];
-        }
-    }
-}
-
-__global__ __launch_bounds__(THREADS) void sgd_step_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, const HyperArgs hy,
-                                                           const double* partials, int n_partials, float max_norm, float* norm_out) {
+__global__ __launch_bounds__(THREADS) void sgd_step_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks,
+                                                           const GroupArgs<gssd_sgd_hyper> hy, const double* partials, int n_partials,
+                                                           float max_norm, float* norm_out) {
     __shared__ double red[4];
-    float c = 1.f;
-    if (max_norm >= 0.f) {
-        float total;
-        c = clip_coef(partials, n_partials, max_norm, red, total);
-        if (blockIdx.x == 0 && threadIdx.x == 0 && hy.g0 == 0) norm_out[0] = total;
-    }
+    const float c = max_norm >= 0.f ? clip_step(partials, n_partials, max_norm, red, blockIdx.x == 0 && hy.g0 == 0, norm_out) : 1.f;
     const gssd_sgd_chunk ch = chunks[blockIdx.x];
     const gssd_sgd_item it = items[ch.item];
-    const int gi = __builtin_amdgcn_readfirstlane(it.group) - hy.g0;
-    if (gi < 0 || gi >= hy.ng) return;                    // a group of another launch
-    const gssd_sgd_hyper gh = hy.h[gi];
-    Hyper h;
-    h.lr = gh.lr, h.wd = gh.weight_decay, h.mom = gh.momentum, h.omd = 1.f - gh.dampening;
-    h.nesterov = gh.nesterov != 0, h.has_buf = it.buf != nullptr, h.first = (it.flags & 1) != 0;
-    gfloat* p = as_global(it.p) + ch.off;
-    const gfloat* g = as_global(it.g) + ch.off;
-    gfloat* b = h.has_buf ? as_global(it.buf) + ch.off : nullptr;
-    const int len = chunk_len(it, ch);
-    int done = 0;
-    if (aligned16(p) && aligned16(g) && aligned16(b)) {
-        constexpr int NV = CHUNK / 4 / THREADS;
-        const int nv = len >> 2;
-        sgd_vec<NV>((gfloat4*)p, (const gfloat4*)g, (gfloat4*)b, nv, c, h);
-        done = nv << 2;
-    }
-    for (int i = done + threadIdx.x; i < len; i += THREADS) {
-        float pv = p[i], bv = (h.has_buf && !h.first) ? b[i] : 0.f;
-        sgd_update(pv, g[i], bv, c, h);
-        p[i] = pv;
-        if (h.has_buf) b[i] = bv;
-    }
+    const int gi = group_slot(hy, it.group);
+    if (gi < 0) return;                                   // a group of another launch
+    momentum_chunk<false>(it, ch, c, momentum_of(hy.h[gi], it, 1.f));
 }
 
 __global__ __launch_bounds__(THREADS) void grad_scale_clip_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks,
                                                                   const double* partials, int n_partials, float max_norm, float* norm_out) {
     __shared__ double red[4];
-    float total;
-    const float c = clip_coef(partials, n_partials, max_norm, red, total);
-    if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = total;
+    const float c = clip_step(partials, n_partials, max_norm, red, blockIdx.x == 0, norm_out);
     const gssd_sgd_chunk ch = chunks[blockIdx.x];
     const gssd_sgd_item it = items[ch.item];
     gfloat* g = as_global(it.g) + ch.off;                 // (the table's gradients are plain device memory: this kernel writes them)
@@ -168,16 +91,10 @@ extern "C" int gssd_sgd_step_f32(const gssd_sgd_item* items, const gssd_sgd_chun
     GSSD_CHECK_ARG(items && chunks && n_chunks > 0 && hyper && n_groups > 0);
     const bool clip = max_norm >= 0.f;
     GSSD_CHECK_ARG(!clip || (partials && n_partials > 0 && norm_out));
-    for (int g0 = 0; g0 < n_groups; g0 += HYPER_CAP) {
-        HyperArgs hy = {};
-        hy.g0 = g0;
-        hy.ng = n_groups - g0 < HYPER_CAP ? n_groups - g0 : HYPER_CAP;
-        for (int i = 0; i < hy.ng; ++i) hy.h[i] = hyper[g0 + i];
+    return for_group_batches(hyper, n_groups, [&](const GroupArgs<gssd_sgd_hyper>& hy) {
         hipLaunchKernelGGL(sgd_step_kernel, dim3(n_chunks), dim3(THREADS), 0, as_stream(stream), items, chunks, hy, partials, n_partials,
                            max_norm, norm_out);
-        GSSD_CHECK_LAUNCH();
-    }
-    return GSSD_OK;
+    });
 }
 
 extern "C" int gssd_grad_scale_clip_f32(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const double* partials,

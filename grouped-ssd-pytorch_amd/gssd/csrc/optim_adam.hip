@@ -12,15 +12,8 @@
 
 namespace {
 
-struct AdamHyperArgs {
-    gssd_adam_hyper h[HYPER_CAP];
-    int g0, ng;                        // this launch updates the groups [g0, g0 + ng)
-};
-
-struct Adam {
-    float b1, b2, omb1, omb2;          // omb = 1 - beta, rounded from the host's double
-    float eps, wd, decay;              // decay = 1 - lr wd (AdamW)
-    float step_size, sqrt_bc2;         // lr / (1 - beta1^step), sqrt(1 - beta2^step)
+struct Adam : Moments {
+    float decay, step_size;            // 1 - lr wd (AdamW), lr / (1 - beta1^step)
     bool amsgrad, decoupled;
 };
 
@@ -31,8 +24,7 @@ __device__ __forceinline__ void adam_update(float& p, const float g, float& m, f
     } else if (h.wd != 0.f) {
         d = fmaf(h.wd, p, d);
     }
-    m = fmaf(h.b1, m, h.omb1 * d);
-    v = fmaf(h.omb2 * d, d, h.b2 * v);
+    moments_update(m, v, d, h);
     float vh = v;
     if (h.amsgrad) {
         vmax = (v > vmax || v != v) ? v : vmax;            // torch.maximum: a NaN wins
@@ -42,8 +34,7 @@ __device__ __forceinline__ void adam_update(float& p, const float g, float& m, f
     p = fmaf(-h.step_size, m / den, p);
 }
 
-// NV: 16-byte vectors per thread, known at compile time for a full chunk (all loads of a thread issue before the first use)
-template <int NV>
+// all loads of a thread issue before the first use
 __device__ __forceinline__ void adam_vec(gfloat4* p4, const gfloat4* g4, gfloat4* m4, gfloat4* v4, gfloat4* x4, int nv, const float c,
                                          const Adam& h) {
     f32x4 pv[NV], gv[NV], mv[NV], vv[NV], xv[NV];
@@ -76,27 +67,20 @@ __device__ __forceinline__ void adam_vec(gfloat4* p4, const gfloat4* g4, gfloat4
     }
 }
 
-__global__ __launch_bounds__(THREADS) void adam_step_kernel(const gssd_adam_item* items, const gssd_sgd_chunk* chunks, const AdamHyperArgs hy,
-                                                            const long long t, const double* partials, int n_partials, float max_norm,
-                                                            float* norm_out) {
+__global__ __launch_bounds__(THREADS) void adam_step_kernel(const gssd_adam_item* items, const gssd_sgd_chunk* chunks,
+                                                            const GroupArgs<gssd_adam_hyper> hy, const long long t, const double* partials,
+                                                            int n_partials, float max_norm, float* norm_out) {
     __shared__ double red[4];
-    float c = 1.f;
-    if (max_norm >= 0.f) {
-        float total;
-        c = clip_coef(partials, n_partials, max_norm, red, total);
-        if (blockIdx.x == 0 && threadIdx.x == 0 && hy.g0 == 0) norm_out[0] = total;
-    }
+    const float c = max_norm >= 0.f ? clip_step(partials, n_partials, max_norm, red, blockIdx.x == 0 && hy.g0 == 0, norm_out) : 1.f;
     const gssd_sgd_chunk ch = chunks[blockIdx.x];
     const gssd_adam_item it = items[ch.item];
-    const int gi = __builtin_amdgcn_readfirstlane(it.group) - hy.g0;
-    if (gi < 0 || gi >= hy.ng) return;                    // a group of another launch
+    const int gi = group_slot(hy, it.group);
+    if (gi < 0) return;                                   // a group of another launch
     const gssd_adam_hyper gh = hy.h[gi];
-    const double step = (double)(t - it.t0);
-    const double bc1 = 1.0 - pow(gh.beta1, step), bc2 = 1.0 - pow(gh.beta2, step);
+    double bc1;
     Adam h;
-    h.b1 = (float)gh.beta1, h.b2 = (float)gh.beta2, h.omb1 = gh.one_minus_beta1, h.omb2 = gh.one_minus_beta2;
-    h.eps = gh.eps, h.wd = gh.weight_decay, h.decay = (float)(1.0 - gh.lr * (double)gh.weight_decay);
-    h.step_size = (float)(gh.lr / bc1), h.sqrt_bc2 = (float)sqrt(bc2);
+    static_cast<Moments&>(h) = moments_consts(gh, t - it.t0, true, bc1);
+    h.decay = (float)(1.0 - gh.lr * (double)gh.weight_decay), h.step_size = (float)(gh.lr / bc1);
     h.amsgrad = gh.amsgrad != 0 && it.vmax != nullptr, h.decoupled = gh.decoupled != 0;
     gfloat* p = as_global(it.p) + ch.off;
     const gfloat* g = as_global(it.g) + ch.off;
@@ -106,9 +90,8 @@ __global__ __launch_bounds__(THREADS) void adam_step_kernel(const gssd_adam_item
     const int len = chunk_len(it, ch);
     int done = 0;
     if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(x)) {
-        constexpr int NV = CHUNK / 4 / THREADS;
         const int nv = len >> 2;
-        adam_vec<NV>((gfloat4*)p, (const gfloat4*)g, (gfloat4*)m, (gfloat4*)v, (gfloat4*)x, nv, c, h);
+        adam_vec((gfloat4*)p, (const gfloat4*)g, (gfloat4*)m, (gfloat4*)v, (gfloat4*)x, nv, c, h);
         done = nv << 2;
     }
     for (int i = done + threadIdx.x; i < len; i += THREADS) {
@@ -127,14 +110,8 @@ extern "C" int gssd_adam_step_f32(const gssd_adam_item* items, const gssd_sgd_ch
     GSSD_CHECK_ARG(items && chunks && n_chunks > 0 && hyper && n_groups > 0);
     const bool clip = max_norm >= 0.f;
     GSSD_CHECK_ARG(!clip || (partials && n_partials > 0 && norm_out));
-    for (int g0 = 0; g0 < n_groups; g0 += HYPER_CAP) {
-        AdamHyperArgs hy = {};
-        hy.g0 = g0;
-        hy.ng = n_groups - g0 < HYPER_CAP ? n_groups - g0 : HYPER_CAP;
-        for (int i = 0; i < hy.ng; ++i) hy.h[i] = hyper[g0 + i];
+    return for_group_batches(hyper, n_groups, [&](const GroupArgs<gssd_adam_hyper>& hy) {
         hipLaunchKernelGGL(adam_step_kernel, dim3(n_chunks), dim3(THREADS), 0, as_stream(stream), items, chunks, hy, (long long)t, partials,
                            n_partials, max_norm, norm_out);
-        GSSD_CHECK_LAUNCH();
-    }
-    return GSSD_OK;
+    });
 }

@@ -24,8 +24,7 @@ __device__ __forceinline__ float lerp(const float a, const float b, const float 
     return w < 0.5f ? a + w * d : b - d * omw;
 }
 
-constexpr int NV = 4;                  // 16-byte vectors per thread and array in flight: a full fp32 chunk is one round of them
-
+// NV (optim_util.h) 16-byte vectors per thread and array in flight: a full fp32 chunk is one round of them.
 // a4[i] = lerp(a4[i], b4[i]) for i < nv.  Rounds of NV vectors per thread with all loads of a round issued before its first use and
 // no bounds check inside; what is left of a short chunk one vector at a time.
 __device__ __forceinline__ void lerp_vec(gfloat4* a4, const gfloat4* b4, const int nv, const float w, const float omw) {

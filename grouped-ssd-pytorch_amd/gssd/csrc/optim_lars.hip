@@ -33,45 +33,6 @@ struct NormRec {                        // 16 bytes per chunk
 };
 static_assert(sizeof(NormRec) == 16, "gssd_lars_workspace_bytes");
 
-constexpr int NV = CHUNK / 4 / THREADS; // 16-byte vectors per thread and array of a full chunk
-constexpr int NE = CHUNK / THREADS;     // elements per thread and array
-
-struct LarsHyperArgs {
-    gssd_lars_hyper h[HYPER_CAP];
-    int g0, ng;                         // this launch updates the groups [g0, g0 + ng)
-};
-struct LambHyperArgs {
-    gssd_lamb_hyper h[HYPER_CAP];
-    int g0, ng;
-};
-
-// This thread's share of the `len` elements at a: NE of them and one of the up to three that a vector path leaves over.  What the chunk
-// does not have stays +0, which adds nothing to a sum of squares.
-__device__ __forceinline__ void load_share(const gfloat* a, const int len, float (&x)[NE + 1]) {
-#pragma unroll
-    for (int k = 0; k <= NE; ++k) x[k] = 0.f;
-    if (aligned16(a)) {
-        const gfloat4* a4 = (const gfloat4*)a;
-        const int nv = len >> 2;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int i = threadIdx.x + k * THREADS;
-            if (i < nv) {
-                const f32x4 v = a4[i];
-                x[4 * k] = v.x, x[4 * k + 1] = v.y, x[4 * k + 2] = v.z, x[4 * k + 3] = v.w;
-            }
-        }
-        const int i = (nv << 2) + threadIdx.x;
-        if (i < len) x[NE] = a[i];
-    } else {
-#pragma unroll
-        for (int k = 0; k < NE; ++k) {
-            const int i = threadIdx.x + k * THREADS;
-            if (i < len) x[k] = a[i];
-        }
-    }
-}
-
 __device__ __forceinline__ double sumsq_share(const float (&x)[NE + 1]) {
     double s = 0.0;
 #pragma unroll
@@ -113,108 +74,39 @@ __global__ __launch_bounds__(THREADS) void lars_norm_kernel(const gssd_sgd_item*
     if (partials != nullptr && threadIdx.x == 0) partials[blockIdx.x] = part;
 }
 
-struct Lars {
-    float lr, wd, mom, omd, r;          // omd = 1 - dampening
-    bool nesterov, has_buf, first;
-};
-
-__device__ __forceinline__ void lars_update(float& p, const float g, float& b, const float c, const Lars& h) {
-    const float cg = c * g;
-    const float d = h.r * (h.wd != 0.f ? fmaf(h.wd, p, cg) : cg);      // r = 1 (no adaptation): the product is exact, the rule is SGD's
-    float step = d;
-    if (h.has_buf) {
-        b = h.first ? d : fmaf(h.mom, b, h.omd * d);
-        step = h.nesterov ? fmaf(h.mom, b, d) : b;
-    }
-    p = fmaf(-h.lr, step, p);
-}
-
-__device__ __forceinline__ void lars_vec(gfloat4* p4, const gfloat4* g4, gfloat4* b4, int nv, const float c, const Lars& h) {
-    const bool rd_b = h.has_buf && !h.first;
-    f32x4 pv[NV], gv[NV], bv[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = threadIdx.x + k * THREADS;
-        if (i < nv) {
-            pv[k] = p4[i];
-            gv[k] = g4[i];
-            bv[k] = rd_b ? b4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = threadIdx.x + k * THREADS;
-        if (i < nv) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float pe = pv[k][e], be = bv[k][e];
-                lars_update(pe, gv[k][e], be, c, h);
-                pv[k][e] = pe, bv[k][e] = be;
-            }
-            p4[i] = pv[k];
-            if (h.has_buf) b4[i] = bv[k];
-        }
-    }
-}
-
 __global__ __launch_bounds__(THREADS) void lars_step_kernel(const gssd_sgd_item* items, const gssd_sgd_chunk* chunks, const int n_chunks,
                                                             const int* item_chunk0, const int* item_slot, const NormRec* recs,
-                                                            const LarsHyperArgs hy, const double* partials, int n_partials, float max_norm,
-                                                            float* norm_out, float* ratio_out) {
+                                                            const GroupArgs<gssd_lars_hyper> hy, const double* partials, int n_partials,
+                                                            float max_norm, float* norm_out, float* ratio_out) {
     __shared__ double red[4];
     __shared__ double red2[2][4];
-    float c = 1.f;
-    if (max_norm >= 0.f) {
-        float total;
-        c = clip_coef(partials, n_partials, max_norm, red, total);
-        if (blockIdx.x == 0 && threadIdx.x == 0 && hy.g0 == 0) norm_out[0] = total;
-    }
+    const float c = max_norm >= 0.f ? clip_step(partials, n_partials, max_norm, red, blockIdx.x == 0 && hy.g0 == 0, norm_out) : 1.f;
     const gssd_sgd_chunk ch = chunks[blockIdx.x];
     const gssd_sgd_item it = items[ch.item];
-    const int gi = __builtin_amdgcn_readfirstlane(it.group) - hy.g0;
-    if (gi < 0 || gi >= hy.ng) return;                    // a group of another launch
+    const int gi = group_slot(hy, it.group);
+    if (gi < 0) return;                                   // a group of another launch
     const gssd_lars_hyper gh = hy.h[gi];
     double sg, sp;
     fold_records(recs, item_chunk0, ch.item, n_chunks, sg, sp, red2);
-    Lars h;
-    h.r = 1.f;
+    float r = 1.f;
     if (gh.adapt != 0) {
         const double wn = sqrt(sp), gn = (double)c * sqrt(sg);         // ||g'|| = c ||g||
-        if (wn != 0.0 && gn != 0.0) h.r = (float)(gh.trust_coefficient * wn / (gn + gh.weight_decay * wn + gh.eps));
+        if (wn != 0.0 && gn != 0.0) r = (float)(gh.trust_coefficient * wn / (gn + gh.weight_decay * wn + gh.eps));
     }
-    if (ch.off == 0 && threadIdx.x == 0) ratio_out[item_slot ? item_slot[ch.item] : ch.item] = h.r;
-    h.lr = (float)gh.lr, h.wd = (float)gh.weight_decay, h.mom = gh.momentum, h.omd = 1.f - gh.dampening;
-    h.nesterov = gh.nesterov != 0, h.has_buf = it.buf != nullptr, h.first = (it.flags & 1) != 0;
-    gfloat* p = as_global(it.p) + ch.off;
-    const gfloat* g = as_global(it.g) + ch.off;
-    gfloat* b = h.has_buf ? as_global(it.buf) + ch.off : nullptr;
-    const int len = chunk_len(it, ch);
-    int done = 0;
-    if (aligned16(p) && aligned16(g) && aligned16(b)) {
-        const int nv = len >> 2;
-        lars_vec((gfloat4*)p, (const gfloat4*)g, (gfloat4*)b, nv, c, h);
-        done = nv << 2;
-    }
-    for (int i = done + threadIdx.x; i < len; i += THREADS) {
-        float pv = p[i], bv = (h.has_buf && !h.first) ? b[i] : 0.f;
-        lars_update(pv, g[i], bv, c, h);
-        p[i] = pv;
-        if (h.has_buf) b[i] = bv;
-    }
+    if (ch.off == 0 && threadIdx.x == 0) ratio_out[item_slot ? item_slot[ch.item] : ch.item] = r;
+    momentum_chunk<true>(it, ch, c, momentum_of(gh, it, r));
 }
 
 // ---------------------------------------------------------------------------------------------- LAMB
-struct Lamb {
-    float b1, b2, omb1, omb2;           // omb = 1 - beta, rounded from the host's double
-    float eps, wd, bc1, sqrt_bc2;       // 1 - beta1^step, sqrt(1 - beta2^step): formed in fp64, rounded once (1 without bias correction)
+struct Lamb : Moments {
+    float bc1;                          // 1 - beta1^step, rounded once (1 without bias correction)
 };
 
 __device__ __forceinline__ Lamb lamb_consts(const gssd_lamb_hyper& gh, const long long step) {
-    double bc1 = 1.0, bc2 = 1.0;
-    if (gh.bias_correction != 0) bc1 = 1.0 - pow(gh.beta1, (double)step), bc2 = 1.0 - pow(gh.beta2, (double)step);
+    double bc1;
     Lamb h;
-    h.b1 = (float)gh.beta1, h.b2 = (float)gh.beta2, h.omb1 = gh.one_minus_beta1, h.omb2 = gh.one_minus_beta2;
-    h.eps = gh.eps, h.wd = gh.weight_decay, h.bc1 = (float)bc1, h.sqrt_bc2 = (float)sqrt(bc2);
+    static_cast<Moments&>(h) = moments_consts(gh, step, gh.bias_correction != 0, bc1);
+    h.bc1 = (float)bc1;
     return h;
 }
 
@@ -229,9 +121,7 @@ __device__ __forceinline__ float lamb_u(const float p, const float m, const floa
 
 __device__ __forceinline__ void lamb_moments(const float p, const float g, float& m, float& v, const float c, const Lamb& h, double& su,
                                              double& sp) {
-    const float d = c * g;
-    m = fmaf(h.b1, m, h.omb1 * d);
-    v = fmaf(h.omb2 * d, d, h.b2 * v);
+    moments_update(m, v, c * g, h);
     const float u = lamb_u(p, m, v, h);
     su += (double)u * (double)u;
     sp += (double)p * (double)p;
@@ -271,23 +161,20 @@ __device__ __forceinline__ void lamb_moments_vec(const gfloat4* p4, const gfloat
 // with the registers of its own phase alone; <true, true> is the launch in the middle of a step over more than eight groups.
 template <bool MO, bool UP>
 __global__ __launch_bounds__(THREADS) void lamb_kernel(const gssd_adam_item* items, const gssd_sgd_chunk* chunks, const int n_chunks,
-                                                       const int* item_chunk0, const int* item_slot, NormRec* recs, const LambHyperArgs mo,
-                                                       const LambHyperArgs up, const long long t, const double* partials, int n_partials,
-                                                       float max_norm, float* norm_out, float* ratio_out) {
+                                                       const int* item_chunk0, const int* item_slot, NormRec* recs,
+                                                       const GroupArgs<gssd_lamb_hyper> mo, const GroupArgs<gssd_lamb_hyper> up,
+                                                       const long long t, const double* partials, int n_partials, float max_norm,
+                                                       float* norm_out, float* ratio_out) {
     __shared__ double red[4];
     __shared__ double red2[2][4];
     const gssd_sgd_chunk ch = chunks[blockIdx.x];
     const gssd_adam_item it = items[ch.item];
-    const int grp = __builtin_amdgcn_readfirstlane(it.group);
-    const int gm = grp - mo.g0, gu = grp - up.g0;
-    const bool in_mo = MO && gm >= 0 && gm < mo.ng, in_up = UP && gu >= 0 && gu < up.ng;
+    const int gm = MO ? group_slot(mo, it.group) : -1, gu = UP ? group_slot(up, it.group) : -1;
+    const bool in_mo = gm >= 0, in_up = gu >= 0;
     const bool writes_norm = MO && blockIdx.x == 0 && mo.g0 == 0;
     float c = 1.f;
-    if (MO && max_norm >= 0.f && (in_mo || writes_norm)) {  // (the same answer in every thread of the workgroup)
-        float total;
-        c = clip_coef(partials, n_partials, max_norm, red, total);
-        if (writes_norm && threadIdx.x == 0) norm_out[0] = total;
-    }
+    if (MO && max_norm >= 0.f && (in_mo || writes_norm))    // (the same answer in every thread of the workgroup)
+        c = clip_step(partials, n_partials, max_norm, red, writes_norm, norm_out);
     if (!in_mo && !in_up) return;                         // a group of other launches
     gfloat* p = as_global(it.p) + ch.off;
     gfloat* m = as_global(it.m) + ch.off;
@@ -369,16 +256,10 @@ extern "C" int gssd_lars_step_f32(const gssd_sgd_item* items, const gssd_sgd_chu
     hipLaunchKernelGGL(lars_norm_kernel, dim3(blocks), dim3(THREADS), 0, as_stream(stream), items, chunks, n_chunks, (NormRec*)workspace,
                        clip ? partials : (double*)nullptr);
     GSSD_CHECK_LAUNCH();
-    for (int g0 = 0; g0 < n_groups; g0 += HYPER_CAP) {
-        LarsHyperArgs hy = {};
-        hy.g0 = g0;
-        hy.ng = n_groups - g0 < HYPER_CAP ? n_groups - g0 : HYPER_CAP;
-        for (int i = 0; i < hy.ng; ++i) hy.h[i] = hyper[g0 + i];
+    return for_group_batches(hyper, n_groups, [&](const GroupArgs<gssd_lars_hyper>& hy) {
         hipLaunchKernelGGL(lars_step_kernel, dim3(n_chunks), dim3(THREADS), 0, as_stream(stream), items, chunks, n_chunks, item_chunk0,
                            item_slot, (const NormRec*)workspace, hy, (const double*)partials, n_partials, max_norm, norm_out, ratio_out);
-        GSSD_CHECK_LAUNCH();
-    }
-    return GSSD_OK;
+    });
 }
 
 extern "C" int gssd_lamb_step_f32(const gssd_adam_item* items, const gssd_sgd_chunk* chunks, int n_chunks, const int* item_chunk0,
@@ -389,12 +270,9 @@ extern "C" int gssd_lamb_step_f32(const gssd_adam_item* items, const gssd_sgd_ch
     GSSD_CHECK_ARG(((uintptr_t)workspace & 7) == 0);
     const bool clip = max_norm >= 0.f;
     GSSD_CHECK_ARG(!clip || (partials && n_partials > 0 && norm_out));
-    LambHyperArgs prev = {};                              // the groups whose moments phase the launch before ran (none yet)
+    GroupArgs<gssd_lamb_hyper> prev = {};                 // the groups whose moments phase the launch before ran (none yet)
     for (int g0 = 0; g0 < n_groups || prev.ng > 0; g0 += HYPER_CAP) {
-        LambHyperArgs mo = {};
-        mo.g0 = g0;
-        mo.ng = g0 >= n_groups ? 0 : (n_groups - g0 < HYPER_CAP ? n_groups - g0 : HYPER_CAP);
-        for (int i = 0; i < mo.ng; ++i) mo.h[i] = hyper[g0 + i];
+        const GroupArgs<gssd_lamb_hyper> mo = group_batch(hyper, n_groups, g0);
         auto kernel = mo.ng > 0 ? (prev.ng > 0 ? lamb_kernel<true, true> : lamb_kernel<true, false>) : lamb_kernel<false, true>;
         hipLaunchKernelGGL(kernel, dim3(n_chunks), dim3(THREADS), 0, as_stream(stream), items, chunks, n_chunks, item_chunk0, item_slot,
                            (NormRec*)workspace, mo, prev, (long long)t, partials, n_partials, max_norm, norm_out, ratio_out);

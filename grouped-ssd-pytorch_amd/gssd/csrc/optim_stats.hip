@@ -24,8 +24,6 @@ struct StatsRec {                       // 32 bytes per chunk
 static_assert(sizeof(StatsRec) == 32, "gssd_tensor_stats_workspace_bytes");
 
 constexpr int OUT_COLS = 8;             // g: sumsq, norm, absmax, nonfinite; then the same of p
-constexpr int NV = CHUNK / 4 / THREADS; // 16-byte vectors per thread and array of a full chunk
-constexpr int NE = CHUNK / THREADS;     // elements per thread and array
 constexpr uint32_t ABS_MASK = 0x7fffffffu, EXP_MASK = 0x7f800000u;
 
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
@@ -50,34 +48,6 @@ __device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t* red) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// This thread's share of the `len` elements at a (null: none): NE of them and one of the up to three that a vector path leaves over.
-// What the chunk does not have stays +0, which adds nothing to any of the three statistics -- the second phase needs no bounds.
-__device__ __forceinline__ void load_share(const gfloat* a, const int len, float (&x)[NE + 1]) {
-#pragma unroll
-    for (int k = 0; k <= NE; ++k) x[k] = 0.f;
-    if (a == nullptr) return;
-    if (aligned16(a)) {
-        const gfloat4* a4 = (const gfloat4*)a;
-        const int nv = len >> 2;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int i = threadIdx.x + k * THREADS;
-            if (i < nv) {
-                const f32x4 v = a4[i];
-                x[4 * k] = v.x, x[4 * k + 1] = v.y, x[4 * k + 2] = v.z, x[4 * k + 3] = v.w;
-            }
-        }
-        const int i = (nv << 2) + threadIdx.x;
-        if (i < len) x[NE] = a[i];
-    } else {
-#pragma unroll
-        for (int k = 0; k < NE; ++k) {
-            const int i = threadIdx.x + k * THREADS;
-            if (i < len) x[k] = a[i];
-        }
-    }
 }
 
 struct Acc {

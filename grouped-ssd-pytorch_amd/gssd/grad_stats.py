@@ -15,21 +15,10 @@ import numpy as np
 import torch
 
 from ._lib import GssdError, check, lib
+from .optim_table import _Table, _check_tensor, _stream, item_chunk_prefix      # noqa: F401  (item_chunk_prefix: importable from here)
 
 COLUMNS = ('grad_sumsq', 'grad_norm', 'grad_absmax', 'grad_nonfinite', 'param_sumsq', 'param_norm', 'param_absmax', 'param_nonfinite')
 Row = collections.namedtuple('Row', COLUMNS)      # one row of the table on the host (GradStats.to_host)
-
-
-def item_chunk_prefix(numels, chunk=None):
-    """``item_chunk0`` of gssd_tensor_stats_f32 for a table whose item i has numels[i] elements: int32 [n + 1], item i owns the chunks
-    [prefix[i], prefix[i + 1]) of ``optim.build_chunks(numels)``; an empty item owns none, the last entry is the number of chunks."""
-    from . import optim
-    chunk = chunk or optim.CHUNK
-    counts = [-(-int(n) // chunk) for n in numels]
-    total = sum(counts)
-    if total >= 2 ** 31:
-        raise GssdError(f'gssd.grad_stats: {total} chunks do not fit the 32-bit chunk index')
-    return np.concatenate([np.zeros(1, np.int64), np.cumsum(np.asarray(counts, np.int64))]).astype(np.int32)
 
 
 def monitor_order(n, flushed, history):
@@ -59,41 +48,33 @@ def _entries(parameters):
 
 
 class _StatsTable:
-    """Device copies of gssd_sgd_item[n] / gssd_sgd_chunk[m] / item_chunk0[n + 1], the 32 m bytes of chunk records and the table's own
+    """The _Table (items, chunks, chunk prefix) of (name, tensor) entries, the 32 bytes of chunk records per chunk and the table's own
     output buffer.  Every tensor is validated before anything is built."""
 
     def __init__(self, entries, params):
-        from . import optim
         rows, device = [], None
         for i, (name, t) in enumerate(entries):
             what = f'parameter {name!r} (row {i}, shape {tuple(t.shape)})'
-            optim._check_tensor(t.detach(), what, device)
+            _check_tensor(t.detach(), what, device)
             device = t.device
             g = t.grad
             if g is not None:
-                optim._check_tensor(g, 'the gradient of ' + what, device)
+                _check_tensor(g, 'the gradient of ' + what, device)
                 if g.numel() != t.numel():
                     raise GssdError(f'gssd.grad_stats: the gradient of {what} has shape {tuple(g.shape)}')
             rows.append((t.data_ptr() if params else 0, 0 if g is None else g.data_ptr(), 0, t.numel(), 0, 0))
-        items = np.zeros(len(rows), optim._ITEM)
-        for i, r in enumerate(rows):
-            items[i] = r
-        ci, co = optim.build_chunks(items['n'])
-        chunks = np.zeros(len(ci), optim._CHUNK)
-        chunks['item'], chunks['off'] = ci, co
-        self.device, self.n_items, self.n_chunks = device, len(rows), len(ci)
-        self.items = torch.from_numpy(items.view(np.uint8).copy()).to(device)
-        self.chunks = torch.from_numpy(chunks.view(np.uint8).copy()).to(device) if len(ci) else None
-        self.chunk0 = torch.from_numpy(item_chunk_prefix(items['n'])).to(device)
+        self.table = t = _Table(rows, device, prefix=True)
+        self.device, self.n_items, self.n_chunks = device, t.n_items, t.n_chunks
         n_ws = lib.gssd_tensor_stats_workspace_bytes(self.n_chunks)
         self.workspace = torch.empty(n_ws // 8, device=device, dtype=torch.float64) if n_ws else None
         self.out = torch.zeros(self.n_items + 1, len(COLUMNS), device=device, dtype=torch.float64)
 
     def launch(self, out):
+        t = self.table
         with torch.cuda.device(self.device):
-            check(lib.gssd_tensor_stats_f32(self.items.data_ptr(), self.n_items, self.chunks.data_ptr() if self.n_chunks else None,
-                                            self.n_chunks, self.chunk0.data_ptr(), self.workspace.data_ptr() if self.n_chunks else None,
-                                            out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            check(lib.gssd_tensor_stats_f32(t.items.data_ptr(), self.n_items, t.chunks.data_ptr() if self.n_chunks else None,
+                                            self.n_chunks, t.chunk0.data_ptr(), self.workspace.data_ptr() if self.n_chunks else None,
+                                            out.data_ptr(), _stream(self.device)))
 
 
 # (params, ((data_ptr, grad data_ptr, numel, grad dtype), ...)) -> _StatsTable, the few most recent, as optim.clip_grad_norm_ keeps its
@@ -152,7 +133,6 @@ def grad_stats(parameters, params=True, out=None):
 
     The device table is cached under the tensors' and gradients' storage pointers and sizes and rebuilt (one validation, four small
     uploads) when they change.  With the table built a call is two launches and reads nothing back."""
-    from . import optim
     entries = _entries(parameters)
     if not entries:
         raise GssdError('gssd.grad_stats: no tensor given (and so no device to put the table on)')
@@ -175,7 +155,7 @@ def grad_stats(parameters, params=True, out=None):
     if out is None:
         out = table.out
     else:
-        optim._check_tensor(out, 'out', table.device, torch.float64)
+        _check_tensor(out, 'out', table.device, torch.float64)
         if tuple(out.shape) != (table.n_items + 1, len(COLUMNS)):
             raise GssdError(f'gssd.grad_stats: out has shape {tuple(out.shape)}, the table {(table.n_items + 1, len(COLUMNS))}')
     table.launch(out)

@@ -13,80 +13,164 @@ The reference driver's step (train_lesion_multiphase_v2.py:242-253) then runs on
     ...
     loss.backward(); optimizer.step()                                                                     # :251-253, clip included
 
+The four optimizers are one core, ``_DeviceOptimizer``: it owns step() (closure, hyperparameters, table key, build, clip, launch, step
+counts, version bump), the walk over the parameters with its validation and the refusals; a class adds its state tensors, its item rows,
+its hyper struct and its one library call, and keeps what it built in a ``_Built``.  The device tables themselves -- item and chunk
+layouts, their upload, the aligned slices of one flat tensor that fresh state lives in -- are gssd/optim_table.py, which
+gssd/grad_stats.py shares.
+
 Nothing here reads back to the host.  There is no CPU fallback: a parameter or gradient that is not a contiguous fp32 device tensor
 raises GssdError.
 """
 import copy
-import ctypes as C
 import itertools
 
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import GssdError, check, lib
+from .optim_table import (CHUNK, _ADAM_ITEM, _AVG_ITEM, _CHUNK, _ITEM, _Table, _check_tensor, _stream,      # noqa: F401
+                          build_chunks, flat_views, item_chunk_prefix)
+# per-parameter gradient / weight statistics on the same tables (gssd/grad_stats.py, csrc/optim_stats.hip), re-exported here: they sit
+# in the training loop between backward() and step() like everything below
+from .grad_stats import GradMonitor, GradStats, grad_stats      # noqa: F401
 
-CHUNK = lib.gssd_optim_chunk_elems()      # elements per chunk (csrc/optim.hip)
-
-_ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('buf', np.uint64), ('n', np.int64), ('group', np.int32), ('flags', np.int32)])
-_CHUNK = np.dtype([('off', np.int64), ('item', np.int32), ('reserved', np.int32)])
-_ADAM_ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('vmax', np.uint64), ('n', np.int64),
-                       ('group', np.int32), ('flags', np.int32), ('t0', np.int64)])
-_AVG_ITEM = np.dtype([('dst', np.uint64), ('src', np.uint64), ('n', np.int64), ('kind', np.int32), ('reserved', np.int32)])
 FIRST_STEP = 1
 AVG_LERP, AVG_COPY32, AVG_COPY64 = 0, 1, 2     # gssd_avg_item.kind
 
 
-def build_chunks(numels, chunk=None):
-    """The chunk list of a table whose item i has numels[i] elements: (item index, element offset) arrays, item by item, offsets
-    0, chunk, 2 chunk, ... below numels[i].  Every element lies in exactly one chunk, no chunk crosses an item, an empty item has none."""
-    chunk = chunk or CHUNK
-    items, offs = [], []
-    for i, n in enumerate(numels):
-        k = -(-int(n) // chunk)
-        items.append(np.full(k, i, np.int32))
-        offs.append(np.arange(k, dtype=np.int64) * chunk)
-    if not items:
-        return np.zeros(0, np.int32), np.zeros(0, np.int64)
-    return np.concatenate(items), np.concatenate(offs)
+_PLAIN = (float, int)
+_NO_CLIP = (None, 0, -1.0, None)     # (partials, n_partials, max_norm, norm_out) as every step function takes them
 
 
-class _Table:
-    """Device copies of gssd_sgd_item[n] (or gssd_adam_item[n]) / gssd_sgd_chunk[m] and the partial-sum workspace that goes with them."""
-
-    def __init__(self, rows, device, dtype=_ITEM):
-        # rows: (p ptr, g ptr, buf ptr, numel, group, flags), numel > 0 -- or the fields of ``dtype``, in order
-        items = np.zeros(len(rows), dtype)
-        for i, r in enumerate(rows):
-            items[i] = r
-        ci, co = build_chunks(items['n'])
-        chunks = np.zeros(len(ci), _CHUNK)
-        chunks['item'], chunks['off'] = ci, co
-        self.n_chunks = len(ci)
-        self.n_partials = lib.gssd_optim_sumsq_blocks(self.n_chunks)
-        self.items = torch.from_numpy(items.view(np.uint8).copy()).to(device)
-        self.chunks = torch.from_numpy(chunks.view(np.uint8).copy()).to(device)
-        self.partials = torch.empty(max(self.n_partials, 1), device=device, dtype=torch.float64)
-
-    def sumsq(self, stream, partials=None):
-        partials = self.partials if partials is None else partials
-        check(lib.gssd_grad_sumsq_f32(self.items.data_ptr(), self.chunks.data_ptr(), self.n_chunks, partials.data_ptr(), stream))
+def _holds_tensor(v):
+    """Whether a hyperparameter is a tensor or (betas) a pair with one."""
+    if isinstance(v, (tuple, list)):
+        return isinstance(v[0], torch.Tensor) or isinstance(v[1], torch.Tensor)
+    return isinstance(v, torch.Tensor)
 
 
-def _check_tensor(t, what, device=None, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor) or t.layout != torch.strided or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        d = f'{t.layout}, {t.device}, {t.dtype}, shape {tuple(t.shape)}, strides {t.stride() if t.layout == torch.strided else None}'
-        name = 'fp32' if dtype == torch.float32 else str(dtype).replace('torch.', '')
-        raise GssdError(f'gssd.optim: {what} must be a contiguous {name} tensor on the MI355X (got {d}); there is no CPU fallback')
-    if device is not None and t.device != device:
-        raise GssdError(f'gssd.optim: {what} is on {t.device}, the other tensors on {device}')
+class _Built:
+    """What a step keeps from one call to the next, built for one ``key`` (the optimizer's ``_table_key()``): ``table``, the _Table of
+    the parameters that take part (None: there are none); ``norm``, the gssd_sgd_item _Table of their gradients whose partial sums
+    the clip reads (None without max_grad_norm); ``params``, those parameters; ``steps``, the one host tensor their step counts are
+    views of (None: the rule keeps no count); ``device``; ``first``, whether the table carries first-step flags and so serves one step
+    only; ``ratios``, the _Ratios of a trust-ratio rule (None otherwise); ``clip``, whether it was built for a clipping step."""
+    __slots__ = ('key', 'clip', 'table', 'norm', 'params', 'steps', 'device', 'first', 'ratios')
+
+    def __init__(self, params, device):
+        self.key = self.clip = self.table = self.norm = self.steps = self.ratios = None
+        self.params, self.device, self.first = params, device, False
 
 
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+class _DeviceOptimizer(torch.optim.Optimizer):
+    """The core of the four optimizers: the step() skeleton, the walk over the parameters with its validation, the refusals of what the
+    kernels do not implement, the clip and the version bump.  A subclass supplies what differs: ``_table_key()``, ``_state_tensors()``
+    (the state a parameter brings along), ``_rows()`` (fresh state and the item rows), ``_fill()`` (one group's hyper struct) and
+    ``_launch()`` (its one ``lib.gssd_*_step_f32`` call)."""
+    _OFF = ()              # keys accepted for signature compatibility, in the constructor and in param_groups: they must stay off
+    _NUMBERS = ()          # hyperparameters that must be Python numbers (a tensor would need a host read per step)
+    _HYPER = None          # the ctypes struct of one group's hyperparameters
+    _ITEM_DTYPE = _ITEM    # the item layout of the update kernel
+    _OFF_NAME = None       # the class the flag refusals name (default: the class itself)
+    _SUMSQ_LAUNCH = True   # the clip's norm takes gssd_grad_sumsq_f32, a launch of its own
+    _CHUNK_PREFIX = False  # the table carries the items' chunk prefix
+
+    def __init__(self, params, defaults, flags, max_grad_norm):
+        self._refuse_flags(flags)
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f'Invalid max_grad_norm: {max_grad_norm}')
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None
+        self._launches = 0         # steps that reached the device: the kernels' `t`
+        self._table = None         # the _Built of the last step
+        super().__init__(params, defaults)
+
+    def _refuse_flags(self, values, gi=None):
+        name = self._OFF_NAME or type(self).__name__
+        for k in self._OFF:
+            if values.get(k):
+                where = k if gi is None else f'param_groups[{gi}][{k!r}]'
+                raise NotImplementedError(f'gssd.optim.{name}: {where}={values[k]!r} is not implemented')
+
+    def _hyper(self):
+        # (runs at every step: the two refusals cost a C-level pass over the names when there is nothing to refuse)
+        arr = (self._HYPER * len(self.param_groups))()
+        off, numbers, fill = self._OFF, self._NUMBERS, self._fill
+        for gi, (h, g) in enumerate(zip(arr, self.param_groups)):
+            if any(map(g.get, off)):
+                self._refuse_flags(g, gi)
+            for k in numbers:
+                v = g[k]
+                if v.__class__ not in _PLAIN and _holds_tensor(v):
+                    raise NotImplementedError(f'gssd.optim.{type(self).__name__}: {k} must be a Python number')
+            fill(h, g, gi)
+        return arr
+
+    def _ratios(self, table, params, device):
+        return None
+
+    def _build(self):
+        todo, device = [], None
+        for gi, g in enumerate(self.param_groups):
+            for pi, p in enumerate(g['params']):
+                if p.grad is None:
+                    continue
+                what = f'param_groups[{gi}]["params"][{pi}] (shape {tuple(p.shape)})'
+                _check_tensor(p.detach(), what, device)
+                device = p.device
+                _check_tensor(p.grad, 'the gradient of ' + what, device)
+                if p.grad.shape != p.shape:
+                    raise GssdError(f'gssd.optim: the gradient of {what} has shape {tuple(p.grad.shape)}')
+                if p.numel() == 0:
+                    continue
+                for label, t in self._state_tensors(g, p, what):
+                    _check_tensor(t, f'{label} of ' + what, device)
+                    if t.numel() != p.numel():
+                        raise GssdError(f'gssd.optim: {label} of {what} has {t.numel()} elements')
+                todo.append((gi, g, p))
+        b = _Built([p for _, _, p in todo], device)
+        rows = self._rows(todo, device, b)
+        if rows:
+            b.table = _Table(rows, device, self._ITEM_DTYPE, self._CHUNK_PREFIX)
+            if self.max_grad_norm is not None:
+                b.norm = b.table if self._ITEM_DTYPE is _ITEM else \
+                    _Table([(0, p.grad.data_ptr(), 0, p.numel(), 0, 0) for p in b.params], device)
+                if self.grad_norm is None:
+                    self.grad_norm = torch.zeros((), device=device, dtype=torch.float32)
+        b.ratios = self._ratios(b.table, b.params, device)
+        b.key, b.clip = self._table_key(), self.max_grad_norm is not None
+        return b
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        hyper = self._hyper()
+        clip = self.max_grad_norm is not None
+        b = self._table
+        if b is None or b.key != self._table_key() or b.clip != clip:      # (a max_grad_norm set or cleared later: the norm table)
+            b = self._table = self._build()
+        if b.table is None:
+            return loss
+        with torch.cuda.device(b.device):
+            stream = _stream(b.device)
+            if clip and self._SUMSQ_LAUNCH:
+                b.norm.sumsq(stream)
+            self._launch(b, hyper, (b.norm.partials.data_ptr(), b.norm.n_partials, self.max_grad_norm, self.grad_norm.data_ptr()) if clip
+                         else _NO_CLIP, stream)
+        self._launches += 1
+        if b.steps is not None:
+            b.steps.add_(1.0)
+        torch.autograd.graph.increment_version(b.params)
+        if b.first:
+            self._table = None       # the table carries first-step flags: the next step builds one without them
+        return loss
 
 
-class SGD(torch.optim.Optimizer):
+class SGD(_DeviceOptimizer):
     """torch.optim.SGD's constructor, update rule, ``param_groups`` and ``state[p]['momentum_buffer']`` -- checkpoints go either way --
     with the whole step in ONE launch of csrc/optim.hip for all parameters of all groups.
 
@@ -115,17 +199,15 @@ class SGD(torch.optim.Optimizer):
             raise ValueError(f'Invalid weight_decay value: {weight_decay}')
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError('Nesterov momentum requires a momentum and zero dampening')
-        for name, v in (('maximize', maximize), ('foreach', foreach), ('differentiable', differentiable), ('fused', fused)):
-            if v:
-                raise NotImplementedError(f'gssd.optim.SGD: {name}={v!r} is not implemented')
-        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
-            raise ValueError(f'Invalid max_grad_norm: {max_grad_norm}')
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=False,
                         foreach=None, differentiable=False, fused=None)
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.grad_norm = None
-        self._table = None         # (_Table, key, updated params, table holds first-step flags, device)
-        super().__init__(params, defaults)
+        super().__init__(params, defaults, dict(maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused),
+                         max_grad_norm)
+
+    _OFF = ('maximize', 'foreach', 'differentiable', 'fused')
+    _OFF_NAME = 'SGD'          # (LARS's refusals of SGD's flags name SGD)
+    _NUMBERS = ('lr', 'weight_decay', 'momentum', 'dampening')
+    _HYPER = _lib.SgdHyper
 
     # ------------------------------------------------------------------------------------------
     def _table_key(self):
@@ -144,96 +226,34 @@ class SGD(torch.optim.Optimizer):
                     key.append((p.data_ptr(), grad.data_ptr(), 0 if buf is None else buf.data_ptr(), grad.dtype, grad.numel()))
         return tuple(key)
 
-    def _build(self):
-        todo, device = [], None
-        for gi, g in enumerate(self.param_groups):
-            for name in ('maximize', 'foreach', 'differentiable', 'fused'):
-                if g.get(name):
-                    raise NotImplementedError(f'gssd.optim.SGD: param_groups[{gi}][{name!r}]={g[name]!r} is not implemented')
-            for pi, p in enumerate(g['params']):
-                if p.grad is None:
-                    continue
-                what = f'param_groups[{gi}]["params"][{pi}] (shape {tuple(p.shape)})'
-                _check_tensor(p.detach(), what, device)
-                device = p.device
-                _check_tensor(p.grad, 'the gradient of ' + what, device)
-                if p.grad.shape != p.shape:
-                    raise GssdError(f'gssd.optim: the gradient of {what} has shape {tuple(p.grad.shape)}')
-                if p.numel() == 0:
-                    continue
-                buf = None
-                if g['momentum'] != 0:
-                    buf = self.state[p].get('momentum_buffer') if p in self.state else None
-                    if buf is not None:
-                        _check_tensor(buf, 'the momentum buffer of ' + what, device)
-                        if buf.numel() != p.numel():
-                            raise GssdError(f'gssd.optim: the momentum buffer of {what} has {buf.numel()} elements')
-                todo.append((gi, p, buf, g['momentum'] != 0))
-        # new momentum buffers: 16-byte aligned slices of one flat tensor (the views keep it alive).  All of them on the first step; a
-        # gradient or group that appears later gets a flat tensor of its own
-        fresh = [p for _, p, buf, mom in todo if mom and buf is None]
-        if fresh:
-            flat = torch.empty(sum(-(-p.numel() // 4) * 4 for p in fresh), device=device, dtype=torch.float32)
-            o = 0
-            for p in fresh:
-                self.state[p]['momentum_buffer'] = flat[o:o + p.numel()].view(p.shape)
-                o += -(-p.numel() // 4) * 4
+    def _state_tensors(self, g, p, what):
+        buf = self.state[p].get('momentum_buffer') if g['momentum'] != 0 and p in self.state else None
+        return [] if buf is None else [('the momentum buffer', buf)]
+
+    def _rows(self, todo, device, built):
+        # new momentum buffers: 16-byte aligned slices of one flat tensor.  All of them on the first step; a gradient or group that
+        # appears later gets a flat tensor of its own
+        fresh = [p for _, g, p in todo if g['momentum'] != 0 and self.state[p].get('momentum_buffer') is None]
+        for p, buf in zip(fresh, flat_views(fresh, device)):
+            self.state[p]['momentum_buffer'] = buf
         fresh = set(fresh)
-        rows, params = [], []
-        for gi, p, buf, mom in todo:
-            first = p in fresh
-            if mom and buf is None:
-                buf = self.state[p]['momentum_buffer']
-            rows.append((p.data_ptr(), p.grad.data_ptr(), 0 if buf is None else buf.data_ptr(), p.numel(), gi, FIRST_STEP if first else 0))
-            params.append(p)
-        table = _Table(rows, device) if rows else None
-        if table is not None and self.max_grad_norm is not None and self.grad_norm is None:
-            self.grad_norm = torch.zeros((), device=device, dtype=torch.float32)
-        return table, params, bool(fresh), device
+        built.first = bool(fresh)
+        return [(p.data_ptr(), p.grad.data_ptr(), self.state[p]['momentum_buffer'].data_ptr() if g['momentum'] != 0 else 0, p.numel(), gi,
+                 FIRST_STEP if p in fresh else 0) for gi, g, p in todo]
 
-    def _hyper(self):
-        arr = (_lib.SgdHyper * len(self.param_groups))()
-        for h, g in zip(arr, self.param_groups):
-            for name in ('lr', 'weight_decay', 'momentum', 'dampening'):
-                if isinstance(g[name], torch.Tensor):
-                    raise NotImplementedError(f'gssd.optim.SGD: {name} must be a Python number')
-            h.lr, h.weight_decay, h.momentum, h.dampening, h.nesterov = g['lr'], g['weight_decay'], g['momentum'], g['dampening'], \
-                bool(g['nesterov'])
-        return arr
+    def _fill(self, h, g, gi):
+        h.lr, h.weight_decay, h.momentum, h.dampening, h.nesterov = g['lr'], g['weight_decay'], g['momentum'], g['dampening'], \
+            bool(g['nesterov'])
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        key = self._table_key() if self._table is not None else None
-        if self._table is None or self._table[1] != key:
-            table, params, first, device = self._build()
-            self._table = (table, self._table_key(), params, first, device)
-        table, _, params, first, device = self._table
-        if table is None:
-            return loss
-        hyper = self._hyper()
-        clip = self.max_grad_norm is not None
-        with torch.cuda.device(device):
-            stream = _stream(device)
-            if clip:
-                table.sumsq(stream)
-            check(lib.gssd_sgd_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, hyper, len(hyper),
-                                        table.partials.data_ptr(), table.n_partials, self.max_grad_norm if clip else -1.0,
-                                        self.grad_norm.data_ptr() if clip else None, stream))
-        torch.autograd.graph.increment_version(params)
-        if first:
-            self._table = None       # the table carries first-step flags: the next step builds one without them
-        return loss
+    def _launch(self, b, hyper, clip, stream):
+        check(lib.gssd_sgd_step_f32(*b.table.head, hyper, len(hyper), *clip, stream))
 
 
 _ADAM_OFF = ('maximize', 'foreach', 'capturable', 'differentiable', 'fused')
 _ADAM_STATE = ('exp_avg', 'exp_avg_sq', 'max_exp_avg_sq')
 
 
-class Adam(torch.optim.Optimizer):
+class Adam(_DeviceOptimizer):
     """torch.optim.Adam's constructor, update rule (amsgrad and ``decoupled_weight_decay`` included), ``param_groups`` and state
     ``step`` / ``exp_avg`` / ``exp_avg_sq`` / ``max_exp_avg_sq`` -- checkpoints go either way -- with the whole step in ONE launch of
     csrc/optim_adam.hip for all parameters of all groups (one per eight groups beyond eight).
@@ -272,19 +292,15 @@ class Adam(torch.optim.Optimizer):
             raise ValueError(f'Invalid weight_decay value: {weight_decay}')
         if not (isinstance(betas[0], float) and isinstance(betas[1], float)):
             raise ValueError('betas must be either both floats or both Tensors')
-        for what, v in (('maximize', maximize), ('foreach', foreach), ('capturable', capturable), ('differentiable', differentiable),
-                        ('fused', fused)):
-            if v:
-                raise NotImplementedError(f'gssd.optim.{name}: {what}={v!r} is not implemented')
-        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
-            raise ValueError(f'Invalid max_grad_norm: {max_grad_norm}')
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=False, foreach=None,
                         capturable=False, differentiable=False, fused=None, decoupled_weight_decay=decoupled_weight_decay)
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.grad_norm = None
-        self._launches = 0         # steps that reached the device: the kernel's `t`
-        self._table = None         # (key, _Table, its gradients' _Table for the norm or None, params, their step counts, device)
-        super().__init__(params, defaults)
+        super().__init__(params, defaults, dict(maximize=maximize, foreach=foreach, capturable=capturable, differentiable=differentiable,
+                                                fused=fused), max_grad_norm)
+
+    _OFF = _ADAM_OFF
+    _NUMBERS = ('lr', 'betas', 'eps', 'weight_decay')
+    _HYPER = _lib.AdamHyper
+    _ITEM_DTYPE = _ADAM_ITEM
 
     # ------------------------------------------------------------------------------------------
     def _table_key(self):
@@ -307,103 +323,48 @@ class Adam(torch.optim.Optimizer):
                     key.append((p.data_ptr(), s, grad.data_ptr(), grad.dtype, grad.numel()))
         return tuple(key)
 
-    def _hyper(self):
-        name = type(self).__name__
-        arr = (_lib.AdamHyper * len(self.param_groups))()
-        for gi, (h, g) in enumerate(zip(arr, self.param_groups)):
-            for what in _ADAM_OFF:
-                if g.get(what):
-                    raise NotImplementedError(f'gssd.optim.{name}: param_groups[{gi}][{what!r}]={g[what]!r} is not implemented')
-            b1, b2 = g['betas']
-            for what, v in (('lr', g['lr']), ('betas', b1), ('betas', b2), ('eps', g['eps']), ('weight_decay', g['weight_decay'])):
-                if isinstance(v, torch.Tensor):
-                    raise NotImplementedError(f'gssd.optim.{name}: {what} must be a Python number')
-            h.lr, h.beta1, h.beta2 = g['lr'], b1, b2
-            h.one_minus_beta1, h.one_minus_beta2 = 1.0 - b1, 1.0 - b2            # formed in double, rounded once
-            h.eps, h.weight_decay = g['eps'], g['weight_decay']
-            h.amsgrad, h.decoupled = bool(g['amsgrad']), bool(g.get('decoupled_weight_decay', False))
-        return arr
+    def _fill(self, h, g, gi):
+        b1, b2 = g['betas']
+        h.lr, h.beta1, h.beta2 = g['lr'], b1, b2
+        h.one_minus_beta1, h.one_minus_beta2 = 1.0 - b1, 1.0 - b2            # formed in double, rounded once
+        h.eps, h.weight_decay = g['eps'], g['weight_decay']
+        self._fill_rule(h, g, gi)
 
-    def _build(self):
-        todo, device = [], None
-        for gi, g in enumerate(self.param_groups):
-            for pi, p in enumerate(g['params']):
-                if p.grad is None:
-                    continue
-                what = f'param_groups[{gi}]["params"][{pi}] (shape {tuple(p.shape)})'
-                _check_tensor(p.detach(), what, device)
-                device = p.device
-                _check_tensor(p.grad, 'the gradient of ' + what, device)
-                if p.grad.shape != p.shape:
-                    raise GssdError(f'gssd.optim: the gradient of {what} has shape {tuple(p.grad.shape)}')
-                if p.numel() == 0:
-                    continue
-                s = self.state.get(p) or {}
-                for k in _ADAM_STATE:
-                    if k in s:
-                        _check_tensor(s[k], f'{k} of ' + what, device)
-                        if s[k].numel() != p.numel():
-                            raise GssdError(f'gssd.optim: {k} of {what} has {s[k].numel()} elements')
-                if s and not ('step' in s and 'exp_avg' in s and 'exp_avg_sq' in s):
-                    raise GssdError(f'gssd.optim: the state of {what} holds {sorted(s)}, not step, exp_avg and exp_avg_sq')
-                todo.append((gi, p, bool(g['amsgrad'])))
-        # new moments: 16-byte aligned slices of one flat ZERO tensor per kind (the views keep it alive).  All of them on the first step; a
-        # gradient or group that appears later gets flat tensors of its own
-        pad = lambda p: -(-p.numel() // 4) * 4                                   # noqa: E731
-        fresh = {k: [p for _, p, ams in todo if k not in (self.state.get(p) or {}) and (ams or k != 'max_exp_avg_sq')] for k in _ADAM_STATE}
+    def _fill_rule(self, h, g, gi):
+        h.amsgrad, h.decoupled = bool(g['amsgrad']), bool(g.get('decoupled_weight_decay', False))
+
+    def _state_tensors(self, g, p, what):
+        s = self.state.get(p) or {}
+        for k in _ADAM_STATE:
+            if k in s:
+                yield k, s[k]
+        if s and not ('step' in s and 'exp_avg' in s and 'exp_avg_sq' in s):
+            raise GssdError(f'gssd.optim: the state of {what} holds {sorted(s)}, not step, exp_avg and exp_avg_sq')
+
+    def _rows(self, todo, device, built):
+        # new moments: 16-byte aligned slices of one flat ZERO tensor per kind.  All of them on the first step; a gradient or group that
+        # appears later gets flat tensors of its own
+        fresh = {k: [p for _, g, p in todo if k not in (self.state.get(p) or {}) and (g['amsgrad'] or k != 'max_exp_avg_sq')]
+                 for k in _ADAM_STATE}
         # the step counts of the table's parameters move into ONE host tensor, state[p]['step'] becoming a 0-dim view of it, so that a
         # step counts them all with one add_ (253 host tensors incremented one by one cost more than the launch).  A count that arrives
         # as a device tensor is read back here, once
-        counts = torch.tensor([float(self.state[p]['step']) if self.state.get(p) else 0.0 for _, p, _ in todo], dtype=torch.float32)
-        for i, (_, p, _) in enumerate(todo):
+        built.steps = counts = torch.tensor([float(self.state[p]['step']) if self.state.get(p) else 0.0 for _, _, p in todo],
+                                            dtype=torch.float32)
+        for i, (_, _, p) in enumerate(todo):
             self.state[p]['step'] = counts[i]
         for k in _ADAM_STATE:                                                     # (torch's key order: step, exp_avg, exp_avg_sq, max_...)
-            if fresh[k]:
-                flat = torch.zeros(sum(pad(p) for p in fresh[k]), device=device, dtype=torch.float32)
-                o = 0
-                for p in fresh[k]:
-                    self.state[p][k] = flat[o:o + p.numel()].view(p.shape)
-                    o += pad(p)
-        rows, params = [], []
-        for i, (gi, p, ams) in enumerate(todo):
+            for p, t in zip(fresh[k], flat_views(fresh[k], device, zero=True)):
+                self.state[p][k] = t
+        rows = []
+        for i, (gi, g, p) in enumerate(todo):
             s = self.state[p]
             rows.append((p.data_ptr(), p.grad.data_ptr(), s['exp_avg'].data_ptr(), s['exp_avg_sq'].data_ptr(),
-                         s['max_exp_avg_sq'].data_ptr() if ams else 0, p.numel(), gi, 0, self._launches - int(counts[i])))
-            params.append(p)
-        if not rows:
-            return None, None, params, counts, device
-        table, norm = _Table(rows, device, _ADAM_ITEM), None
-        if self.max_grad_norm is not None:
-            norm = _Table([(0, p.grad.data_ptr(), 0, p.numel(), 0, 0) for p in params], device)
-            if self.grad_norm is None:
-                self.grad_norm = torch.zeros((), device=device, dtype=torch.float32)
-        return table, norm, params, counts, device
+                         s['max_exp_avg_sq'].data_ptr() if g['amsgrad'] else 0, p.numel(), gi, 0, self._launches - int(counts[i])))
+        return rows
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        hyper = self._hyper()
-        if self._table is None or self._table[0] != self._table_key():
-            built = self._build()
-            self._table = (self._table_key(),) + built
-        _, table, norm, params, steps, device = self._table
-        if table is None:
-            return loss
-        clip = norm is not None
-        with torch.cuda.device(device):
-            stream = _stream(device)
-            if clip:
-                norm.sumsq(stream)
-            check(lib.gssd_adam_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, hyper, len(hyper),
-                                         self._launches + 1, norm.partials.data_ptr() if clip else None, norm.n_partials if clip else 0,
-                                         self.max_grad_norm if clip else -1.0, self.grad_norm.data_ptr() if clip else None, stream))
-        self._launches += 1
-        steps.add_(1.0)
-        torch.autograd.graph.increment_version(params)
-        return loss
+    def _launch(self, b, hyper, clip, stream):
+        check(lib.gssd_adam_step_f32(*b.table.head, hyper, len(hyper), self._launches + 1, *clip, stream))
 
 
 class AdamW(Adam):
@@ -424,12 +385,10 @@ def step_launches(n_groups, cap=8):
 
 
 class _Ratios:
-    """What a trust-ratio step needs next to its item / chunk table: the items' chunk prefix, their slots in ``trust_ratio`` (the index
-    of the parameter in ``param_groups`` order) and the per-chunk norm records -- all owned by the table they were built for."""
+    """What a trust-ratio step needs next to its table (which carries the items' chunk prefix): the items' slots in ``trust_ratio`` (the
+    index of the parameter in ``param_groups`` order) and the per-chunk norm records -- owned by the table they were built for."""
 
     def __init__(self, table, params, slot_of, device):
-        from .grad_stats import item_chunk_prefix
-        self.chunk0 = torch.from_numpy(item_chunk_prefix([p.numel() for p in params])).to(device)
         self.slot = torch.tensor([slot_of[id(p)] for p in params], dtype=torch.int32).to(device)
         self.workspace = torch.empty(lib.gssd_lars_workspace_bytes(table.n_chunks) // 8, device=device, dtype=torch.float64)
 
@@ -437,7 +396,7 @@ class _Ratios:
 class _TrustRatio:
     """Shared by LARS and LAMB: the extra group keys (filled from the defaults in new groups and in loaded checkpoints that lack them)
     and ``trust_ratio``."""
-    _EXTRA = ()
+    _CHUNK_PREFIX = True
 
     def add_param_group(self, param_group):
         self.defaults.update(self._extra_defaults)          # (torch fills a new group from self.defaults)
@@ -449,14 +408,6 @@ class _TrustRatio:
             for k, v in self._extra_defaults.items():
                 g.setdefault(k, v)
         self._table = None
-
-    def _check_extra(self, gi, g):
-        name = type(self).__name__
-        for k in self._EXTRA:
-            if isinstance(g[k], torch.Tensor):
-                raise NotImplementedError(f'gssd.optim.{name}: {k} must be a Python number')
-            if not g[k] >= 0.0:
-                raise ValueError(f'gssd.optim.{name}: param_groups[{gi}][{k!r}]={g[k]!r} is negative')
 
     def _ratios(self, table, params, device):
         """The _Ratios of a freshly built table, and ``trust_ratio`` zeroed (entries of parameters that left the table read 0)."""
@@ -492,7 +443,9 @@ class LARS(_TrustRatio, SGD):
     ``self.trust_ratio``: an fp32 device vector with one entry per parameter in ``param_groups`` order, written by the step (None before
     the first): r for every updated parameter, 1 in a group without adaptation, 0 for a parameter the step did not touch.  The host
     never reads it; it stands until the next step overwrites it.  ``max_grad_norm`` / ``self.grad_norm`` and everything else are SGD's."""
-    _EXTRA = ('trust_coefficient', 'eps')
+    _NUMBERS = SGD._NUMBERS + ('trust_coefficient', 'eps')
+    _HYPER = _lib.LarsHyper
+    _SUMSQ_LAUNCH = False      # (the norm launch leaves the clip's partial sums)
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, trust_coefficient=1e-3, eps=1e-8,
                  layer_adaptation=True, maximize=False, foreach=None, differentiable=False, fused=None, max_grad_norm=None):
@@ -504,49 +457,21 @@ class LARS(_TrustRatio, SGD):
         self._extra_defaults = dict(trust_coefficient=trust_coefficient, eps=eps, layer_adaptation=bool(layer_adaptation))
         self.trust_ratio = None
         self.launches = 0
-        self._ratio = None         # the _Ratios of self._table
         super().__init__(params, lr, momentum, dampening, weight_decay, nesterov, maximize=maximize, foreach=foreach,
                          differentiable=differentiable, fused=fused, max_grad_norm=max_grad_norm)
 
-    def _hyper(self):
-        arr = (_lib.LarsHyper * len(self.param_groups))()
-        for gi, (h, g) in enumerate(zip(arr, self.param_groups)):
-            for name in ('lr', 'weight_decay', 'momentum', 'dampening'):
-                if isinstance(g[name], torch.Tensor):
-                    raise NotImplementedError(f'gssd.optim.LARS: {name} must be a Python number')
-            self._check_extra(gi, g)
-            h.lr, h.weight_decay, h.momentum, h.dampening, h.nesterov = g['lr'], g['weight_decay'], g['momentum'], g['dampening'], \
-                bool(g['nesterov'])
-            h.trust_coefficient, h.eps, h.adapt = g['trust_coefficient'], g['eps'], bool(g['layer_adaptation'])
-        return arr
+    def _fill(self, h, g, gi):
+        for k in ('trust_coefficient', 'eps'):
+            if not g[k] >= 0.0:
+                raise ValueError(f'gssd.optim.{type(self).__name__}: param_groups[{gi}][{k!r}]={g[k]!r} is negative')
+        super()._fill(h, g, gi)
+        h.trust_coefficient, h.eps, h.adapt = g['trust_coefficient'], g['eps'], bool(g['layer_adaptation'])
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        hyper = self._hyper()
-        key = self._table_key() if self._table is not None else None
-        if self._table is None or self._table[1] != key:
-            table, params, first, device = self._build()
-            self._ratio = self._ratios(table, params, device)
-            self._table = (table, self._table_key(), params, first, device)
-        table, _, params, first, device = self._table
-        if table is None:
-            return loss
-        rt = self._ratio
-        clip = self.max_grad_norm is not None
-        with torch.cuda.device(device):
-            check(lib.gssd_lars_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, rt.chunk0.data_ptr(),
-                                         rt.slot.data_ptr(), hyper, len(hyper), rt.workspace.data_ptr(), table.partials.data_ptr(),
-                                         table.n_partials, self.max_grad_norm if clip else -1.0,
-                                         self.grad_norm.data_ptr() if clip else None, self.trust_ratio.data_ptr(), _stream(device)))
+    def _launch(self, b, hyper, clip, stream):
+        rt = b.ratios
+        check(lib.gssd_lars_step_f32(*b.table.head, b.table.chunk0.data_ptr(), rt.slot.data_ptr(), hyper, len(hyper), rt.workspace.data_ptr(),
+                                     *clip, self.trust_ratio.data_ptr(), stream))
         self.launches = 1 + step_launches(len(hyper))
-        torch.autograd.graph.increment_version(params)
-        if first:
-            self._table = None       # the table carries first-step flags: the next step builds one without them
-        return loss
 
 
 class LAMB(_TrustRatio, Adam):
@@ -580,56 +505,20 @@ class LAMB(_TrustRatio, Adam):
         self._extra_defaults = dict(bias_correction=bool(bias_correction), layer_adaptation=bool(layer_adaptation))
         self.trust_ratio = None
         self.launches = 0
-        self._ratio = None         # the _Ratios of self._table
         super().__init__(params, lr, betas, eps, weight_decay, False, foreach=foreach, maximize=maximize, capturable=capturable,
                          differentiable=differentiable, fused=fused, max_grad_norm=max_grad_norm)
 
-    def _hyper(self):
-        arr = (_lib.LambHyper * len(self.param_groups))()
-        for gi, (h, g) in enumerate(zip(arr, self.param_groups)):
-            for what in _ADAM_OFF + ('amsgrad', 'decoupled_weight_decay'):
-                if g.get(what):
-                    raise NotImplementedError(f'gssd.optim.LAMB: param_groups[{gi}][{what!r}]={g[what]!r} is not implemented')
-            b1, b2 = g['betas']
-            for what, v in (('lr', g['lr']), ('betas', b1), ('betas', b2), ('eps', g['eps']), ('weight_decay', g['weight_decay'])):
-                if isinstance(v, torch.Tensor):
-                    raise NotImplementedError(f'gssd.optim.LAMB: {what} must be a Python number')
-            h.lr, h.beta1, h.beta2 = g['lr'], b1, b2
-            h.one_minus_beta1, h.one_minus_beta2 = 1.0 - b1, 1.0 - b2            # formed in double, rounded once
-            h.eps, h.weight_decay = g['eps'], g['weight_decay']
-            h.bias_correction, h.adapt = bool(g['bias_correction']), bool(g['layer_adaptation'])
-        return arr
+    _OFF = _ADAM_OFF + ('amsgrad', 'decoupled_weight_decay')
+    _HYPER = _lib.LambHyper
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        hyper = self._hyper()
-        if self._table is None or self._table[0] != self._table_key():
-            built = self._build()
-            self._ratio = self._ratios(built[0], built[2], built[4])
-            self._table = (self._table_key(),) + built
-        _, table, norm, params, steps, device = self._table
-        if table is None:
-            return loss
-        rt = self._ratio
-        clip = norm is not None
-        with torch.cuda.device(device):
-            stream = _stream(device)
-            if clip:
-                norm.sumsq(stream)
-            check(lib.gssd_lamb_step_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, rt.chunk0.data_ptr(),
-                                         rt.slot.data_ptr(), hyper, len(hyper), self._launches + 1, rt.workspace.data_ptr(),
-                                         norm.partials.data_ptr() if clip else None, norm.n_partials if clip else 0,
-                                         self.max_grad_norm if clip else -1.0, self.grad_norm.data_ptr() if clip else None,
-                                         self.trust_ratio.data_ptr(), stream))
-        self.launches = int(clip) + 1 + step_launches(len(hyper))
-        self._launches += 1
-        steps.add_(1.0)
-        torch.autograd.graph.increment_version(params)
-        return loss
+    def _fill_rule(self, h, g, gi):
+        h.bias_correction, h.adapt = bool(g['bias_correction']), bool(g['layer_adaptation'])
+
+    def _launch(self, b, hyper, clip, stream):
+        rt = b.ratios
+        check(lib.gssd_lamb_step_f32(*b.table.head, b.table.chunk0.data_ptr(), rt.slot.data_ptr(), hyper, len(hyper), self._launches + 1,
+                                     rt.workspace.data_ptr(), *clip, self.trust_ratio.data_ptr(), stream))
+        self.launches = int(self.max_grad_norm is not None) + 1 + step_launches(len(hyper))
 
 
 # (device, ((grad ptr, numel), ...)) -> _Table, the few most recent: building a table costs a host-to-device copy, and a training loop
@@ -673,8 +562,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
         stream = _stream(device)
         partials = torch.empty(table.n_partials, device=device, dtype=torch.float64)
         table.sumsq(stream, partials)
-        check(lib.gssd_grad_scale_clip_f32(table.items.data_ptr(), table.chunks.data_ptr(), table.n_chunks, partials.data_ptr(),
-                                           table.n_partials, float(max_norm), norm.data_ptr(), stream))
+        check(lib.gssd_grad_scale_clip_f32(*table.head, partials.data_ptr(), table.n_partials, float(max_norm), norm.data_ptr(), stream))
     torch.autograd.graph.increment_version(grads)
     return norm
 
@@ -738,10 +626,8 @@ class _AvgTable:
         if self.table is None:
             self.count.add_(1)
             return
-        t = self.table
         with torch.cuda.device(self.device):
-            check(lib.gssd_avg_update_f32(t.items.data_ptr(), t.chunks.data_ptr(), t.n_chunks, w, self.count.data_ptr(),
-                                          self.ticket.data_ptr(), _stream(self.device)))
+            check(lib.gssd_avg_update_f32(*self.table.head, w, self.count.data_ptr(), self.ticket.data_ptr(), _stream(self.device)))
         torch.autograd.graph.increment_version(self.written)
 
 
@@ -863,13 +749,8 @@ def update_bn(loader, model, device=None):
             if fold is None or fold[0] != key:
                 # the accumulators: 16-byte aligned slices of one flat tensor; a statistic whose storage moved keeps its accumulator
                 if fold is None:
-                    pad = lambda t: -(-t.numel() // 4) * 4                      # noqa: E731
-                    flat = torch.zeros(sum(pad(t) for t in stats), device=stats[0].device, dtype=torch.float32)
+                    accs = flat_views(stats, stats[0].device, zero=True)
                     count = torch.zeros((), device=stats[0].device, dtype=torch.int64)
-                    accs, o = [], 0
-                    for t in stats:
-                        accs.append(flat[o:o + t.numel()].view(t.shape))
-                        o += pad(t)
                 fold = (key, _AvgTable([(AVG_LERP, a, t, 'running statistic') for a, t in zip(accs, stats)], count))
                 unfold = _AvgTable([(AVG_COPY32, t, a, 'running statistic') for a, t in zip(accs, stats)], torch.zeros_like(count))
             fold[1].launch(-1.0)
@@ -879,8 +760,3 @@ def update_bn(loader, model, device=None):
         for m, mom in zip(bns, momenta):
             m.momentum = mom
         model.train(was_training)
-
-
-# per-parameter gradient / weight statistics on the same tables (gssd/grad_stats.py, csrc/optim_stats.hip), re-exported here: they sit
-# in the training loop between backward() and step() like everything above
-from .grad_stats import GradMonitor, GradStats, grad_stats      # noqa: E402,F401

@@ -249,7 +249,8 @@ SIGNATURES = {
     'gssd_grad_scale_clip_f32': (c_i, [c_fp, c_fp, c_i, c_fp, c_i, c_f, c_fp, c_fp]),
     'gssd_adam_step_f32': (c_i, [c_fp, c_fp, c_i, C.POINTER(AdamHyper), c_i, c_i64, c_fp, c_i, c_f, c_fp, c_fp]),
     'gssd_avg_update_f32': (c_i, [c_fp, c_fp, c_i, c_f, c_fp, c_fp, c_fp]),
-    'gssd_tensor_stats_workspace_bytes': (C.c_longlong, [c_i]),
+    'gssd_grad_accumulate_f32': (c_i, [c_fp, c_fp, c_i, c_d, c_fp, c_i, c_fp, c_fp, c_fp]),
+    'gssd_tensor_stats_workspace_bytes':(C.c_longlong, [c_i]),
     'gssd_tensor_stats_f32': (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp]),
     'gssd_lars_workspace_bytes': (C.c_longlong, [c_i]),
     'gssd_lars_step_f32': (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, C.POINTER(LarsHyper), c_i, c_fp, c_fp, c_i, c_f, c_fp, c_fp, c_fp]),

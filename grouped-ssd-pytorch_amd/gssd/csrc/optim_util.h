@@ -1,5 +1,5 @@
 // The one core of the optimizer kernels (optim.hip: clip + SGD; optim_adam.hip: Adam / AdamW; optim_lars.hip: LARS / LAMB; optim_stats.hip:
-// per-tensor statistics; optim_avg.hip: averaged weights).  What they share lives here once:
+// per-tensor statistics; optim_avg.hip: averaged weights; optim_accum.hip: gradient accumulation).  What they share lives here once:
 //   the chunk scheme       CHUNK / THREADS / NV / NE, chunk_len, the global-address-space casts, load_share (a thread's share of a chunk);
 //   the reductions         block_sum / block_sum2, bit-identical in every thread, and clip_coef / clip_step, the clip coefficient that
 //                          every workgroup derives from the same partial sums;

@@ -172,6 +172,7 @@ const PlanFn g_plan_fns[] = {
     GSSD_PLAN_FN(gssd_grad_scale_clip_f32),
     GSSD_PLAN_FN(gssd_adam_step_f32),
     GSSD_PLAN_FN(gssd_avg_update_f32),
+    GSSD_PLAN_FN(gssd_grad_accumulate_f32),
     GSSD_PLAN_FN(gssd_tensor_stats_f32),
     GSSD_PLAN_FN(gssd_lars_step_f32),
     GSSD_PLAN_FN(gssd_lamb_step_f32),

@@ -4,8 +4,9 @@ fused in) and a stand-alone ``clip_grad_norm_``, each two launches of csrc/optim
 ``LAMB`` (csrc/optim_lars.hip), the two with a per-tensor trust ratio that is formed and consumed on the device; and what a
 training loop keeps next to its optimizer, ``AveragedModel`` (torch.optim.swa_utils.AveragedModel's layout and checkpoints: an EMA or
 the equal SWA average of the weights, every tensor in ONE launch of csrc/optim_avg.hip, the update count on the device) with an
-``update_bn`` that works on this engine (torch's sets ``momentum = None``, which the launch plans cannot take); and ``grad_stats`` /
-``GradMonitor`` (gssd/grad_stats.py, re-exported here): per-parameter norms, maxima and non-finite counts in two launches.
+``update_bn`` that works on this engine (torch's sets ``momentum = None``, which the launch plans cannot take); ``grad_stats`` /
+``GradMonitor`` (gssd/grad_stats.py, re-exported here): per-parameter norms, maxima and non-finite counts in two launches; and
+``GradAccumulator``, the weighted mean of the gradients of k micro-batches in ONE launch of csrc/optim_accum.hip per micro-batch.
 
 The reference driver's step (train_lesion_multiphase_v2.py:242-253) then runs on this library's kernels alone:
 
@@ -29,14 +30,15 @@ import torch
 
 from . import _lib
 from ._lib import GssdError, check, lib
-from .optim_table import (CHUNK, _ADAM_ITEM, _AVG_ITEM, _CHUNK, _ITEM, _Table, _check_tensor, _stream,      # noqa: F401
-                          build_chunks, flat_views, item_chunk_prefix)
+from .optim_table import (ACCUM_ADD, ACCUM_FIRST, ACCUM_SCALE, CHUNK, _ACCUM_ITEM, _ADAM_ITEM, _AVG_ITEM, _CHUNK, _ITEM,      # noqa: F401
+                          _Table, _check_tensor, _stream, accum_plan, build_chunks, flat_views, item_chunk_prefix)
 # per-parameter gradient / weight statistics on the same tables (gssd/grad_stats.py, csrc/optim_stats.hip), re-exported here: they sit
 # in the training loop between backward() and step() like everything below
 from .grad_stats import GradMonitor, GradStats, grad_stats      # noqa: F401
 
 FIRST_STEP = 1
 AVG_LERP, AVG_COPY32, AVG_COPY64 = 0, 1, 2     # gssd_avg_item.kind
+ACCUM_W_F32, ACCUM_RESET, ACCUM_FINALIZE = 1, 2, 4     # launch flags of gssd_grad_accumulate_f32
 
 
 _PLAIN = (float, int)
@@ -710,6 +712,166 @@ class AveragedModel(torch.nn.Module):
         if self._table is None or self._table[0] != key:
             self._table = (key, _AvgTable(pairs, self.n_averaged))
         self._table[1].launch(w)
+
+
+# ----------------------------------------------------------------------------------------------
+# gradient accumulation over micro-batches
+# ----------------------------------------------------------------------------------------------
+class GradAccumulator:
+    """The weighted mean (``average=True``, the default) or sum of the gradients of k micro-batches, ONE launch of csrc/optim_accum.hip
+    per micro-batch for all parameters:
+
+        acc = gssd.optim.GradAccumulator(net.parameters())      # or optimizer.param_groups
+        for x, t in micro_batches:
+            ll, lc = criterion(net(x), t); (ll + lc).backward()
+            acc.add(weight=criterion.num_pos)                   # acc (+)= w g for every parameter with a gradient; then p.grad = None
+        acc.finish()                                            # acc /= sum of the weights;  p.grad = acc
+        optimizer.step(); optimizer.zero_grad()
+
+    ``add(weight=None, last=False)`` consumes every parameter whose ``grad`` is not None (a contiguous fp32 device tensor of the
+    parameter's shape: GssdError otherwise, before anything is written) and sets it to None afterwards, so that the next ``backward()``
+    hands its gradients out directly instead of adding into existing ones tensor by tensor.  ``weight``: None (1.0), a Python number
+    (finite, >= 0: ValueError otherwise) or a 1-element fp32 / fp64 tensor on the parameters' device, such as ``MultiBoxLoss.num_pos`` --
+    read by the kernel, never by the host.  It acts rounded to fp32: acc = w32 g for a parameter's first gradient of the cycle (which
+    ones those are is host bookkeeping; the storage is not read, so nothing is zero-filled), acc = fmaf(w32, g, acc) afterwards.  A
+    parameter without a gradient in some micro-batch is not in that launch and is still divided by the full weight sum, torch's
+    "sum what arrived, divide by k".  ``last=True`` folds the division into this launch; otherwise ``finish()`` makes one scale-only
+    launch.  Both give the same bits: acc * (float)(1 / W), W the fp64 sum of the fp32 weights, kept on the device in ``weight_sum`` (a
+    1-element fp64 tensor; it restarts from 0 with every cycle).  ``W == 0`` gives inf / NaN as a division by zero does in torch.
+
+    ``finish()`` sets ``p.grad`` of every parameter seen in the cycle to its accumulator and clears the cycle.  The accumulators are
+    16-byte aligned slices of ONE flat fp32 tensor allocated once, the same tensor objects in every cycle: an optimizer's table is built
+    once, ``gssd.dist.allreduce_grads`` reduces the flat base in place.  ``launches`` counts the launches so far.  The device tables are
+    cached by (gradient pointers, first / later / scale-only pattern); a loop over one plan's gradients builds each of its patterns once.
+
+    Everything runs on the current stream and nothing synchronises.  Launches of one accumulator must follow each other on one
+    stream."""
+    _TABLES_MAX = 8
+
+    def __init__(self, params, average=True):
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            params = [p for g in params for p in g['params']]
+        self.params, ids = [], set()
+        for p in params:
+            if not isinstance(p, torch.Tensor):
+                raise TypeError(f'gssd.optim.GradAccumulator: parameters or param_groups, not {type(p).__name__}')
+            if id(p) not in ids:
+                ids.add(id(p))
+                self.params.append(p)
+        if not self.params:
+            raise ValueError('gssd.optim.GradAccumulator: got an empty parameter list')
+        devices = sorted({str(p.device) for p in self.params})
+        if len(devices) > 1:
+            raise GssdError(f'gssd.optim.GradAccumulator: the parameters are on {" and ".join(devices)}; make one accumulator per device')
+        self.device = self.params[0].device
+        self.average = bool(average)
+        self.launches = 0
+        self.weight_sum = None
+        self._numels = [p.numel() for p in self.params]
+        self._views = self._ptrs = self._ticket = None
+        if self.device.type == 'cuda':
+            self._views = flat_views(self.params, self.device)
+            self._ptrs = [v.data_ptr() for v in self._views]
+            self.weight_sum = torch.zeros(1, device=self.device, dtype=torch.float64)
+            self._ticket = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self._tables = {}          # key -> (_Table, the accumulators it writes), the few most recent
+        self._clear()
+
+    def _clear(self):
+        self._seen = [False] * len(self.params)
+        self._launched = self._final = False       # this cycle: a launch has run; add(last=True) has closed it
+
+    def _weight(self, weight):
+        """(by-value weight, device pointer or None, launch flags)"""
+        if weight is None:
+            return 1.0, None, 0
+        if isinstance(weight, torch.Tensor):
+            if weight.layout != torch.strided or not weight.is_cuda or weight.device != self.device or weight.numel() != 1 or \
+                    weight.dtype not in (torch.float32, torch.float64):
+                raise GssdError(f'gssd.optim.GradAccumulator: a tensor weight must have one fp32 or fp64 element on {self.device} (got '
+                                f'{weight.dtype}, {weight.device}, shape {tuple(weight.shape)}); pass a Python number otherwise')
+            return 0.0, weight.data_ptr(), ACCUM_W_F32 if weight.dtype == torch.float32 else 0
+        if isinstance(weight, (int, float)) and not isinstance(weight, bool):
+            w = float(weight)
+            if not (w >= 0.0 and w != float('inf')):
+                raise ValueError(f'gssd.optim.GradAccumulator: weight={weight!r} must be finite and not negative')
+            return w, None, 0
+        raise GssdError(f'gssd.optim.GradAccumulator: weight must be None, a Python number or a 1-element device tensor, not '
+                        f'{type(weight).__name__}')
+
+    def _table(self, plan, grads, ptrs):
+        """The cached (_Table, written accumulators) of a launch plan, by (gradient pointers, plan); the gradients are validated when a
+        table is built.  torch itself holds an assigned ``grad`` to the parameter's shape, dtype and device, so a gradient at a known
+        address can differ from the validated one in its strides alone: ``ptrs`` carries -1 for one that is not contiguous, which no
+        cached key has."""
+        key = (tuple(ptrs), tuple(plan))
+        hit = self._tables.pop(key, None)
+        if hit is None:
+            for i, g in enumerate(grads):
+                if g is None:
+                    continue
+                p = self.params[i]
+                what = f'the gradient of parameter {i} (shape {tuple(p.shape)})'
+                _check_tensor(g, what, self.device)
+                if g.shape != p.shape:
+                    raise GssdError(f'gssd.optim: {what} has shape {tuple(g.shape)}')
+            rows = [(self._ptrs[i], 0 if kind == ACCUM_SCALE else ptrs[i], self._numels[i], int(kind == ACCUM_FIRST), 0) for i, kind in plan]
+            hit = (_Table(rows, self.device, _ACCUM_ITEM), [self._views[i] for i, _ in plan])
+            while len(self._tables) >= self._TABLES_MAX:
+                self._tables.pop(next(iter(self._tables)))
+        self._tables[key] = hit
+        return hit
+
+    def _launch(self, table, written, w, w_dev, flags):
+        if not self._launched:
+            flags |= ACCUM_RESET
+        with torch.cuda.device(self.device):
+            check(lib.gssd_grad_accumulate_f32(*table.head, w, w_dev, flags, self.weight_sum.data_ptr(), self._ticket.data_ptr(),
+                                               _stream(self.device)))
+        self.launches += 1
+        self._launched = True
+        torch.autograd.graph.increment_version(written)
+
+    @torch.no_grad()
+    def add(self, weight=None, last=False):
+        w, w_dev, flags = self._weight(weight)
+        if self._final:
+            raise GssdError('gssd.optim.GradAccumulator: add(last=True) has closed this cycle; call finish() before the next add()')
+        grads = [p.grad for p in self.params]
+        has = [g is not None for g in grads]
+        if True not in has:
+            raise GssdError('gssd.optim.GradAccumulator.add(): no parameter has a gradient; call backward() before add()')
+        ptrs = [0 if g is None else g.data_ptr() if g.is_contiguous() else -1 for g in grads]
+        if self._ptrs is not None and True in map(int.__eq__, ptrs, self._ptrs):
+            for i, (a, b) in enumerate(zip(ptrs, self._ptrs)):
+                if a == b and self._numels[i]:
+                    raise GssdError(f'gssd.optim.GradAccumulator.add(): the gradient of parameter {i} (shape {tuple(grads[i].shape)}) is '
+                                    f'the accumulator itself, so autograd has summed into it; call optimizer.zero_grad() '
+                                    f'(set_to_none=True) after the step that follows finish()')
+        fin = bool(last) and self.average
+        plan = accum_plan(self._numels, has, self._seen, fin)
+        table, written = self._table(plan, grads, ptrs)
+        if plan:
+            self._launch(table, written, w, w_dev, flags | (ACCUM_FINALIZE if fin else 0))
+        for i, p in enumerate(self.params):
+            if has[i]:
+                p.grad = None
+                self._seen[i] = True
+        self._final = bool(last)
+
+    @torch.no_grad()
+    def finish(self):
+        if True not in self._seen:
+            raise GssdError('gssd.optim.GradAccumulator.finish(): no add() since the last finish(); call add() after every backward()')
+        if self.average and not self._final:
+            plan = accum_plan(self._numels, [False] * len(self.params), self._seen, True)
+            if plan:
+                self._launch(*self._table(plan, [None] * len(self.params), [0] * len(self.params)), 0.0, None, ACCUM_FINALIZE)
+        for p, v, s in zip(self.params, self._views, self._seen):
+            if s:
+                p.grad = v
+        self._clear()
 
 
 @torch.no_grad()

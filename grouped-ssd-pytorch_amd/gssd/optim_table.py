@@ -14,6 +14,26 @@ _CHUNK = np.dtype([('off', np.int64), ('item', np.int32), ('reserved', np.int32)
 _ADAM_ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64), ('vmax', np.uint64), ('n', np.int64),
                        ('group', np.int32), ('flags', np.int32), ('t0', np.int64)])
 _AVG_ITEM = np.dtype([('dst', np.uint64), ('src', np.uint64), ('n', np.int64), ('kind', np.int32), ('reserved', np.int32)])
+_ACCUM_ITEM = np.dtype([('dst', np.uint64), ('src', np.uint64), ('n', np.int64), ('flags', np.int32), ('reserved', np.int32)])
+
+ACCUM_ADD, ACCUM_FIRST, ACCUM_SCALE = 0, 1, 2     # what accum_plan() gives an item to do
+
+
+def accum_plan(numels, has_grad, seen, finalize):
+    """The items of one gssd_grad_accumulate_f32 launch, as (parameter index, ACCUM_*) in parameter order, for parameters of ``numels``
+    elements of which ``has_grad[i]`` bring a gradient in this micro-batch and ``seen[i]`` brought one earlier in the cycle.  A gradient
+    that is the parameter's first of the cycle is ACCUM_FIRST (the accumulator is written, not read), a later one ACCUM_ADD; a parameter
+    without one is not in the launch -- unless the launch is the cycle's last (``finalize``) and the parameter was seen: then it is
+    ACCUM_SCALE, an item without source that only takes the division.  Empty parameters are skipped."""
+    plan = []
+    for i, (n, g, s) in enumerate(zip(numels, has_grad, seen)):
+        if n == 0:
+            continue
+        if g:
+            plan.append((i, ACCUM_ADD if s else ACCUM_FIRST))
+        elif s and finalize:
+            plan.append((i, ACCUM_SCALE))
+    return plan
 
 
 def build_chunks(numels, chunk=None):
@@ -42,8 +62,9 @@ def item_chunk_prefix(numels, chunk=None):
 
 
 class _Table:
-    """Device copies of the items (gssd_sgd_item[n], or gssd_adam_item / gssd_avg_item by ``dtype``) and their gssd_sgd_chunk[m], the
-    partial-sum workspace that goes with them and, with ``prefix``, the items' chunk prefix ``chunk0`` (int32 [n + 1])."""
+    """Device copies of the items (gssd_sgd_item[n], or gssd_adam_item / gssd_avg_item / gssd_accum_item by ``dtype``) and their
+    gssd_sgd_chunk[m], the partial-sum workspace that goes with them and, with ``prefix``, the items' chunk prefix ``chunk0`` (int32
+    [n + 1])."""
 
     def __init__(self, rows, device, dtype=_ITEM, prefix=False):
         # rows: the fields of ``dtype``, in order -- (p ptr, g ptr, buf ptr, numel, group, flags) by default

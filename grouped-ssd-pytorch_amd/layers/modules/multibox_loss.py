@@ -18,17 +18,19 @@ from data.config import v2 as cfg
 
 class _MultiBoxLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loc, conf, priors, tg, n_gt, threshold, negpos_ratio, variance, global_n=False, fused=None):
+    def forward(ctx, loc, conf, priors, tg, n_gt, threshold, negpos_ratio, variance, global_n=False, fused=None, keep=None):
         st = ops.multibox_loss_forward(loc.detach(), conf.detach(), priors, tg, n_gt, threshold, negpos_ratio,
                                        variance, global_n=global_n, fused=fused)
         ctx.st = st
+        if keep is not None:
+            keep.append(st['n_total'])               # the normaliser, for MultiBoxLoss.num_pos: not an output of the graph
         losses = st['losses']
         return losses[0], losses[1]
 
     @staticmethod
     def backward(ctx, g_l, g_c):
         dloc, dconf = ops.multibox_loss_backward(ctx.st, g_l, g_c)
-        return dloc, dconf, None, None, None, None, None, None, None, None
+        return dloc, dconf, None, None, None, None, None, None, None, None, None
 
 
 class MultiBoxLoss(nn.Module):
@@ -50,6 +52,9 @@ class MultiBoxLoss(nn.Module):
         self.global_normalizer = False
         # None: the forward's launch sequence follows GSSD_FUSE_LOSS (default: the fused two launches); True / False choose it here
         self.fused = None
+        # extension: after each forward the 1-element fp64 device tensor that holds the normaliser N the returned losses were divided by
+        # (with global_normalizer the all-reduced one) -- the weight of this micro-batch for gssd.optim.GradAccumulator.add()
+        self.num_pos = None
 
     def forward(self, predictions, targets, fused=None):
         loc_data, conf_data, priors = predictions
@@ -58,6 +63,9 @@ class MultiBoxLoss(nn.Module):
         if priors.device != loc_data.device:
             priors = priors.to(loc_data.device)
         tg, n_gt = ops.pack_targets(targets, loc_data.device)
-        return _MultiBoxLossFn.apply(loc_data, conf_data, priors.detach().contiguous(), tg, n_gt, float(self.threshold),
-                                     int(self.negpos_ratio), (float(self.variance[0]), float(self.variance[1])),
-                                     bool(self.global_normalizer), self.fused if fused is None else fused)
+        keep = []
+        losses = _MultiBoxLossFn.apply(loc_data, conf_data, priors.detach().contiguous(), tg, n_gt, float(self.threshold),
+                                       int(self.negpos_ratio), (float(self.variance[0]), float(self.variance[1])),
+                                       bool(self.global_normalizer), self.fused if fused is None else fused, keep)
+        self.num_pos = keep[0]
+        return losses

@@ -1131,6 +1131,34 @@ int gssd_lamb_step_f32(const gssd_adam_item* items, const gssd_sgd_chunk* chunks
                        const int* item_slot, const gssd_lamb_hyper* hyper, int n_groups, int64_t t, void* workspace, const double* partials,
                        int n_partials, float max_norm, float* norm_out, float* ratio_out, gssd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Gradient accumulation (csrc/optim_accum.hip): the weighted sum, or mean, of micro-batch gradients, one launch per micro-batch
+ * ------------------------------------------------------------------------------------------
+ * The same scheme: a device table of items, the same chunk list (gssd_sgd_chunk), one workgroup per chunk, 16-byte vectors where dst and
+ * src are both 16-byte aligned at the chunk's offset, element by element otherwise.  dst is updated in place; src is only read. */
+#define GSSD_ACCUM_FIRST 1    /* gssd_accum_item.flags bit 0: the first gradient of this accumulator's cycle: dst is written, not read */
+typedef struct gssd_accum_item {
+    float* dst;       /* the accumulator, n floats */
+    const float* src; /* this micro-batch's gradient; NULL: scale-only (the item takes part in the final division alone) */
+    int64_t n;
+    int32_t flags;    /* GSSD_ACCUM_FIRST */
+    int32_t reserved;
+} gssd_accum_item;
+#define GSSD_ACCUM_W_F32 1    /* launch flags: *w_dev is a float (default: a double, as gssd_multibox_loss_forward_f32 leaves n_total) */
+#define GSSD_ACCUM_RESET 2    /* the first launch of a cycle: the weight sum starts from 0, whatever *weight_sum holds */
+#define GSSD_ACCUM_FINALIZE 4 /* the last launch of a cycle: every element is divided by the new weight sum after its update */
+/* The weight of this micro-batch is w (w_dev NULL; a negative or NaN w is refused) or the one element at w_dev on the device, rounded
+ * to w32 = (float)w.  W_prev = *weight_sum is read on the device by every workgroup before it writes anything, W_new = (RESET ? 0 :
+ * W_prev) + (double)w32, and the same launch leaves *weight_sum = W_new, stored by the workgroup that finishes last (`ticket`: one 32-bit
+ * word that belongs to the accumulator, zero before the first launch and zero again after every launch, as in gssd_avg_update_f32).
+ * Per element, in exactly these forms (results are bitwise reproducible):
+ *   FIRST item: dst = w32 * src;   otherwise: dst = fmaf(w32, src, dst);   with FINALIZE, then: dst = dst * inv, inv = (float)(1.0 / W_new)
+ * and an item with src NULL takes only the `* inv` (without FINALIZE it is left alone).  A launch with w = 0 over src-less items is the
+ * division on its own.  IEEE semantics: W_new == 0 gives inf / NaN, as torch's division would.  The host never reads w or W.  Launches
+ * that share a ticket word or a weight sum must follow each other on one stream. */
+int gssd_grad_accumulate_f32(const gssd_accum_item* items, const gssd_sgd_chunk* chunks, int n_chunks, double w, const void* w_dev,
+                             int flags, double* weight_sum, uint32_t* ticket, gssd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
